@@ -3,8 +3,10 @@
 Run in the build container (needs /root/reference):  python oracle/make_golden_init.py
 Constructs the reference's own ViTEncoder / ViTDecoder / VectorQuantizer (+ the two stock nn.Linear of vitvqgan.py:38-39) in the
 reference's construction order (vitvqgan.py:34-39) under torch.manual_seed(seed) and stores, per tensor, its float64 sum, its sum of
-squares and its first 4 values — enough to tell a different RNG stream apart with certainty, small enough to commit.
+squares and its first 4 values — enough to tell a different RNG stream apart with certainty, small enough to commit — the SHA-256 of its
+dtype, shape and bytes, so that the tests compare every tensor bit for bit without the reference checkout, and the state dict's key order.
 TEST INFRASTRUCTURE ONLY."""
+import hashlib
 import os
 import sys
 
@@ -40,6 +42,12 @@ def fingerprint(sd):
     return names, fp
 
 
+def digests(sd):
+    """per tensor (sorted names): SHA-256 of dtype, shape and bytes — equal digests = torch.equal"""
+    return [hashlib.sha256(f"{sd[n].dtype} {tuple(sd[n].shape)} ".encode() + sd[n].detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+            for n in sorted(sd)]
+
+
 if __name__ == "__main__":
     L, Q = RL.load_layers(), RL.load_quantizers()
     out = {}
@@ -47,6 +55,7 @@ if __name__ == "__main__":
         sd, tail = build(L, Q, case, 0)
         names, fp = fingerprint(sd)
         out[f"{case}_names"], out[f"{case}_fp"], out[f"{case}_tail"] = np.array(names), fp, tail.numpy()
+        out[f"{case}_sha256"], out[f"{case}_order"] = np.array(digests(sd)), np.array(list(sd))
     path = os.path.join(os.path.dirname(HERE), "tests", "golden", "init_seed.npz")
     np.savez_compressed(path, **out)
     print("wrote", path, {k: v.shape for k, v in out.items()})

@@ -44,7 +44,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo_accounts_for_every_gradient_byte()
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-                        str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline"],
+                        str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
@@ -64,16 +64,23 @@ def _json_lines(stdout):
     return [ln for ln in stdout.splitlines() if ln.startswith('{"metric"')]
 
 
-def test_bench_bare_single_gpu_form_prints_one_json_line():
-    """the driver's N = 1 command, `python bench.py --gpus 1 ...` with no launcher environment: exactly ONE JSON line on stdout"""
+def test_bench_bare_single_gpu_form_prints_one_json_line(tmp_path):
+    """the driver's N = 1 command, `python bench.py --gpus 1 ...` with no launcher environment: exactly ONE JSON line on stdout; --dump-outputs writes
+    the last timed step's outputs as float32 / float64 .npy files, 64 MB at most"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dump = tmp_path / "outputs"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline",
-                        "--no-parity-mode"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--no-parity-mode", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout[-2000:]
     line = json.loads(lines[0])
-    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    files = {f.name: np.load(f) for f in dump.glob("*.npy")}
+    assert {"loss.npy", "xrec.npy", "indices.npy", "h.npy", "master_weights_sample.npy"} <= set(files), sorted(files)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert sum(f.stat().st_size for f in dump.glob("*.npy")) <= 64 << 20
+    assert files["xrec.npy"].shape == (4, 3, 256, 256) and float(files["loss.npy"]) == line["final_loss"]
 
 
 def test_bench_bare_multi_gpu_form_launches_itself_two_ranks_over_gloo():
@@ -85,7 +92,7 @@ def test_bench_bare_multi_gpu_form_launches_itself_two_ranks_over_gloo():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env.update(ENH_DIST_BACKEND="gloo", ENH_FORCE_DEVICE="0", MASTER_PORT=str(port))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline",
-                        "--no-parity-mode"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--no-parity-mode", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout[-2000:]
@@ -96,7 +103,7 @@ def test_bench_bare_multi_gpu_form_launches_itself_two_ranks_over_gloo():
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (RCCL refuses two ranks per device)")
 def test_bench_bare_multi_gpu_form_over_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "ENH_DIST_BACKEND", "ENH_FORCE_DEVICE")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-parity-mode"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-parity-mode", "--full"],
                        capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = _json_lines(r.stdout)

@@ -28,11 +28,12 @@ case $task in
 suite)
   timeout 2000 python -m pytest tests -m gpu -q --no-header -p no:cacheprovider 2>&1 | tee gpurun_out/gpu_suite.log | tail -8 ;;
 bench)
+  set -- --full "$@"      # the headline line with every block beyond it (roofline, kernels, vq_match, parity_mode, cpu_baseline)
   timeout 900 python bench.py "$@" 2>gpurun_out/bench_latest.err | tee gpurun_out/bench_latest.json | line bench ;;
 lib-ab)
   for i in 1 2; do for lib in "$@"; do
     [ -f $R/enhancing-transformers_amd/lib/$lib ] || { echo "missing $lib"; continue; }
-    ENH_HIP_LIB=$R/enhancing-transformers_amd/lib/$lib timeout 300 python bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-parity-mode 2>/dev/null | python -c "
+    ENH_HIP_LIB=$R/enhancing-transformers_amd/lib/$lib timeout 300 python bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-parity-mode 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']
 row=lambda n: next((f\"{v['total_ms']/v['launches']:.4f}\" for kk,v in k.items() if kk.startswith(n)), '-')
@@ -44,7 +45,7 @@ landing-pmc)
   bash tools/r5_pmc_landing.sh ;;
 parity-ab)
   for f in 1 0; do
-    ENH_X3_FUSED_SPLIT=$f timeout 900 python bench.py --steps 10 --warmup 3 2>/dev/null | tee gpurun_out/bench_parity_fused$f.json | python -c "
+    ENH_X3_FUSED_SPLIT=$f timeout 900 python bench.py --full --steps 10 --warmup 3 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); pm=d.get('parity_mode',{})
 print('fused=$f headline', d['value'], json.dumps({k:v for k,v in pm.items() if k not in ('note','x3_whole_forward_kernels')}))
@@ -56,7 +57,7 @@ attn-lab)
 configs)
   ( for spec in "$@"; do
       IFS=: read cfg b g <<< "$spec"
-      timeout 400 python bench.py --config $cfg --batch $b --steps ${STEPS:-8} --warmup ${WARMUP:-3} --no-cpu-baseline --no-parity-mode ${g:+--graphs} 2>/dev/null | line "$cfg B=$b ${g:+graphs}"
+      timeout 400 python bench.py --full --config $cfg --batch $b --steps ${STEPS:-8} --warmup ${WARMUP:-3} --no-cpu-baseline --no-parity-mode ${g:+--graphs} 2>/dev/null | line "$cfg B=$b ${g:+graphs}"
     done ) | tee -a gpurun_out/other_configs_raw.txt ;;
 kstats)
   cd /tmp; rm -rf /tmp/p_ks
