@@ -33,6 +33,7 @@ SIGNATURES = {
     "enh_last_error": (_c.c_char_p, []),
     "enh_abi_version": (_i32, []),
     "enh_vq_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "enh_vq_workspace_bytes_d": (_sz, [_i64, _i32, _i32, _i32]),
     "enh_vq_forward": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
     "enh_vq_backward": (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
     "enh_vq_lookup": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
@@ -116,7 +117,7 @@ SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 17  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 18  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -246,7 +247,8 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
 
 
 def vq_forward(z: torch.Tensor, codebook: torch.Tensor, beta: float, depth: int, use_norm: bool, want_bf16: bool = True, h16: torch.dtype = BF16):
-    """z [M,32] f32, codebook [K,32] f32 -> (zq f32 [M,32], zq 16-bit copy (format h16) | None, idx i64 [M,depth], loss f32 [1])."""
+    """z [M,d] f32, codebook [K,d] f32 (d % 8 == 0, 8 <= d <= 256) -> (zq f32 [M,d], zq 16-bit copy (format h16) | None, idx i64 [M,depth],
+    loss f32 [1])."""
     _p(z, F32, "z"); _p(codebook, F32, "codebook")  # device / dtype / contiguity first: fail before allocating
     M, d = z.shape
     K = codebook.shape[0]
@@ -255,7 +257,7 @@ def vq_forward(z: torch.Tensor, codebook: torch.Tensor, beta: float, depth: int,
     idx = torch.empty(M, depth, dtype=I64, device=z.device)
     loss = torch.empty(1, dtype=F32, device=z.device)
     L = lib()
-    nb = L.enh_vq_workspace_bytes(M, K, depth)
+    nb = L.enh_vq_workspace_bytes_d(M, K, d, depth)
     ws = _workspace(nb, z.device)
     # work model: 2*K*d FLOP per token per depth on the exact-f32 MFMA (157.3 TF peak); the call = vq_prep + vq_nn + vq_loss_finalize
     _timed("vq_forward (vq_prep + vq_nn_kernel + vq_loss_finalize)", 2.0 * M * K * d * depth,
@@ -266,14 +268,14 @@ def vq_forward(z: torch.Tensor, codebook: torch.Tensor, beta: float, depth: int,
 
 def vq_backward(z, codebook, idx, g_out, g_loss: float, g_loss_dev: Optional[torch.Tensor], beta: float, depth: int,
                 use_residual: bool, use_norm: bool, d_codebook: torch.Tensor, want_bf16: bool = True, h16: torch.dtype = BF16):
-    """Returns (dz f32, dz_bf16|None); ACCUMULATES into d_codebook [K,32] f32."""
+    """Returns (dz f32 [M,d], dz_bf16|None); ACCUMULATES into d_codebook [K,d] f32."""
     _p(z, F32, "z"); _p(codebook, F32, "codebook")
     M, d = z.shape
     K = codebook.shape[0]
     dz = torch.empty_like(z)
     dz16 = torch.empty(M, d, dtype=h16, device=z.device) if want_bf16 else None
     L = lib()
-    nb = L.enh_vq_workspace_bytes(M, K, depth)
+    nb = L.enh_vq_workspace_bytes_d(M, K, d, depth)
     ws = _workspace(nb, z.device)
     _check(L.enh_vq_backward(_p(z, F32, "z"), _p(codebook, F32, "codebook"), _p(idx, I64, "idx"), _p(g_out, F32, "g_out"),
                              float(g_loss), _p(g_loss_dev, F32, "g_loss_dev"), M, K, d, beta, depth, int(use_residual),
@@ -283,7 +285,7 @@ def vq_backward(z, codebook, idx, g_out, g_loss: float, g_loss_dev: Optional[tor
 
 
 def vq_lookup(codebook, idx, use_norm: bool, want_bf16: bool = True, h16: torch.dtype = BF16):
-    """idx [M,depth] i64 -> (sum_i n(E[idx_i]) f32 [M,32], bf16 copy)."""
+    """idx [M,depth] i64, codebook [K,d] f32 -> (sum_i n(E[idx_i]) f32 [M,d], 16-bit copy)."""
     _p(idx, I64, "idx"); _p(codebook, F32, "codebook")
     M, depth = idx.shape
     K, d = codebook.shape

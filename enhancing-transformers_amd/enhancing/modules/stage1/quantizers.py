@@ -85,14 +85,14 @@ class BaseQuantizer(nn.Module):
 
 
 class VectorQuantizer(BaseQuantizer):
-    """reference quantizers.py:66-92.  embed_dim must be 32 (the fused kernel's MFMA tiling; every reference
-    config uses 32)."""
+    """reference quantizers.py:66-92.  embed_dim: any multiple of 8 in [8, 256] (the fused kernel runs it on its smallest compiled
+    width of 32, 64, 128 or 256 that fits, zero-padded; every reference config uses 32)."""
 
     def __init__(self, embed_dim: int, n_embed: int, beta: float = 0.25, use_norm: bool = True,
                  use_residual: bool = False, num_quantizers: Optional[int] = None, **kwargs) -> None:
+        if not (isinstance(embed_dim, int) and 8 <= embed_dim <= 256 and embed_dim % 8 == 0):
+            raise ValueError(f"the fused gfx950 quantizer kernel requires embed_dim % 8 == 0 and 8 <= embed_dim <= 256, got {embed_dim!r}")
         super().__init__(embed_dim, n_embed, True, use_norm, use_residual, num_quantizers)
-        if embed_dim != 32:
-            raise ValueError("the fused gfx950 quantizer kernel requires embed_dim == 32")
         if use_residual and not num_quantizers:
             raise ValueError("use_residual=True needs num_quantizers")
         if use_residual and int(num_quantizers) > 8:

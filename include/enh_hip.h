@@ -52,29 +52,38 @@ typedef uint16_t enh_h16;  /* raw 16-bit float bits: bfloat16 or binary16, per t
 typedef enh_h16 enh_bf16;  /* raw bfloat16 bits (bf16-only entries) */
 
 const char* enh_last_error(void);
-#define ENH_ABI_VERSION 17  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 18  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Vector / residual quantizer  — enhancing/modules/stage1/quantizers.py:38-92
  * ------------------------------------------------------------------------------------------------
- * Arithmetic contract (bit-exactly restated in oracle/vq_oracle.c):
- *   n(x) = x / max(sqrt(S(x)), 1e-12),  S(x) = chain(x[0..15]) + chain(x[16..31]),
- *   chain = ascending fmaf chain from 0;  zz = S(zn), ee_k = S(en_k);
- *   dot_k = fmaf chain over the order k = 0,16,1,17,...,15,31 (f32 MFMA 32x32x2, exact f32);
+ * Code width d = embed_dim: any multiple of 8 in [8, 256] (every shipped config uses 32: configs/imagenet_vitvq_*.yaml:17-19); anything else
+ * is ENH_E_SHAPE.  A width-d call runs on the compiled width DW = the smallest of {32, 64, 128, 256} that is >= d, as that width on the
+ * inputs zero-padded to DW columns (loads masked to d, padding never stored): appended exact zeros change no sum below, so every d <= 32
+ * is bit-for-bit the width-32 contract on zero-padded rows.
+ * Arithmetic contract at width DW (the DW = 32 case is restated bit-exactly by oracle/vq_oracle.c):
+ *   n(x) = x / max(sqrt(S(x)), 1e-12),  S(x) = c_0 + c_1 + ... + c_{DW/16-1} added left to right, c_j = chain(x[16j..16j+15]),
+ *   chain = ascending fmaf chain from 0 (DW = 32: S = chain(x[0..15]) + chain(x[16..31]));  zz = S(zn), ee_k = S(en_k);
+ *   dot_k = f32 MFMA 32x32x2 accumulation (exact f32) over the column order 0, DW/2, 1, DW/2+1, ..., DW/2-1, DW-1
+ *           (DW = 32: 0,16,1,17,...,15,31);
  *   d_k = (zz + ee_k) - 2*dot_k ; idx = argmin_k d_k, lowest k on ties  (quantizers.py:78-83).
- * embed_dim must be 32 (every shipped config: configs/imagenet_vitvq_*.yaml:17-19).
+ * Losses are means over the true M*d elements.  The same bits on every run at every width.
  */
 
-/* bytes of scratch needed by enh_vq_forward / enh_vq_backward for a codebook of n_embed codes and M tokens */
+/* bytes of scratch needed by enh_vq_forward / enh_vq_backward for a codebook of n_embed codes of width embed_dim and M tokens.
+ * Scale: the backward keeps one contribution vector per (token, depth), M*depth*embed_dim floats — at M = 131 072, depth 8 and
+ * embed_dim 256 that alone is 1 GiB. */
+size_t enh_vq_workspace_bytes_d(int64_t M, int n_embed, int embed_dim, int depth);
+/* the same at embed_dim 32 */
 size_t enh_vq_workspace_bytes(int64_t M, int n_embed, int depth);
 
 /* Forward of BaseQuantizer.forward + VectorQuantizer.quantize (quantizers.py:38-63,74-92).
- *   z        [M,32] f32   quantizer input (pre_quant output)
- *   codebook [K,32] f32   quantizer.embedding.weight
- *   depth    1 = plain VQ ; >1 = residual quantizer with one shared codebook (use_residual, num_quantizers)
- *   zq_out   [M,32] f32   straight-through VALUE  z + (sum_i en_i - z)          (quantizers.py:61)
- *   zq_h16   [M,32] 16-bit optional (may be NULL): same, rounded to `dtype` (operand of post_quant GEMM)
+ *   z        [M,d] f32    quantizer input (pre_quant output)
+ *   codebook [K,d] f32    quantizer.embedding.weight
+ *   depth    1 = plain VQ ; >1 = residual quantizer with one shared codebook (use_residual, num_quantizers); <= 8 when d > 32
+ *   zq_out   [M,d] f32    straight-through VALUE  z + (sum_i en_i - z)          (quantizers.py:61)
+ *   zq_h16   [M,d] 16-bit optional (may be NULL): same, rounded to `dtype` (operand of post_quant GEMM)
  *   idx_out  [M,depth] i64 code indices (stacked on the last axis as quantizers.py:55)
  *   loss_out [1] f32      mean_i( beta*mean((en_i-zn_i)^2) + mean((en_i-zn_i)^2) ) (quantizers.py:56,89-90)
  */
@@ -84,18 +93,18 @@ int enh_vq_forward(const float* z, const float* codebook, int64_t M, int n_embed
                    int dtype, void* stream);
 
 /* Backward (derived from the reference autograd graph):
- *   g_out   [M,32] f32  grad wrt returned z_q;  g_loss_dev: optional device scalar multiplying g_loss
+ *   g_out   [M,d] f32   grad wrt returned z_q;  g_loss_dev: optional device scalar multiplying g_loss
  *   use_residual: 1 when the forward ran the residual loop (z is detached at quantizers.py:43, so the
  *           encoder then receives g_out only, and the codebook grad gets the cross-depth term)
- *   dz      [M,32] f32  (VQ: g_out + beta-term through the normalise Jacobian; RQ: g_out only)
- *   dz_h16 optional 16-bit copy (`dtype`) ; d_codebook [K,32] f32 is ACCUMULATED into (caller zeroes it).
+ *   dz      [M,d] f32   (VQ: g_out + beta-term through the normalise Jacobian; RQ: g_out only)
+ *   dz_h16 optional 16-bit copy (`dtype`) ; d_codebook [K,d] f32 is ACCUMULATED into (caller zeroes it).
  */
 int enh_vq_backward(const float* z, const float* codebook, const int64_t* idx, const float* g_out,
                     float g_loss, const float* g_loss_dev, int64_t M, int n_embed, int embed_dim,
                     float beta, int depth, int use_residual, int use_norm, float* dz, enh_h16* dz_h16,
                     float* d_codebook, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
-/* decode_codes front half (vitvqgan.py:81-87): out[m] = sum_i n(codebook[idx[m,i]]) as f32 and as a 16-bit operand (`dtype`) */
+/* decode_codes front half (vitvqgan.py:81-87): out[m] = sum_i n(codebook[idx[m,i]]) ([M,d]) as f32 and as a 16-bit operand (`dtype`) */
 int enh_vq_lookup(const float* codebook, const int64_t* idx, int64_t M, int n_embed, int embed_dim,
                   int depth, int use_norm, float* out, enh_h16* out_h16, int dtype, void* stream);
 
