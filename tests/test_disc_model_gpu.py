@@ -13,7 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from util import bf16r, disc_case, rel
+from util import bf16r, disc_case, floor16, h16r, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -30,19 +30,32 @@ GEOMS = [  # layout, B, C, H, W, k, stride, pad
     ("cm", 8, 513, 4, 4, 3, 1, 1), ("nchw", 1, 5, 70, 70, 3, 1, 1), ("cm", 1, 96, 35, 35, 3, 2, 0)]
 
 
+CONV2D_CASES = [(2, 3, 128, 16, 1, 1, 0), (2, 64, 128, 16, 3, 1, 1), (2, 64, 136, 17, 3, 2, 0), (8, 520, 64, 4, 3, 1, 1)]
+
+
 @pytest.mark.parametrize("layout,B,Cc,H,W,k,s,p", GEOMS)
 def test_im2col_col2im(C, layout, B, Cc, H, W, k, s, p):
+    _im2col_col2im(C, layout, B, Cc, H, W, k, s, p, torch.bfloat16)
+
+
+@pytest.mark.parametrize("layout,B,Cc,H,W,k,s,p", GEOMS)
+def test_im2col_col2im_fp16(C, layout, B, Cc, H, W, k, s, p):
+    """the fp16 columns of the im2col_fp16 lowering (operand_dtype("fp16")): the same RNE rounding, bit for bit"""
+    _im2col_col2im(C, layout, B, Cc, H, W, k, s, p, torch.float16)
+
+
+def _im2col_col2im(C, layout, B, Cc, H, W, k, s, p, dt):
     g = torch.Generator().manual_seed(B * 100 + Cc)
     img = torch.randn(B, Cc, H, W, generator=g)
     x = (img if layout == "nchw" else img.permute(1, 0, 2, 3).contiguous()).cuda()
     sb, sc = (Cc * H * W, H * W) if layout == "nchw" else (H * W, B * H * W)
-    cols = C.im2col(x, sb, sc, B, Cc, H, W, k, s, p)
+    cols = C.im2col(x, sb, sc, B, Cc, H, W, k, s, p, dtype=dt)
     Ho, Wo = C.conv_out_size(H, k, s, p), C.conv_out_size(W, k, s, p)
     ref = F.unfold(img, k, padding=p, stride=s).permute(0, 2, 1).reshape(B * Ho * Wo, Cc * k * k)
-    assert cols.shape == (B * Ho * Wo, (Cc * k * k + 7) // 8 * 8)
-    assert torch.equal(cols[:, :Cc * k * k].cpu(), ref.to(torch.bfloat16))          # pure data movement + RNE rounding: bit-exact
+    assert cols.shape == (B * Ho * Wo, (Cc * k * k + 7) // 8 * 8) and cols.dtype == dt
+    assert torch.equal(cols[:, :Cc * k * k].cpu(), ref.to(dt))                         # pure data movement + RNE rounding: bit-exact
     assert not cols[:, Cc * k * k:].float().abs().sum().item()                        # alignment columns are zero
-    d = torch.randn(cols.shape, generator=g).to(torch.bfloat16)
+    d = torch.randn(cols.shape, generator=g).to(dt)
     out = torch.full((B, Cc, H, W) if layout == "nchw" else (Cc, B, H, W), 7.0, device="cuda")
     C.col2im(d.cuda(), B, Cc, H, W, k, s, p, out, sb, sc)
     want = F.fold(d[:, :Cc * k * k].float().reshape(B, Ho * Wo, Cc * k * k).permute(0, 2, 1), (H, W), k, padding=p, stride=s)
@@ -50,23 +63,42 @@ def test_im2col_col2im(C, layout, B, Cc, H, W, k, s, p):
     assert rel(got, want) <= 1e-6
 
 
-@pytest.mark.parametrize("B,Cin,Cout,H,k,s,p", [(2, 3, 128, 16, 1, 1, 0), (2, 64, 128, 16, 3, 1, 1), (2, 64, 136, 17, 3, 2, 0), (8, 520, 64, 4, 3, 1, 1)])
+@pytest.mark.parametrize("B,Cin,Cout,H,k,s,p", CONV2D_CASES)
 def test_conv2d_values_and_gradients(C, B, Cin, Cout, H, k, s, p):
     """conv2d_gradfix.conv2d (the reference's NCHW signature) against F.conv2d on the same bf16-representable operands"""
+    _conv2d_values_and_gradients(B, Cin, Cout, H, k, s, p, torch.bfloat16)
+
+
+@pytest.mark.parametrize("B,Cin,Cout,H,k,s,p", CONV2D_CASES)
+def test_conv2d_values_and_gradients_fp16(C, B, Cin, Cout, H, k, s, p):
+    """the same under operand_dtype("fp16"): fp16 columns and fp16 GEMM operands on fp16-representable inputs"""
+    from enhancing.losses.op import conv2d_gradfix
+    with conv2d_gradfix.operand_dtype("fp16"):
+        _conv2d_values_and_gradients(B, Cin, Cout, H, k, s, p, torch.float16)
+
+
+def _conv2d_values_and_gradients(B, Cin, Cout, H, k, s, p, dt):
     from enhancing.losses.op import conv2d_gradfix
     g = torch.Generator().manual_seed(Cin + Cout)
-    x = bf16r(torch.randn(B, Cin, H, H, generator=g))
-    w = bf16r(torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5)
+    x = h16r(torch.randn(B, Cin, H, H, generator=g), dt)
+    w = h16r(torch.randn(Cout, Cin, k, k, generator=g) / (Cin * k * k) ** 0.5, dt)
     b = torch.randn(Cout, generator=g)
     xr, wr, br = x.clone().requires_grad_(True), w.clone().requires_grad_(True), b.clone().requires_grad_(True)
     yr = F.conv2d(xr, wr, br, stride=s, padding=p)
-    dy = bf16r(torch.randn(yr.shape, generator=g))
+    dy = h16r(torch.randn(yr.shape, generator=g), dt)
     yr.backward(dy)
     xd, wd, bd = x.cuda().requires_grad_(True), w.cuda().requires_grad_(True), b.cuda().requires_grad_(True)
     y = conv2d_gradfix.conv2d(xd, wd, bias=bd, stride=s, padding=p)
     y.backward(dy.cuda())
+    e_x = rel(xd.grad, xr.grad)
+    print(f"conv2d_gradfix {dt} {B}x{Cin}x{H} -> {Cout} k{k} s{s}: dx {e_x:.2e} (floor {floor16(xr.grad, dt):.2e})")
     assert rel(y, yr) <= 1e-5 and rel(wd.grad, wr.grad) <= 1e-5 and rel(bd.grad, br.grad) <= 1e-5
-    assert rel(xd.grad, xr.grad) <= 4e-3      # dcols leaves the dgrad GEMM in bf16: up to k*k rounded terms per input pixel
+    if dt == torch.bfloat16:
+        assert e_x <= 4e-3      # dcols leaves the dgrad GEMM in bf16: up to k*k rounded terms per input pixel
+    else:
+        # dcols leaves the dgrad GEMM in fp16 and col2im adds up to k*k of them per input pixel, exactly enough in f32: independent roundings of terms
+        # whose sum is the result carry, in rms, the rounding error of the result itself — one rounding's class
+        assert e_x <= 1.25 * floor16(xr.grad, dt), (e_x, floor16(xr.grad, dt))
 
 
 # (lowering, operand format) -> bounds (logits, dx of the R1 pass, r1, d_loss, gradient norms, generator-side dx, parameter gradients) against the REFERENCE's own

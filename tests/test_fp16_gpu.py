@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import rel
+from util import floor16, h16r, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -24,12 +24,12 @@ F32_TOL = 1e-5
 
 
 def f16r(x):
-    return x.to(F16).to(torch.float32)
+    return h16r(x, F16)
 
 
 def f16_floor(ref):
     """relative Frobenius error of merely rounding the exact result to fp16"""
-    return rel(f16r(ref.float()), ref)
+    return floor16(ref, F16)
 
 
 @pytest.fixture(scope="module")

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import bf16_floor, bf16r, rel
+from util import bf16_floor, bf16r, floor16, h16r, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -483,12 +483,12 @@ def att_family(request, C):
     C.attention_set_kernel(0, 0, 0)
 
 
-def _prescale_q(qkv, H, scale):
-    """the q_prescaled convention of include/enh_hip.h: the q third holds bf16(q * scale * log2e).  Returns (the tensor the kernels get, the UNSCALED
+def _prescale_q(qkv, H, scale, dt=torch.bfloat16):
+    """the q_prescaled convention of include/enh_hip.h: the q third holds dt(q * scale * log2e).  Returns (the tensor the kernels get, the UNSCALED
     fp64 qkv those bits represent — what the reference attention and its gradients are taken on)."""
     inner = H * 64
     dev = qkv.clone()
-    dev[..., :inner] = bf16r(qkv[..., :inner] * (scale * LOG2E))
+    dev[..., :inner] = h16r(qkv[..., :inner] * (scale * LOG2E), dt)
     ref = dev.double().clone()
     ref[..., :inner] /= (scale * LOG2E)
     return dev, ref
@@ -547,6 +547,18 @@ def test_attention_is_bit_reproducible_across_launches(C, att_family, B, N, H, p
                 f"{name}: {(runs[0][k] != r[k]).sum().item()} elements differ between two launches on the same input"
 
 
+def _spiked_qkv(g, B, N, H):
+    """f32 qkv with keys dominating a row: key 300 of head 0 aligned with query 5, and a staircase for query 70 of head 1 — keys in tiles 1, 2, 3 and the
+    last tile, each beating everything before it by a wide margin"""
+    qkv = torch.randn(B, N, 3 * H * 64, generator=g)
+    qkv[0, 5, :64] *= 6.0
+    qkv[0, 300, H * 64:H * 64 + 64] = qkv[0, 5, :64] * 1.5
+    qv = qkv[0, 70, 64:128].clone()
+    for key, gain in ((100, 2.0), (130, 4.0), (200, 7.0), (505, 11.0)):
+        qkv[0, key, H * 64 + 64:H * 64 + 128] = qv * gain
+    return qkv
+
+
 @pytest.mark.parametrize("pre", [False, True], ids=["plain", "prescaled"])
 def test_attention_spiked_scores(C, att_family, pre):
     """keys dominating a row (force the running maximum / the pipelined kernels' reference maximum to jump mid-sweep, several times and in adjacent
@@ -554,14 +566,7 @@ def test_attention_spiked_scores(C, att_family, pre):
     bounded random data and shows only in the rows that took the branch)."""
     B, N, H = 1, 512, 2
     g = torch.Generator().manual_seed(0)
-    qkv = torch.randn(B, N, 3 * H * 64, generator=g)
-    qkv[0, 5, :64] *= 6.0
-    qkv[0, 300, H * 64:H * 64 + 64] = qkv[0, 5, :64] * 1.5   # key 300 of head 0 aligned with query 5
-    # a staircase for query 70 of head 1: keys in tiles 1, 2, 3 and the last tile, each beating everything before it by a wide margin
-    qv = qkv[0, 70, 64:128].clone()
-    for key, gain in ((100, 2.0), (130, 4.0), (200, 7.0), (505, 11.0)):
-        qkv[0, key, H * 64 + 64:H * 64 + 128] = qv * gain
-    qkv = bf16r(qkv)
+    qkv = bf16r(_spiked_qkv(g, B, N, H))
     qdev, qref = _prescale_q(qkv, H, 0.125) if pre else (qkv, qkv.double())
     ref, lse_ref = _attn_ref(qref, B, N, H, 0.125)
     out = torch.empty(B, N, H * 64, dtype=torch.bfloat16, device="cuda")
@@ -582,6 +587,44 @@ def test_attention_spiked_scores(C, att_family, pre):
     C.attention_backward(qdev.to(torch.bfloat16).cuda(), out, do.to(torch.bfloat16).cuda(), lse, B, N, H, 0.125, dqkv, delta, q_prescaled=pre)
     assert torch.isfinite(dqkv.float()).all()
     assert rel(dqkv.float(), qt.grad) <= 3 * ATT_TOL, rel(dqkv.float(), qt.grad)
+
+
+@pytest.mark.parametrize("pre", [False, True], ids=["plain", "prescaled"])
+def test_attention_spiked_scores_fp16(C, pre):
+    """the spiked rows above on fp16 operands (the format of the loss-scaled engine) and the default kernels: the running maximum jumps several times,
+    so exponentials far below it reach fp16's subnormal range before P V.  Rows that took the rescale branch are checked one by one against fp64 at
+    twice the forward's floor class (1.5 x the fp16 floor, tests/test_fp16_gpu.py), the whole output at the class itself."""
+    F16 = torch.float16
+    B, N, H = 1, 512, 2
+    g = torch.Generator().manual_seed(0)
+    qkv = h16r(_spiked_qkv(g, B, N, H), F16)
+    qdev, qref = _prescale_q(qkv, H, 0.125, F16) if pre else (qkv, qkv.double())
+    ref, lse_ref = _attn_ref(qref, B, N, H, 0.125)
+    out = torch.empty(B, N, H * 64, dtype=F16, device="cuda")
+    lse = torch.empty(B, H, N, device="cuda")
+    C.attention_set_kernel(0, 0, 0)
+    C.attention_forward(qdev.to(F16).cuda(), B, N, H, 0.125, out, lse, q_prescaled=pre)
+    assert torch.isfinite(out.float()).all()
+    fl = floor16(ref, F16)
+    e_o = rel(out.float(), ref)
+    assert rel(lse, lse_ref) <= 1e-5
+    # the rows that took the branch, individually, in units of the whole output's floor (a row led by one key is that key's v, exactly
+    # representable: its own floor is zero)
+    rows = [rel(out.float().cpu()[0, q, h * 64:(h + 1) * 64], ref[0, q, h * 64:(h + 1) * 64]) / fl for q, h in ((5, 0), (70, 1))]
+    print(f"fp16 spiked attention pre={pre}: out {e_o / fl:.3f} x floor, branch rows {rows[0]:.3f} / {rows[1]:.3f} x the output's floor")
+    assert e_o <= 1.5 * fl + 1e-6
+    assert max(rows) <= 3.0, rows
+    do = h16r(torch.randn(B, N, H * 64, generator=g), F16)
+    qt = qref.clone().requires_grad_(True)
+    r2, _ = _attn_ref(qt, B, N, H, 0.125)
+    r2.backward(do.double())
+    dqkv = torch.full((B, N, 3 * H * 64), float("nan"), dtype=F16, device="cuda")
+    delta = torch.empty(B, H, N, device="cuda")
+    C.attention_backward(qdev.to(F16).cuda(), out, do.to(F16).cuda(), lse, B, N, H, 0.125, dqkv, delta, q_prescaled=pre)
+    assert torch.isfinite(dqkv.float()).all()
+    e_g = rel(dqkv.float(), qt.grad)
+    print(f"  gradient {e_g:.2e}")
+    assert e_g <= 3e-3, e_g              # fp16's 2e-3 class of tests/test_fp16_gpu.py, with the 1.5x this test grants bf16 for the spiked rows
 
 
 # ---------------------------------------------------------------------------------------------

@@ -167,6 +167,33 @@ def test_lookup(C, d, depth):
     assert torch.equal(out16h, out.to(torch.float16))
 
 
+@pytest.mark.parametrize("d", [8, 64, 256])
+@pytest.mark.parametrize("depth", [1, 4])
+def test_fp16_copies_are_the_rounded_f32_results(C, d, depth):
+    """the loss-scaled fp16 engine asks the quantizer for fp16 copies (h16=float16): zq16 and dz16 must be the round-to-nearest-even images of zq and dz
+    bit for bit, with the codebook-loss gradient as a host scalar and as the device scalar the engine passes; the bf16 copies are unchanged"""
+    import vitvq_oracle as O
+    M, K = 4096, 1024
+    z, E, g = O.make_vq_inputs(40 + d + depth, M, K, d)
+    z, E, g = z.cuda(), E.cuda(), g.cuda()
+    zq, zq16, idx, loss = C.vq_forward(z, E, 0.25, depth, True, h16=torch.float16)
+    assert zq16.dtype == torch.float16 and zq16.shape == (M, d)
+    assert torch.equal(zq16.view(torch.int16), zq.to(torch.float16).view(torch.int16))
+    zqb, zqb16, idxb, lossb = C.vq_forward(z, E, 0.25, depth, True)
+    assert torch.equal(idx, idxb) and torch.equal(zq.view(torch.int32), zqb.view(torch.int32)) and torch.equal(loss, lossb)
+    assert torch.equal(zqb16, zqb.to(torch.bfloat16))
+    resid = depth > 1
+    gs = g * 1024.0                   # the upstream gradient carries the loss scale in the engine
+    for g_loss, g_dev in ((0.7 * 1024.0, None), (1.0, torch.tensor([0.7 * 1024.0], device="cuda"))):
+        dE = torch.zeros(K, d, device="cuda")
+        dz, dz16 = C.vq_backward(z, E, idx, gs, g_loss, g_dev, 0.25, depth, resid, True, dE, h16=torch.float16)
+        assert dz16.dtype == torch.float16 and torch.isfinite(dz16).all()
+        assert torch.equal(dz16.view(torch.int16), dz.to(torch.float16).view(torch.int16)), (g_loss, g_dev)
+        dEb = torch.zeros(K, d, device="cuda")
+        dzb, dzb16 = C.vq_backward(z, E, idx, gs, g_loss, g_dev, 0.25, depth, resid, True, dEb)
+        assert torch.equal(dzb.view(torch.int32), dz.view(torch.int32)) and torch.equal(dzb16, dzb.to(torch.bfloat16))
+
+
 def _fmaf_chain_sq(x):
     """ascending fmaf chain sum x_j * x_j from 0 in float32, column by column (x [N,16] float32): the product is exact in float64"""
     s = np.zeros(x.shape[0], dtype=np.float32)

@@ -20,6 +20,17 @@ def bf16_floor(ref: torch.Tensor) -> float:
     return rel(bf16r(ref.float()), ref)
 
 
+def h16r(x: torch.Tensor, dt: torch.dtype) -> torch.Tensor:
+    """round to the 16-bit format `dt` (torch.bfloat16 | torch.float16) and back to f32: bf16r for either operand format"""
+    return x.to(dt).to(torch.float32)
+
+
+def floor16(ref: torch.Tensor, dt: torch.dtype) -> float:
+    """relative Frobenius error of merely ROUNDING the exact result to `dt`: bf16_floor for either format.  torch's CPU cast rounds to nearest even and
+    keeps fp16 subnormals (and overflows to inf), so the floor stays the right yardstick for outputs in fp16's subnormal range."""
+    return rel(h16r(ref.float(), dt), ref)
+
+
 def disc_case(golden_npz):
     """the discriminator golden case of oracle/make_golden_disc.py: module (CPU parameters regenerated from the seed), real, fake"""
     from enhancing.losses.layers import StyleDiscriminator
