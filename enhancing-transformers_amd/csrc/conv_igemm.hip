@@ -22,6 +22,7 @@
 // Register-staged double buffer (the gather needs per-lane predication, which global_load_lds cannot do), 128 x 128 x 64 tile,
 // 4 waves of 64 x 64 (v_mfma_f32_16x16x32_bf16), 2 workgroups per CU.  C and N multiples of 8; any grid size.
 #include "gemm_tiles.h"
+#include "w256_loop.h"
 
 // conv_pointwise.hip: the dense 1 x 1 geometries with an 8-channel side (the discriminator's first layer) as streaming kernels
 int conv_pointwise_forward(const uint16_t* src, const uint16_t* wt, const enh_conv_geom& g, int mode, const float* bias, float p0, float p1, uint16_t* out,
@@ -430,9 +431,8 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const ConvArgs 
 }
 
 // =================================================================================================
-// "w256" form of the convolution (round 4): the dense w256 main loop (gemm.hip gemm_bf16_w256_kernel — 256 x 256 tile, FOUR waves of 128 x 128, one wave per
-// SIMD, v_mfma_f32_32x32x16_bf16, two 64-KiB LDS slots, one barrier per 64-deep K stage, one fragment read per MFMA and one global_load_lds per two
-// MFMAs) fed by the gather of conv_igemm_glds_kernel: C % 64 == 0, so a K stage lies inside ONE tap and a staged row is "pixel offset + a tap offset that is
+// "w256" form of the convolution (round 4): the K loop of the dense gemm_w256_kernel (w256_loop.h: the schedule is described there) fed by the gather of
+// conv_igemm_glds_kernel: C % 64 == 0, so a K stage lies inside ONE tap and a staged row is "pixel offset + a tap offset that is
 // uniform for the wave"; lanes whose tap falls outside the image read the zero page.  Waves 0, 1 stage the two 128-pixel halves of the A tile, waves 2, 3 the
 // weights; BOTH run the same instruction stream — a staging lane keeps, per 1-KiB piece u, an element offset and a packed (y, x), and the wave keeps
 // (dy, dx, tap offset) in scalar registers (weights: y = x = dy = dx = 0, the offset advances by 64) — so the pointer of a piece costs ~10 vector
@@ -509,9 +509,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int nst = (int)(args.K / G_BK);   // >= 2 (launcher)
 
   // ---- staging state -----------------------------------------------------------------------------------------------------------
-  static_assert(NJ == 4, "256 x 256 tiles");
+  static_assert(NJ == 4, "waves 2 and 3 stage two 128-column weight sub-tiles: the tile is 256 columns wide");
   const bool stage_a = wave < 2;                                   // wave-uniform
-  constexpr int slab0 = 0;
   unsigned char* const my_sub = smem + wave * G_TILE_BYTES;        // the 16-KiB sub-tile of a slot this wave fills
   const uint16_t* const gbase = stage_a ? args.X : args.Wt;
   const uint16_t* const zero = reinterpret_cast<const uint16_t*>(g_conv_zero_page);
@@ -519,12 +518,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   {
     // pixel (b, y, x) of this lane's row of piece 0 by one 32-bit division; the rows of pieces 1..15 are 8 pixels further each
     const unsigned hw = (unsigned)g.Hm * (unsigned)g.Wm;
-    const unsigned row0 = (unsigned)m0 + wave * 128 + slab0 * 8 + (lane >> 3);
+    const unsigned row0 = (unsigned)m0 + wave * 128 + (lane >> 3);
     unsigned pb = row0 / hw, prem = row0 - pb * hw;
     unsigned py_ = prem / (unsigned)g.Wm, px_ = prem - py_ * (unsigned)g.Wm;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
-      const int r = (slab0 + u) * 8 + (lane >> 3), pc = lane & 7;    // row of the sub-tile, physical chunk ; logical chunk of the row image:
+      const int r = u * 8 + (lane >> 3), pc = lane & 7;    // row of the sub-tile, physical chunk ; logical chunk of the row image:
       const int c = pc ^ ((r >> 1) & 7);
       if (stage_a) {
         const bool exists = (int64_t)m0 + wave * 128 + r < args.M;
@@ -544,7 +543,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int s_dy = stage_a ? g.oy0 : 0, s_dx = stage_a ? g.ox0 : 0;
   int s_off = stage_a ? (s_dy * g.Ws + s_dx) * g.C : 0;
   const unsigned lim_y = stage_a ? (unsigned)g.Hs : 1u, lim_x = stage_a ? (unsigned)g.Ws : 1u;
-#define CW_ADVANCE()                                                                                                              \
+#define W256_ADVANCE()                                                                                                            \
   do {                                                                                                                            \
     if (stage_a) {                                                                                                                \
       s_ch += G_BK;                                                                                                               \
@@ -560,86 +559,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       __builtin_amdgcn_global_load_lds((const GLB_AS void*)p_, (LDS_AS void*)(my_sub + (SLOT) * CW_SLOT + (U) * 1024), 16, 0, ENH_GLDS_AUX);  \
     }                                                                                                                             \
   } while (0)
-#define CW_READ_ONE(FA, FB, SLOT, S, U)                                                                                           \
-  do {                                                                                                                            \
-    if ((U) < 4) FA[(U) & 3] = frag32<false>(smem + (SLOT) * CW_SLOT + wm * G_TILE_BYTES, ((U) & 3) * 32, S, lane);               \
-    else FB[(U) & 3] = frag32<false>(smem + (SLOT) * CW_SLOT + (2 + wn) * G_TILE_BYTES, ((U) & 3) * 32, S, lane);                 \
-  } while (0)
-#define CW_MM(Q, FA, FB)                                                                                                          \
-  acc[(Q) / NJ][(Q) % NJ] = mfma32<OT>(FB[(Q) % NJ], FA[(Q) / NJ], acc[(Q) / NJ][(Q) % NJ])
-#define CW_FENCE() __builtin_amdgcn_sched_barrier(0)
-  // one k16 step: 16 MFMAs on (FA, FB); under the first 8 one fragment read each (k-step RS of slot RSLOT into RA / RB); 8 staging requests (pieces
-  // G0 .. G0+7 into slot GSLOT) under the odd MFMAs
-#define CW_KSTEP(FA, FB, RA, RB, RSLOT, RS, DO_READ, GSLOT, G0, DO_ISSUE)                                                         \
-  do {                                                                                                                            \
-    CW_FENCE();                                                                                                                   \
-    _Pragma("unroll") for (int q_ = 0; q_ < 4 * NJ; ++q_) {                                                                       \
-      CW_MM(q_, FA, FB);                                                                                                          \
-      if ((DO_READ) && q_ < 4 + NJ) { CW_READ_ONE(RA, RB, RSLOT, RS, q_); }                                                       \
-      if ((DO_ISSUE) && (q_ & 1)) { CW_ISSUE_ONE(GSLOT, (G0) + (q_ >> 1)); }                                                      \
-      CW_FENCE();                                                                                                                 \
-    }                                                                                                                             \
-  } while (0)
-
   f32x16 acc[4][NJ];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
   s16x8 fa0[4], fb0[4], fa1[4], fb1[4];
-
-  // prologue: stage 0 -> slot 0 completely; pieces 0-7 of stage 1 -> slot 1 (pieces 8-15 follow under the first k-step)
-#pragma unroll
-  for (int u = 0; u < 16; ++u) CW_ISSUE_ONE(0, u);
-  CW_ADVANCE();
-#pragma unroll
-  for (int u = 0; u < 8; ++u) CW_ISSUE_ONE(1, u);
-  __builtin_amdgcn_s_waitcnt(0x0F78);   // vmcnt(8): stage 0 landed
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int u = 0; u < 4 + NJ; ++u) CW_READ_ONE(fa0, fb0, 0, 0, u);
-  CW_FENCE();
-
-  // invariant at the top of iteration j: the tap state is at stage j+1, whose pieces 0-7 are already requested into slot (j+1)&1
-  int j = 0;
-  for (; j + 2 < nst; ++j) {
-    const int slot = j & 1;
-    CW_KSTEP(fa0, fb0, fa1, fb1, slot, 1, true, slot ^ 1, 8, true);      // + pieces 8-15 of stage j+1
-    CW_ADVANCE();
-    CW_KSTEP(fa1, fb1, fa0, fb0, slot, 2, true, 0, 0, false);
-    CW_KSTEP(fa0, fb0, fa1, fb1, slot, 3, true, 0, 0, false);
-    __builtin_amdgcn_s_waitcnt(0x0070);    // vmcnt(0): stage j+1 landed (nothing newer outstanding) ; lgkmcnt(0): this slot is read out
-    __builtin_amdgcn_s_barrier();
-    CW_FENCE();
-    CW_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 0, true, slot, 0, true);      // + pieces 0-7 of stage j+2 into the slot just vacated
-  }
-  {  // tail: stages nst-2 and nst-1
-    const int slot = j & 1;
-    CW_KSTEP(fa0, fb0, fa1, fb1, slot, 1, true, slot ^ 1, 8, true);      // + pieces 8-15 of stage nst-1
-    CW_KSTEP(fa1, fb1, fa0, fb0, slot, 2, true, 0, 0, false);
-    CW_KSTEP(fa0, fb0, fa1, fb1, slot, 3, true, 0, 0, false);
-    __builtin_amdgcn_s_waitcnt(0x0070);
-    __builtin_amdgcn_s_barrier();
-    CW_FENCE();
-    CW_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 0, true, 0, 0, false);
-    CW_KSTEP(fa0, fb0, fa1, fb1, slot ^ 1, 1, true, 0, 0, false);
-    CW_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 2, true, 0, 0, false);
-    CW_KSTEP(fa0, fb0, fa1, fb1, slot ^ 1, 3, true, 0, 0, false);
-    CW_KSTEP(fa1, fb1, fa0, fb0, 0, 0, false, 0, 0, false);
-  }
-#undef CW_ADVANCE
+#define W256_NJ NJ
+#define W256_LGKM0 false
+#define W256_READ(FA, FB, SLOT, S, U)                                                                                             \
+  W256_READ_TILES(FA, FB, false, false, smem + (SLOT) * CW_SLOT + wm * G_TILE_BYTES, smem + (SLOT) * CW_SLOT + (2 + wn) * G_TILE_BYTES, S, U)
+#define W256_REQUEST(SLOT, HALF, Q) W256_REQUEST_ODD(CW_ISSUE_ONE, SLOT, HALF, Q)
+#define W256_PROLOGUE() W256_PROLOGUE_16(CW_ISSUE_ONE)
+  W256_CLEAR(acc);
+  W256_MAINLOOP(nst);
 #undef CW_ISSUE_ONE
-#undef CW_READ_ONE
-#undef CW_MM
-#undef CW_KSTEP
-#undef CW_FENCE
+#undef W256_NJ
+#undef W256_LGKM0
+#undef W256_READ
+#undef W256_REQUEST
+#undef W256_PROLOGUE
+#undef W256_ADVANCE
   conv_epilogue32<OT, NJ>(args, acc, m0 + wm * 128, n0 + wn * (32 * NJ), lane, reinterpret_cast<float*>(smem + 2 * CW_SLOT) + wave * 128, smem + wave * 8192);
 }
 
 // =================================================================================================
-// "w512": the same main loop for N = 128 layers (the discriminator's 128 -> 128 convolution at 256^2 and its input gradient — the largest single layer).
+// "w512": the same K loop (w256_loop.h) for N = 128 layers (the discriminator's 128 -> 128 convolution at 256^2 and its input gradient — the largest single layer).
 // 512 x 128 tile, the four waves stacked along M (each 128 x 128: the accumulators, fragment reads and MFMA count per wave are those of the 256 x 256
 // kernel), so each wave owns the 128-pixel A sub-tile it multiplies and the ONE 16-KiB weight sub-tile is shared by all four.  LDS image per slot
 // [A0 | A1 | A2 | A3 | B0] = 80 KiB, two slots = the CU's whole 160 KiB; every wave stages its own pixels (16 pieces per K stage) and a quarter of the
@@ -693,7 +634,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int s_ch = 0, s_jx = 0, s_jy = 0, s_k = 0;
   int s_dy = g.oy0, s_dx = g.ox0;
   int s_off = (s_dy * g.Ws + s_dx) * g.C;
-#define CX_ADVANCE()                                                                                                              \
+#define W256_ADVANCE()                                                                                                            \
   do {                                                                                                                            \
     s_k += G_BK; s_ch += G_BK;                                                                                                    \
     if (s_ch == g.C) { s_ch = 0; if (++s_jx == g.ntx) { s_jx = 0; ++s_jy; } s_dy = g.oy0 + s_jy * g.sty; s_dx = g.ox0 + s_jx * g.stx; } \
@@ -707,86 +648,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   } while (0)
 #define CX_ISSUE_B(SLOT, V)                                                                                                       \
   __builtin_amdgcn_global_load_lds((const GLB_AS void*)(args.Wt + (boff[V] + s_k)), (LDS_AS void*)(my_b + (SLOT) * CX_SLOT + (V) * 1024), 16, 0, ENH_GLDS_AUX)
-#define CX_READ_ONE(FA, FB, SLOT, S, U)                                                                                           \
-  do {                                                                                                                            \
-    if ((U) < 4) FA[(U) & 3] = frag32<false>(smem + (SLOT) * CX_SLOT + wave * G_TILE_BYTES, ((U) & 3) * 32, S, lane);             \
-    else FB[(U) & 3] = frag32<false>(smem + (SLOT) * CX_SLOT + 4 * G_TILE_BYTES, ((U) & 3) * 32, S, lane);                        \
-  } while (0)
-#define CX_MM(Q, FA, FB)                                                                                                          \
-  acc[(Q) >> 2][(Q) & 3] = mfma32<OT>(FB[(Q) & 3], FA[(Q) >> 2], acc[(Q) >> 2][(Q) & 3])
-#define CX_FENCE() __builtin_amdgcn_sched_barrier(0)
-  // one k16 step: 16 MFMAs; under the first 8 one fragment read each; HALF = 0 / 1: requests of the first / second half of a stage (A pieces 8*HALF..+7 under
-  // the odd MFMAs, weight pieces 2*HALF, +1 under MFMAs 4 and 10)
-#define CX_KSTEP(FA, FB, RA, RB, RSLOT, RS, DO_READ, GSLOT, HALF, DO_ISSUE)                                                       \
-  do {                                                                                                                            \
-    CX_FENCE();                                                                                                                   \
-    _Pragma("unroll") for (int q_ = 0; q_ < 16; ++q_) {                                                                           \
-      CX_MM(q_, FA, FB);                                                                                                          \
-      if ((DO_READ) && q_ < 8) { CX_READ_ONE(RA, RB, RSLOT, RS, q_); }                                                            \
-      if ((DO_ISSUE) && (q_ & 1)) { CX_ISSUE_A(GSLOT, (HALF) * 8 + (q_ >> 1)); }                                                  \
-      if ((DO_ISSUE) && (q_ == 4 || q_ == 10)) { CX_ISSUE_B(GSLOT, (HALF) * 2 + (q_ == 10)); }                                    \
-      CX_FENCE();                                                                                                                 \
-    }                                                                                                                             \
-  } while (0)
-
   f32x16 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
   s16x8 fa0[4], fb0[4], fa1[4], fb1[4];
-
-  // prologue: stage 0 -> slot 0 completely; the first half of stage 1 -> slot 1
-#pragma unroll
-  for (int u = 0; u < 16; ++u) CX_ISSUE_A(0, u);
-#pragma unroll
-  for (int v = 0; v < 4; ++v) CX_ISSUE_B(0, v);
-  CX_ADVANCE();
-#pragma unroll
-  for (int u = 0; u < 8; ++u) CX_ISSUE_A(1, u);
-  CX_ISSUE_B(1, 0); CX_ISSUE_B(1, 1);
-  __builtin_amdgcn_s_waitcnt(0x0F7A);   // vmcnt(10): stage 0 landed
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int u = 0; u < 8; ++u) CX_READ_ONE(fa0, fb0, 0, 0, u);
-  CX_FENCE();
-
-  // invariant at the top of iteration j: the tap state is at stage j+1, whose first half is already requested into slot (j+1)&1
-  int j = 0;
-  for (; j + 2 < nst; ++j) {
-    const int slot = j & 1;
-    CX_KSTEP(fa0, fb0, fa1, fb1, slot, 1, true, slot ^ 1, 1, true);      // + second half of stage j+1
-    CX_ADVANCE();
-    CX_KSTEP(fa1, fb1, fa0, fb0, slot, 2, true, 0, 0, false);
-    CX_KSTEP(fa0, fb0, fa1, fb1, slot, 3, true, 0, 0, false);
-    __builtin_amdgcn_s_waitcnt(0x0070);    // vmcnt(0): stage j+1 landed (nothing newer outstanding) ; lgkmcnt(0): this slot is read out
-    __builtin_amdgcn_s_barrier();
-    CX_FENCE();
-    CX_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 0, true, slot, 0, true);      // + first half of stage j+2 into the slot just vacated
-  }
-  {  // tail: stages nst-2 and nst-1
-    const int slot = j & 1;
-    CX_KSTEP(fa0, fb0, fa1, fb1, slot, 1, true, slot ^ 1, 1, true);      // + second half of stage nst-1
-    CX_KSTEP(fa1, fb1, fa0, fb0, slot, 2, true, 0, 0, false);
-    CX_KSTEP(fa0, fb0, fa1, fb1, slot, 3, true, 0, 0, false);
-    __builtin_amdgcn_s_waitcnt(0x0070);
-    __builtin_amdgcn_s_barrier();
-    CX_FENCE();
-    CX_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 0, true, 0, 0, false);
-    CX_KSTEP(fa0, fb0, fa1, fb1, slot ^ 1, 1, true, 0, 0, false);
-    CX_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 2, true, 0, 0, false);
-    CX_KSTEP(fa0, fb0, fa1, fb1, slot ^ 1, 3, true, 0, 0, false);
-    CX_KSTEP(fa1, fb1, fa0, fb0, 0, 0, false, 0, 0, false);
-  }
-#undef CX_ADVANCE
+#define W256_NJ 4
+#define W256_LGKM0 false
+#define W256_READ(FA, FB, SLOT, S, U)                                                                                             \
+  W256_READ_TILES(FA, FB, false, false, smem + (SLOT) * CX_SLOT + wave * G_TILE_BYTES, smem + (SLOT) * CX_SLOT + 4 * G_TILE_BYTES, S, U)
+  // half HALF of a stage: A pieces 8 * HALF .. + 7 under the odd MFMAs, weight pieces 2 * HALF, + 1 under MFMAs 4 and 10
+#define W256_REQUEST(SLOT, HALF, Q)                                                                                               \
+  do {                                                                                                                            \
+    if ((Q) & 1) { CX_ISSUE_A(SLOT, (HALF) * 8 + ((Q) >> 1)); }                                                                   \
+    if ((Q) == 4 || (Q) == 10) { CX_ISSUE_B(SLOT, (HALF) * 2 + ((Q) == 10)); }                                                    \
+  } while (0)
+#define W256_PROLOGUE()                                                                                                           \
+  do {                                                                                                                            \
+    _Pragma("unroll") for (int u = 0; u < 16; ++u) CX_ISSUE_A(0, u);                                                              \
+    _Pragma("unroll") for (int v = 0; v < 4; ++v) CX_ISSUE_B(0, v);                                                               \
+    W256_ADVANCE();                                                                                                               \
+    _Pragma("unroll") for (int u = 0; u < 8; ++u) CX_ISSUE_A(1, u);                                                               \
+    CX_ISSUE_B(1, 0); CX_ISSUE_B(1, 1);                                                                                           \
+    __builtin_amdgcn_s_waitcnt(0x0F7A); /* vmcnt(10): stage 0 landed */                                                           \
+  } while (0)
+  W256_CLEAR(acc);
+  W256_MAINLOOP(nst);
 #undef CX_ISSUE_A
 #undef CX_ISSUE_B
-#undef CX_READ_ONE
-#undef CX_MM
-#undef CX_KSTEP
-#undef CX_FENCE
+#undef W256_NJ
+#undef W256_LGKM0
+#undef W256_READ
+#undef W256_REQUEST
+#undef W256_PROLOGUE
+#undef W256_ADVANCE
   conv_epilogue32<OT, 4>(args, acc, m0 + wave * 128, n0, lane, reinterpret_cast<float*>(smem + 32768) + wave * 128, smem + wave * 8192);
 }
 
@@ -810,21 +702,22 @@ extern "C" int enh_conv_set_kernel(int variant) {
 }
 
 // the 256 / 512-row kernels: whole K stages inside one tap, whole N tiles, 32-bit element offsets, (y, x) in 14 bits each.
-// 0 = not applicable, 4 = 256 x 256 tiles (N % 256 == 0), 5 = 512 x 128 tiles (other multiples of 128)
-static int conv_w256_nj(const ConvArgs& a) {
+// Which of them runs a shape: 256 x 256 tiles (N % 256 == 0), 512 x 128 tiles (other multiples of 128), or neither.
+enum ConvWideTile { CONV_WIDE_NONE = 0, CONV_WIDE_256x256, CONV_WIDE_512x128 };
+static ConvWideTile conv_wide_tile(const ConvArgs& a) {
   const enh_conv_geom& g = a.g;
-  if (g_conv_variant == 1 || g_conv_variant == 2) return 0;
-  if (g.C % G_BK != 0 || a.K < 4 * G_BK || g.N % 128 != 0) return 0;
-  if (a.M >= (1ll << 31) - 1024 || (int64_t)g.B * g.Hs * g.Ws * g.C >= (1ll << 31) || (int64_t)g.N * a.K >= (1ll << 31) || g.Hs > 16000 || g.Ws > 16000) return 0;
-  if ((int64_t)(g.Hm - 1) * g.gs > 16000 || (int64_t)(g.Wm - 1) * g.gs > 16000) return 0;
-  const int nj = g.N % 256 == 0 ? 4 : 5;
-  if (g_conv_variant == 3) return nj;
+  if (g_conv_variant == 1 || g_conv_variant == 2) return CONV_WIDE_NONE;
+  if (g.C % G_BK != 0 || a.K < 4 * G_BK || g.N % 128 != 0) return CONV_WIDE_NONE;
+  if (a.M >= (1ll << 31) - 1024 || (int64_t)g.B * g.Hs * g.Ws * g.C >= (1ll << 31) || (int64_t)g.N * a.K >= (1ll << 31) || g.Hs > 16000 || g.Ws > 16000) return CONV_WIDE_NONE;
+  if ((int64_t)(g.Hm - 1) * g.gs > 16000 || (int64_t)(g.Wm - 1) * g.gs > 16000) return CONV_WIDE_NONE;
+  const ConvWideTile wide = g.N % 256 == 0 ? CONV_WIDE_256x256 : CONV_WIDE_512x128;
+  if (g_conv_variant == 3) return wide;
   // per-shape choice (B = 16 layer table, profiles/r04_conv_layers.txt): with dense output rows the large tiles win 1.2-1.4x (760 -> 930, 764 -> 1052 TF/s);
   // the parity classes of a stride-2 input gradient (1-4 taps: two to eight K stages per tile) do not amortise the deeper prologue (408 -> 326)
   const bool dense = g.os == 1 && g.HO == g.Hm && g.WO == g.Wm && g.oph == 0 && g.opw == 0;
-  if (!dense) return 0;
-  const int64_t tiles = nj == 4 ? ((a.M + 255) / 256) * (g.N / 256) : ((a.M + 511) / 512) * (g.N / 128);
-  return tiles >= enh_device_cus() ? nj : 0;   // below one tile per CU the 128-row kernels (four times the workgroups, two per CU) fill the chip better
+  if (!dense) return CONV_WIDE_NONE;
+  const int64_t tiles = wide == CONV_WIDE_256x256 ? ((a.M + 255) / 256) * (g.N / 256) : ((a.M + 511) / 512) * (g.N / 128);
+  return tiles >= enh_device_cus() ? wide : CONV_WIDE_NONE;   // below one tile per CU the 128-row kernels (four times the workgroups, two per CU) fill the chip better
 }
 
 template <typename OT>
@@ -907,15 +800,13 @@ static int conv_nhwc_impl(const enh_h16* src, const enh_h16* wt, const enh_conv_
     ENH_DT_DISPATCH(dtype, (conv_splitk_finish_kernel<OT><<<dim3((unsigned)((a.M * (g->N / 4) + 255) / 256)), 256, 0, (hipStream_t)stream>>>(a)));
     return enh_check_launch("enh_conv_nhwc_h16");
   }
-  const int nj = conv_w256_nj(a);
-  if (nj) {
-    if (nj == 4) {
-      a.nbm = (int)((a.M + 255) / 256); a.nbn = g->N / 256;
-      ENH_DT_DISPATCH(dtype, (conv_igemm_w256_kernel<OT, 4><<<dim3((unsigned)(a.nbm * a.nbn)), 256, CW_LDS_BYTES, (hipStream_t)stream>>>(a)));
-    } else {
-      a.nbm = (int)((a.M + 511) / 512); a.nbn = g->N / 128;
-      ENH_DT_DISPATCH(dtype, (conv_igemm_w512_kernel<OT><<<dim3((unsigned)(a.nbm * a.nbn)), 256, CX_LDS_BYTES, (hipStream_t)stream>>>(a)));
-    }
+  const ConvWideTile wide = conv_wide_tile(a);
+  if (wide == CONV_WIDE_256x256) {
+    a.nbm = (int)((a.M + 255) / 256); a.nbn = g->N / 256;
+    ENH_DT_DISPATCH(dtype, (conv_igemm_w256_kernel<OT, 4><<<dim3((unsigned)(a.nbm * a.nbn)), 256, CW_LDS_BYTES, (hipStream_t)stream>>>(a)));
+  } else if (wide == CONV_WIDE_512x128) {
+    a.nbm = (int)((a.M + 511) / 512); a.nbn = g->N / 128;
+    ENH_DT_DISPATCH(dtype, (conv_igemm_w512_kernel<OT><<<dim3((unsigned)(a.nbm * a.nbn)), 256, CX_LDS_BYTES, (hipStream_t)stream>>>(a)));
   } else if (g->C % G_BK == 0 && a.K >= 2 * G_BK && g_conv_variant != 1)
     ENH_DT_DISPATCH(dtype, (conv_igemm_glds_kernel<OT><<<dim3((unsigned)(a.nbm * a.nbn)), 256, 4 * G_TILE_BYTES, (hipStream_t)stream>>>(a)));
   else
@@ -1040,8 +931,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_igemm_kernel(const ConvWgra
 }
 
 // =================================================================================================
-// "w256" form of the weight gradient (round 4): the dense split-K weight-gradient kernel (gemm_bf16_w256_kernel<true, true, EPI_WS>: both operands
-// contraction-major in the "kmaj2" LDS image, transpose reads, 256 x 256 tile, one wave per SIMD) with the gathered operand fetched by global_load_lds.
+// "w256" form of the weight gradient (round 4): the dense split-K weight-gradient kernel (gemm_w256_kernel<OT, true, true, EPI_WS>: both operands
+// contraction-major in the "kmaj2" LDS image, transpose reads; the K loop of w256_loop.h) with the gathered operand fetched by global_load_lds.
 // The contraction runs over pixels; a 64-pixel K stage of a grid whose width is a multiple of 64 lies inside ONE image row, and a 128-column sub-tile of
 // (tap, channel) with C % 128 == 0 inside ONE tap — so the wave that stages a B sub-tile keeps (image, row, first column, validity of the source row, base
 // pointer) in SCALAR registers, and a lane keeps two 32-bit offsets: per 1-KiB piece the pointer is "scalar base + lane offset", the horizontal padding
@@ -1103,7 +994,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     s_base = args.X + (((int64_t)s_b * g.Hs + sy) * g.Ws + (int64_t)s_x0 * g.gs + dx_) * g.C + ch0;
   }
   unsigned char* const my_sub = smem + wave * G_TILE_BYTES;
-#define WW_ADVANCE()                                                                                                              \
+#define W256_ADVANCE()                                                                                                            \
   do {                                                                                                                            \
     if (stage_a) s_base += (int64_t)G_BK * g.N;                                                                                   \
     else {                                                                                                                        \
@@ -1121,79 +1012,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const uint16_t* p_ = (s_ok && vx_ < lim) ? s_base + ((((U) & 1) ? voff_o : voff_e) + ((U) >> 1) * step2) : zero;              \
     __builtin_amdgcn_global_load_lds((const GLB_AS void*)p_, (LDS_AS void*)(my_sub + (SLOT) * CW_SLOT + (U) * 1024), 16, 0, ENH_GLDS_AUX);    \
   } while (0)
-#define WW_READ_ONE(FA, FB, SLOT, S, U)                                                                                           \
-  do {                                                                                                                            \
-    if ((U) < 4) FA[(U) & 3] = frag32<true>(smem + (SLOT) * CW_SLOT + wm * G_TILE_BYTES, ((U) & 3) * 32, S, lane);                \
-    else FB[(U) & 3] = frag32<true>(smem + (SLOT) * CW_SLOT + (2 + wn) * G_TILE_BYTES, ((U) & 3) * 32, S, lane);                  \
-  } while (0)
-#define WW_MM(Q, FA, FB)                                                                                                          \
-  acc[(Q) >> 2][(Q) & 3] = mfma32<OT>(FB[(Q) & 3], FA[(Q) >> 2], acc[(Q) >> 2][(Q) & 3])
-#define WW_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define WW_KSTEP(FA, FB, RA, RB, RSLOT, RS, DO_READ, GSLOT, G0, DO_ISSUE)                                                         \
-  do {                                                                                                                            \
-    __builtin_amdgcn_s_waitcnt(0xC07F); /* the asm transpose reads are invisible to the compiler's wait-count pass */               \
-    WW_FENCE();                                                                                                                   \
-    _Pragma("unroll") for (int q_ = 0; q_ < 16; ++q_) {                                                                           \
-      WW_MM(q_, FA, FB);                                                                                                          \
-      if ((DO_READ) && q_ < 8) { WW_READ_ONE(RA, RB, RSLOT, RS, q_); }                                                            \
-      if ((DO_ISSUE) && (q_ & 1)) { WW_ISSUE_ONE(GSLOT, (G0) + (q_ >> 1)); }                                                      \
-      WW_FENCE();                                                                                                                 \
-    }                                                                                                                             \
-  } while (0)
-
   f32x16 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
   s16x8 fa0[4], fb0[4], fa1[4], fb1[4];
-
-#pragma unroll
-  for (int u = 0; u < 16; ++u) WW_ISSUE_ONE(0, u);
-  WW_ADVANCE();
-#pragma unroll
-  for (int u = 0; u < 8; ++u) WW_ISSUE_ONE(1, u);
-  __builtin_amdgcn_s_waitcnt(0x0F78);   // vmcnt(8): stage 0 landed
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int u = 0; u < 8; ++u) WW_READ_ONE(fa0, fb0, 0, 0, u);
-  WW_FENCE();
-
-  // invariant at the top of iteration j: the staging state is at stage j+1, whose pieces 0-7 are already requested into slot (j+1)&1
-  int j = 0;
-  for (; j + 2 < nst; ++j) {
-    const int slot = j & 1;
-    WW_KSTEP(fa0, fb0, fa1, fb1, slot, 1, true, slot ^ 1, 8, true);      // + pieces 8-15 of stage j+1
-    WW_ADVANCE();
-    WW_KSTEP(fa1, fb1, fa0, fb0, slot, 2, true, 0, 0, false);
-    WW_KSTEP(fa0, fb0, fa1, fb1, slot, 3, true, 0, 0, false);
-    __builtin_amdgcn_s_waitcnt(0x0070);    // vmcnt(0): stage j+1 landed ; lgkmcnt(0): this slot is read out
-    __builtin_amdgcn_s_barrier();
-    WW_FENCE();
-    WW_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 0, true, slot, 0, true);      // + pieces 0-7 of stage j+2 into the slot just vacated
-  }
-  {  // tail: stages nst-2 and nst-1
-    const int slot = j & 1;
-    WW_KSTEP(fa0, fb0, fa1, fb1, slot, 1, true, slot ^ 1, 8, true);      // + pieces 8-15 of stage nst-1
-    WW_KSTEP(fa1, fb1, fa0, fb0, slot, 2, true, 0, 0, false);
-    WW_KSTEP(fa0, fb0, fa1, fb1, slot, 3, true, 0, 0, false);
-    __builtin_amdgcn_s_waitcnt(0x0070);
-    __builtin_amdgcn_s_barrier();
-    WW_FENCE();
-    WW_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 0, true, 0, 0, false);
-    WW_KSTEP(fa0, fb0, fa1, fb1, slot ^ 1, 1, true, 0, 0, false);
-    WW_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 2, true, 0, 0, false);
-    WW_KSTEP(fa0, fb0, fa1, fb1, slot ^ 1, 3, true, 0, 0, false);
-    WW_KSTEP(fa1, fb1, fa0, fb0, 0, 0, false, 0, 0, false);
-  }
-#undef WW_ADVANCE
+#define W256_NJ 4
+#define W256_LGKM0 true
+#define W256_READ(FA, FB, SLOT, S, U)                                                                                             \
+  W256_READ_TILES(FA, FB, true, true, smem + (SLOT) * CW_SLOT + wm * G_TILE_BYTES, smem + (SLOT) * CW_SLOT + (2 + wn) * G_TILE_BYTES, S, U)
+#define W256_REQUEST(SLOT, HALF, Q) W256_REQUEST_ODD(WW_ISSUE_ONE, SLOT, HALF, Q)
+#define W256_PROLOGUE() W256_PROLOGUE_16(WW_ISSUE_ONE)
+  W256_CLEAR(acc);
+  W256_MAINLOOP(nst);
 #undef WW_ISSUE_ONE
-#undef WW_READ_ONE
-#undef WW_MM
-#undef WW_KSTEP
-#undef WW_FENCE
+#undef W256_NJ
+#undef W256_LGKM0
+#undef W256_READ
+#undef W256_REQUEST
+#undef W256_PROLOGUE
+#undef W256_ADVANCE
   gemm_epilogue32_loops<EPI_WS, 4, BOUNDS, OT>(args.e, acc, m0 + wm * 128, n0 + wn * 128, lane, split, reinterpret_cast<float*>(smem + 2 * CW_SLOT) + wave * 128,
                                            smem + wave * 8192, smem + wave * 16384);
 }

@@ -27,6 +27,7 @@
 #include "common.h"
 
 #include "gemm_launch.h"
+#include "w256_loop.h"
 
 template <typename OT, bool TA, bool TB>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs args) {
@@ -260,20 +261,8 @@ __device__ __forceinline__ const uint16_t* glds_src_ptr2(const uint16_t* __restr
 // (gemm_epilogue32_loops, the epilogue of the swapped 32x32 accumulator layout: gemm_tiles.h)
 
 // =================================================================================================
-// "w256": 256 x 256 x 64 workgroup tile, FOUR waves (2 x 2) of 128 x 128 — one wave per SIMD, 256 accumulator registers (AGPRs) + ~170 VGPRs.
-// Round-2 design, measured step by step in tools/probe/gemm_lab.cpp (profiles/r02_gemm_lab.txt):
-//   * one wave per SIMD reads each LDS byte once per 128 x 128 sub-tile: 32 fragment reads per 64 MFMAs (t256's 128 x 64 waves need 48), and
-//     there is no second wave group to keep in phase — ONE barrier per K stage instead of eight;
-//   * an in-order wave stalls the matrix pipe whenever an instruction takes longer to issue than the ~28 cycles of cover one MFMA gives, so
-//     nothing is issued in bursts: fragment reads go one per MFMA under the first 8 MFMAs of every k16 step (all four waves hit the one LDS
-//     at once: a burst of 32 reads costs ~128 cycles), global_load_lds one per two MFMAs (texture addresser ~64 B/clk per CU);
-//     measured MFMA utilisation inside the K loop: 96 % without loads, 90 % with L2-resident operands, 70-80 % streaming from HBM;
-//   * operands are staged as WHOLE 128-byte lines (64-deep K stages): fetching each line as two 64-byte halves one stage apart (a 4-slot
-//     ring of 32-deep stages, which would allow a deeper prefetch) costs 7-11 % utilisation on HBM-streamed operands, while one stage less
-//     of prefetch depth costs only 1-2 %;
-//   * two 64-KiB slots [A0 | A1 | B0 | B1] (row / kmaj2 images as t256).  The barrier sits after the reads of the last k-step: the slot is
-//     then free and the loads of stage j+2 are spread over the next 32 MFMAs; every load gets 32-64 MFMAs (1-2 K-steps x 4) to land and the
-//     wait at the next barrier is vmcnt(0) with nothing newer in flight — a count, not a drain.
+// "w256": 256 x 256 x 64 workgroup tile, FOUR waves (2 x 2) of 128 x 128, one wave per SIMD, running the two-slot K loop of w256_loop.h (the
+// schedule and its measurements are described there).  Slot image [A0 | A1 | B0 | B1] (row / kmaj2 images); wave w stages sub-tile w.
 // Shapes: M, N multiples of 256, every K slice a multiple of 64 with at least two stages; everything else runs pipe2 / the fallback.
 // =================================================================================================
 #define W2_SLOT (4 * G_TILE_BYTES)
@@ -291,6 +280,19 @@ __device__ __forceinline__ const uint16_t* w256_src(const uint16_t* __restrict__
     return P + (k_begin + k) * ld + x0 + q * 16 + (pp & 1) * 8;
   }
 }
+
+// What the three kernels of this family hand to the shared loop.  In scope where they expand: TA, TB, smem, lane, wm, wn, the wave's source
+// pointers gsrc_e / gsrc_o with pair_step / stage_step, and its sub-tile my_sub.
+#define W256_NJ 4
+#define W256_LGKM0 (TA || TB)
+#define W256_ADVANCE() do { gsrc_e += stage_step; gsrc_o += stage_step; } while (0)
+// staging piece U (one KiB) of the wave's sub-tile into slot SLOT
+#define W2_ISSUE_ONE(SLOT, U, AUX)                                                                                                \
+  __builtin_amdgcn_global_load_lds((const GLB_AS void*)((((U) & 1) ? gsrc_o : gsrc_e) + ((U) >> 1) * pair_step),                  \
+                                   (LDS_AS void*)(my_sub + (SLOT) * W2_SLOT + (U) * 1024), 16, 0, AUX)
+// fragment U of k16-step S from slot SLOT: U = 0..3 the wave's A row-blocks, 4..7 its B column-blocks
+#define W2_READ_ONE(FA, FB, TRA, TRB, SLOT, S, U)                                                                                 \
+  W256_READ_TILES(FA, FB, TRA, TRB, smem + (SLOT) * W2_SLOT + wm * G_TILE_BYTES, smem + (SLOT) * W2_SLOT + (2 + wn) * G_TILE_BYTES, S, U)
 
 // EPI: the epilogue mode is a template parameter of THIS kernel (chosen on the host): an in-kernel 8-way switch over unrolled epilogues made the
 // code 10x larger and the whole kernel ~10 % slower (measured, same main loop)
@@ -323,106 +325,31 @@ __device__ __forceinline__ void gemm_w256_body(const GemmArgs& args) {
   unsigned char* const my_sub = smem + wave * G_TILE_BYTES;
 
   f32x16 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  W256_CLEAR(acc);
   s16x8 fa0[4], fb0[4], fa1[4], fb1[4];
   if (LAB == 2 || LAB == 3) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) { fa0[u] = (s16x8){1, 1, 1, 1, 1, 1, 1, 1}; fb0[u] = fa0[u]; fa1[u] = fa0[u]; fb1[u] = fa0[u]; }
   }
 
-#define W2_ISSUE_ONE(SLOT, U)                                                                                                     \
+  // the request and read hooks of the shared loop in this kernel's laboratory forms
+#define W2L_ISSUE_ONE(SLOT, U)                                                                                                    \
   do {                                                                                                                            \
     if (LAB == 3 || LAB == 5 || (LAB == 4 && ((U) & 1))) break;                                                                   \
-    __builtin_amdgcn_global_load_lds((const GLB_AS void*)((((U) & 1) ? gsrc_o : gsrc_e) + ((U) >> 1) * pair_step),                \
-                                     (LDS_AS void*)(my_sub + (SLOT) * W2_SLOT + (U) * 1024), 16, 0,                               \
-                                     LAB == 6 ? 1 : (LAB == 7 ? 2 : (LAB == 8 ? 16 : (LAB == 9 ? 17 : ENH_GLDS_AUX)))); /* lab 6-9: sc0 / nt / sc1 / sc0 sc1 */ \
+    W2_ISSUE_ONE(SLOT, U, LAB == 6 ? 1 : (LAB == 7 ? 2 : (LAB == 8 ? 16 : (LAB == 9 ? 17 : ENH_GLDS_AUX)))); /* lab 6-9: sc0 / nt / sc1 / sc0 sc1 */ \
   } while (0)
-#define W2_ADVANCE() do { gsrc_e += stage_step; gsrc_o += stage_step; } while (0)
-  // fragment u of k16-step S from slot SLOT: u = 0..3 the wave's A row-blocks, 4..7 its B column-blocks.  Transposed operands are read with the
-  // asm transpose read (the compiler's wait-count pass knows nothing about them: explicit lgkmcnt(0) at every k-step boundary below)
-#define W2_READ_ONE(FA, FB, SLOT, S, U)                                                                                           \
+#define W256_REQUEST(SLOT, HALF, Q) W256_REQUEST_ODD(W2L_ISSUE_ONE, SLOT, HALF, Q)
+#define W256_PROLOGUE() W256_PROLOGUE_16(W2L_ISSUE_ONE)
+#define W256_READ(FA, FB, SLOT, S, U)                                                                                             \
   do {                                                                                                                            \
     if (LAB == 2 || LAB == 3) break;                                                                                              \
-    if ((U) < 4) FA[(U) & 3] = frag32<TA && LAB == 0>(smem + (SLOT) * W2_SLOT + wm * G_TILE_BYTES, ((U) & 3) * 32, S, lane);      \
-    else FB[(U) & 3] = frag32<TB && LAB == 0>(smem + (SLOT) * W2_SLOT + (2 + wn) * G_TILE_BYTES, ((U) & 3) * 32, S, lane);        \
+    W2_READ_ONE(FA, FB, TA && LAB == 0, TB && LAB == 0, SLOT, S, U);                                                              \
   } while (0)
-#define W2_MM(Q, FA, FB)                                                                                                          \
-  acc[(Q) >> 2][(Q) & 3] = mfma32<OT>(FB[(Q) & 3], FA[(Q) >> 2], acc[(Q) >> 2][(Q) & 3])
-#define W2_MMZ(Q, FA, FB)                                                                                                         \
-  acc[(Q) >> 2][(Q) & 3] = mfma32<OT>(FB[(Q) & 3], FA[(Q) >> 2], zero16)
-#define W2_FENCE() __builtin_amdgcn_sched_barrier(0)
-  // one k16 step: 16 MFMAs on (FA, FB); under MFMAs 0-7 one fragment read each (k-step RS of slot RSLOT into RA / RB); under every odd MFMA one
-  // global_load_lds (pieces G0 .. G0+7 into slot GSLOT).  The step opens with lgkmcnt(0): its fragments were read >= 8 MFMAs ago.
-#define W2_KSTEP(FA, FB, RA, RB, RSLOT, RS, DO_READ, GSLOT, G0, DO_ISSUE)                                                         \
-  do {                                                                                                                            \
-    if (TA || TB) __builtin_amdgcn_s_waitcnt(0xC07F); /* asm transpose reads are invisible to the compiler's wait-count pass */      \
-    W2_FENCE();                                                                                                                   \
-    _Pragma("unroll") for (int q_ = 0; q_ < 16; ++q_) {                                                                           \
-      W2_MM(q_, FA, FB);                                                                                                          \
-      if ((DO_READ) && q_ < 8) { W2_READ_ONE(RA, RB, RSLOT, RS, q_); }                                                            \
-      if ((DO_ISSUE) && (q_ & 1)) { W2_ISSUE_ONE(GSLOT, (G0) + (q_ >> 1)); }                                                      \
-      W2_FENCE();                                                                                                                 \
-    }                                                                                                                             \
-  } while (0)
-
-  // the first k16 step of a tile in the persistent kernel: C operand = 0 instead of cleared accumulators; reads k-step RS, requests nothing
-#define W2_KSTEP_Z(FA, FB, RA, RB, RSLOT, RS)                                                                                     \
-  do {                                                                                                                            \
-    if (TA || TB) __builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
-    W2_FENCE();                                                                                                                   \
-    _Pragma("unroll") for (int q_ = 0; q_ < 16; ++q_) {                                                                           \
-      W2_MMZ(q_, FA, FB);                                                                                                         \
-      if (q_ < 8) { W2_READ_ONE(RA, RB, RSLOT, RS, q_); }                                                                         \
-      W2_FENCE();                                                                                                                 \
-    }                                                                                                                             \
-  } while (0)
-
-  // prologue: stage 0 -> slot 0 completely; pieces 0-7 of stage 1 -> slot 1 (pieces 8-15 follow under the first k-step)
-  {
-#pragma unroll
-  for (int u = 0; u < 16; ++u) W2_ISSUE_ONE(0, u);
-  W2_ADVANCE();
-#pragma unroll
-  for (int u = 0; u < 8; ++u) W2_ISSUE_ONE(1, u);
-  __builtin_amdgcn_s_waitcnt(0x0F78);   // vmcnt(8): stage 0 landed
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int u = 0; u < 8; ++u) W2_READ_ONE(fa0, fb0, 0, 0, u);
-  W2_FENCE();
-
-  // invariant at the top of iteration j: the source pointers are at stage j+1, whose pieces 0-7 are already issued into slot (j+1)&1
-  int j = 0;
-  for (; j + 2 < nst; ++j) {
-    const int slot = j & 1;
-    W2_KSTEP(fa0, fb0, fa1, fb1, slot, 1, true, slot ^ 1, 8, true);      // + pieces 8-15 of stage j+1
-    W2_ADVANCE();
-    W2_KSTEP(fa1, fb1, fa0, fb0, slot, 2, true, 0, 0, false);
-    W2_KSTEP(fa0, fb0, fa1, fb1, slot, 3, true, 0, 0, false);
-    __builtin_amdgcn_s_waitcnt(0x0070);    // vmcnt(0): stage j+1 landed (nothing newer outstanding) ; lgkmcnt(0): this slot is read out
-    __builtin_amdgcn_s_barrier();
-    W2_FENCE();
-    W2_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 0, true, slot, 0, true);      // + pieces 0-7 of stage j+2 into the slot just vacated
-  }
-  {  // tail: stages nst-2 and nst-1
-    const int slot = j & 1;
-    W2_KSTEP(fa0, fb0, fa1, fb1, slot, 1, true, slot ^ 1, 8, true);      // + pieces 8-15 of stage nst-1
-    W2_KSTEP(fa1, fb1, fa0, fb0, slot, 2, true, 0, 0, false);
-    W2_KSTEP(fa0, fb0, fa1, fb1, slot, 3, true, 0, 0, false);
-    __builtin_amdgcn_s_waitcnt(0x0070);
-    __builtin_amdgcn_s_barrier();
-    W2_FENCE();
-    W2_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 0, true, 0, 0, false);
-    W2_KSTEP(fa0, fb0, fa1, fb1, slot ^ 1, 1, true, 0, 0, false);
-    W2_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 2, true, 0, 0, false);
-    W2_KSTEP(fa0, fb0, fa1, fb1, slot ^ 1, 3, true, 0, 0, false);
-    W2_KSTEP(fa1, fb1, fa0, fb0, 0, 0, false, 0, 0, false);
-  }
-  }
+  W256_MAINLOOP(nst);
+#undef W2L_ISSUE_ONE
+#undef W256_REQUEST
+#undef W256_PROLOGUE
+#undef W256_READ
   gemm_epilogue32_loops<EPI, 4, false, OT>(args, acc, m0 + wm * 128, n0 + wn * 128, lane, split,
                                        reinterpret_cast<float*>(smem + 2 * W2_SLOT) + wave * 128, smem + wave * 8192, smem + wave * 16384);
 }
@@ -703,9 +630,12 @@ __device__ __forceinline__ void tile_claim_retire(unsigned* ctr, unsigned f, int
   if (f == n_q + w_q - 1u) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// the request and read hooks of the persistent kernels (gemm_w256r_kernel: the read only)
+#define W2P_ISSUE_ONE(SLOT, U) W2_ISSUE_ONE(SLOT, U, ENH_GLDS_AUX)
+#define W256_REQUEST(SLOT, HALF, Q) W256_REQUEST_ODD(W2P_ISSUE_ONE, SLOT, HALF, Q)
+#define W256_READ(FA, FB, SLOT, S, U) W2_READ_ONE(FA, FB, TA, TB, SLOT, S, U)
 template <typename OT, bool TA, bool TB, int EPI, bool DYN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_w256p_kernel(const GemmArgs args) {
-  constexpr int LAB = 0;   // (the shared K-step macros name the one-tile kernel's laboratory switch)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int t = threadIdx.x;
   const int lane = t & 63;
@@ -759,16 +689,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   // prologue of the workgroup: stages 0 and 1 of its first tile
 #pragma unroll
-  for (int u = 0; u < 16; ++u) W2_ISSUE_ONE(0, u);
-  W2_ADVANCE();
+  for (int u = 0; u < 16; ++u) W2P_ISSUE_ONE(0, u);
+  W256_ADVANCE();
 #pragma unroll
-  for (int u = 0; u < 16; ++u) W2_ISSUE_ONE(1, u);
-  W2_ADVANCE();
+  for (int u = 0; u < 16; ++u) W2P_ISSUE_ONE(1, u);
+  W256_ADVANCE();
   __builtin_amdgcn_s_waitcnt(0x4F70);   // vmcnt(16): stage 0 landed
   __builtin_amdgcn_s_barrier();
 #pragma unroll
-  for (int u = 0; u < 8; ++u) W2_READ_ONE(fa0, fb0, 0, 0, u);
-  W2_FENCE();
+  for (int u = 0; u < 8; ++u) W256_READ(fa0, fb0, 0, 0, u);
+  W256_FENCE();
 
   int par = 0;   // slot of the current tile's stage 0
   for (;;) {
@@ -781,50 +711,50 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     unsigned fnext = 0;
     if (DYN && t == 0) fnext = tile_claim(ctr);     // the next tile of this XCD's queue: in flight under the first K stage
     {
-      W2_KSTEP_Z(fa0, fb0, fa1, fb1, par, 1);
-      W2_KSTEP(fa1, fb1, fa0, fb0, par, 2, true, 0, 0, false);
-      W2_KSTEP(fa0, fb0, fa1, fb1, par, 3, true, 0, 0, false);
+      W256_KSTEP_Z(fa0, fb0, fa1, fb1, par, 1);
+      W256_KSTEP(fa1, fb1, fa0, fb0, par, 2, true, 0, 0, false);
+      W256_KSTEP(fa0, fb0, fa1, fb1, par, 3, true, 0, 0, false);
       __builtin_amdgcn_s_waitcnt(0x0070);    // vmcnt(0): stage 1 landed (and the previous tile's stores are acknowledged, and the claim has returned)
       if (DYN) {
         if (t == 0) { tile_claim_retire(ctr, fnext, ntiles, xcd); lds_store_u32(s_next, fnext); }
         __builtin_amdgcn_s_waitcnt(0xC07F);  // the mailbox write is performed before the barrier lets anybody read it
       }
       __builtin_amdgcn_s_barrier();
-      W2_FENCE();
+      W256_FENCE();
       if (DYN) {
         vnext = xcd + 8 * (int)lds_load_u32_sync(s_next);
         last_tile = vnext >= ntiles;
         if (last_tile) vnext = vt;
       }
-      W2_KSTEP(fa1, fb1, fa0, fb0, par ^ 1, 0, true, par, 0, true);      // + pieces 0-7 of stage 2
+      W256_KSTEP(fa1, fb1, fa0, fb0, par ^ 1, 0, true, par, 0, true);      // + pieces 0-7 of stage 2
     }
     float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);   // this tile's bias, for the epilogue's LDS strip: requested now, consumed a K loop later
     if ((EPI == EPI_BF16_BIAS_TANH || EPI == EPI_F32_BIAS_RES || EPI == EPI_BF16_TANH_SPLIT) && lane < 32) bias4 = *reinterpret_cast<const float4*>(args.bias + n0 + wn * 128 + lane * 4);
     for (int j = 1; j < nst; ++j) {
       const int slot = par ^ (j & 1);
-      W2_KSTEP(fa0, fb0, fa1, fb1, slot, 1, true, slot ^ 1, 8, true);      // + pieces 8-15 of stage j+1
+      W256_KSTEP(fa0, fb0, fa1, fb1, slot, 1, true, slot ^ 1, 1, true);      // + pieces 8-15 of stage j+1
       if (j == nst - 2) {   // stage j+2 is the NEXT tile's stage 0
         gemm_tile_coords_of(args, vnext, split_, tile_m, tile_n);
         const int64_t x0 = (stage_a ? (int64_t)tile_m : (int64_t)tile_n) * 256 + xw;
         gsrc_e = base_e + x0 * x_step; gsrc_o = base_o + x0 * x_step;
       } else {
-        W2_ADVANCE();
+        W256_ADVANCE();
       }
-      W2_KSTEP(fa1, fb1, fa0, fb0, slot, 2, true, 0, 0, false);
-      W2_KSTEP(fa0, fb0, fa1, fb1, slot, 3, true, 0, 0, false);
+      W256_KSTEP(fa1, fb1, fa0, fb0, slot, 2, true, 0, 0, false);
+      W256_KSTEP(fa0, fb0, fa1, fb1, slot, 3, true, 0, 0, false);
       __builtin_amdgcn_s_waitcnt(0x0070);
       __builtin_amdgcn_s_barrier();
-      W2_FENCE();
-      W2_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 0, true, slot, 0, true);      // + pieces 0-7 of stage j+2 into the slot just vacated
+      W256_FENCE();
+      W256_KSTEP(fa1, fb1, fa0, fb0, slot ^ 1, 0, true, slot, 0, true);      // + pieces 0-7 of stage j+2 into the slot just vacated
     }
     {   // the rest of the next tile's stage 1, before any store of this tile
       const int slot = par ^ ((nst - 1) & 1);
 #pragma unroll
-      for (int u = 8; u < 16; ++u) W2_ISSUE_ONE(slot, u);
-      W2_ADVANCE();
+      for (int u = 8; u < 16; ++u) W2P_ISSUE_ONE(slot, u);
+      W256_ADVANCE();
     }
     gemm_epilogue_p<EPI, OT>(args, acc, m0 + wm * 128, n0 + wn * 128, lane, wave_bias, st, at, bias4);
-    W2_FENCE();
+    W256_FENCE();
     if (last_tile) break;
     vt = vnext;
     par ^= nst & 1;
@@ -848,7 +778,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #define W2R_D 2
 template <typename OT, bool TB, int EPI, bool DYN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_w256r_kernel(const GemmArgs args) {
-  constexpr int LAB = 0;   // (the shared K-step macros name the one-tile kernel's laboratory switch)
   constexpr bool TA = false;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int t = threadIdx.x;
@@ -911,33 +840,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #define W2R_K0(FA, FB, RA, RB, RSLOT, ZERO, WSLOT, SET)                                                                           \
   do {                                                                                                                            \
     if (TA || TB) __builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
-    W2_FENCE();                                                                                                                   \
+    W256_FENCE();                                                                                                                 \
     _Pragma("unroll") for (int q_ = 0; q_ < 16; ++q_) {                                                                           \
-      if (ZERO) { W2_MMZ(q_, FA, FB); } else { W2_MM(q_, FA, FB); }                                                               \
-      if (q_ < 8) { W2_READ_ONE(RA, RB, RSLOT, 1, q_); }                                                                          \
+      if (ZERO) { W256_MMZ(q_, FA, FB); } else { W256_MM(q_, FA, FB); }                                                           \
+      if (q_ < 8) { W256_READ(RA, RB, RSLOT, 1, q_); }                                                                            \
       if (q_ & 1) { W2R_A_WRITE(WSLOT, SET, q_ >> 1); W2R_A_LOAD(SET, q_ >> 1, 0); }                                              \
-      W2_FENCE();                                                                                                                 \
+      W256_FENCE();                                                                                                               \
     }                                                                                                                             \
   } while (0)
 #define W2R_K12(FA, FB, RA, RB, RSLOT, RS)                                                                                        \
   do {                                                                                                                            \
     if (TA || TB) __builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
-    W2_FENCE();                                                                                                                   \
+    W256_FENCE();                                                                                                                 \
     _Pragma("unroll") for (int q_ = 0; q_ < 16; ++q_) {                                                                           \
-      W2_MM(q_, FA, FB);                                                                                                          \
-      if (q_ < 8) { W2_READ_ONE(RA, RB, RSLOT, RS, q_); }                                                                         \
-      W2_FENCE();                                                                                                                 \
+      W256_MM(q_, FA, FB);                                                                                                        \
+      if (q_ < 8) { W256_READ(RA, RB, RSLOT, RS, q_); }                                                                           \
+      W256_FENCE();                                                                                                               \
     }                                                                                                                             \
   } while (0)
 #define W2R_K3(FA, FB, RA, RB, RSLOT, BSLOT)                                                                                      \
   do {                                                                                                                            \
     if (TA || TB) __builtin_amdgcn_s_waitcnt(0xC07F);                                                                             \
-    W2_FENCE();                                                                                                                   \
+    W256_FENCE();                                                                                                                 \
     _Pragma("unroll") for (int q_ = 0; q_ < 16; ++q_) {                                                                           \
-      W2_MM(q_, FA, FB);                                                                                                          \
-      if (q_ < 8) { W2_READ_ONE(RA, RB, RSLOT, 0, q_); }                                                                          \
+      W256_MM(q_, FA, FB);                                                                                                        \
+      if (q_ < 8) { W256_READ(RA, RB, RSLOT, 0, q_); }                                                                            \
       if (q_ & 1) { W2R_B_DMA(BSLOT, q_ >> 1, 0); }                                                                               \
-      W2_FENCE();                                                                                                                 \
+      W256_FENCE();                                                                                                               \
     }                                                                                                                             \
   } while (0)
   // one K stage (local index j): SET = (j + 1) % 2 is the register set that holds A(j+1)
@@ -953,7 +882,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     __builtin_amdgcn_s_waitcnt(WAIT);                                                                                             \
     HOOK;                                                                                                                         \
     __builtin_amdgcn_s_barrier();                                                                                                 \
-    W2_FENCE();                                                                                                                   \
+    W256_FENCE();                                                                                                                 \
     if (j == nst - 2) { gB_e = baseB_e + offB_next; gB_o = baseB_o + offB_next; }           /* B(j+2) is the next tile's stage 0 */ \
     W2R_K3(fa1, fb1, fa0, fb0, slot_ ^ 1, slot_);                                                                                 \
     gB_e += stageB; gB_o += stageB;                                                                                               \
@@ -964,26 +893,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // wait below leaves the last 16 in flight; fenced, because the scheduler clusters the two register groups by address otherwise)
 #pragma unroll
   for (int u = 0; u < 8; ++u) W2R_A_DMA(0, u, 0);
-  W2_FENCE();
+  W256_FENCE();
 #pragma unroll
   for (int u = 0; u < 8; ++u) W2R_A_LOAD(1, u, G_BK);
-  W2_FENCE();
+  W256_FENCE();
 #pragma unroll
   for (int u = 0; u < 8; ++u) W2R_B_DMA(0, u, 0);
-  W2_FENCE();
+  W256_FENCE();
 #pragma unroll
   for (int u = 0; u < 8; ++u) W2R_A_LOAD(0, u, 2 * G_BK);
-  W2_FENCE();
+  W256_FENCE();
 #pragma unroll
   for (int u = 0; u < 8; ++u) W2R_B_DMA(1, u, stageB);
-  W2_FENCE();
+  W256_FENCE();
   gA_e += 3 * G_BK; gA_o += 3 * G_BK;
   gB_e += 2 * stageB; gB_o += 2 * stageB;
   __builtin_amdgcn_s_waitcnt(0x4F70);   // vmcnt(16): stage 0 landed (set 0 and B(1) are younger)
   __builtin_amdgcn_s_barrier();
 #pragma unroll
-  for (int u = 0; u < 8; ++u) W2_READ_ONE(fa0, fb0, 0, 0, u);
-  W2_FENCE();
+  for (int u = 0; u < 8; ++u) W256_READ(fa0, fb0, 0, 0, u);
+  W256_FENCE();
 
   // The tile loop is rotated — its body runs stages 1 .. nst-1, the epilogue and the NEXT tile's stage 0 — so that the two forms of stage 0's wait
   // (vmcnt(8) in the workgroup's first tile, vmcnt(8 + stores) after an epilogue) sit on separate paths: with one stage-0 body and a runtime flag the
@@ -1021,7 +950,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       W2R_STAGE(false, 0, 0x0078, (void)0);
     }
     gemm_epilogue_p<EPI, OT>(args, acc, m0 + wm * 128, n0 + wn * 128, lane, wave_bias, st, at, bias4);   // (the next wait counts this epilogue's stores)
-    W2_FENCE();
+    W256_FENCE();
     vt = vnext;
     m0 = (int64_t)tile_m * 256; n0 = (int64_t)tile_n * 256;
     if (!DYN) {
@@ -1045,14 +974,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #undef W2R_K3
 #undef W2R_STAGE
 }
+#undef W2P_ISSUE_ONE
 #undef W2_ISSUE_ONE
-#undef W2_ADVANCE
 #undef W2_READ_ONE
-#undef W2_MM
-#undef W2_MMZ
-#undef W2_FENCE
-#undef W2_KSTEP
-#undef W2_KSTEP_Z
+#undef W256_NJ
+#undef W256_LGKM0
+#undef W256_ADVANCE
+#undef W256_REQUEST
+#undef W256_READ
 
 
 // =================================================================================================

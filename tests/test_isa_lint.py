@@ -76,3 +76,13 @@ def test_attention_row_maximum_is_fused_and_hazard_padded(stats):
         assert dkv and dq and stats[dkv[0]]["vgpr"] <= 168 and stats[dq[0]]["vgpr"] <= 168                                          # three waves per SIMD
         for n in dkv + dq + [fwd]:
             assert stats[n].get("scratch_bytes", 0) == 0 and stats[n].get("spills", 0) == 0, (n, stats[n])
+
+
+def test_instruction_diff_reports_first_difference_and_one_sided_symbols():
+    """the comparison behind `isa_lint.py --diff OLD.so NEW.so`, on hand-written instruction lists"""
+    old = {"k_a": ["s_load_dwordx2 s[0:1], s[4:5], 0x0", "s_waitcnt lgkmcnt(0)", "s_endpgm"],
+           "k_b": ["v_mov_b32_e32 v0, 0", "s_endpgm"]}
+    assert isa_lint.diff_instructions(old, {k: list(v) for k, v in old.items()}) == {"k_a": "same", "k_b": "same"}
+    changed = {"k_a": ["s_load_dwordx2 s[0:1], s[4:5], 0x0", "s_waitcnt vmcnt(0)", "s_endpgm"], "k_b": old["k_b"] + ["s_nop 0"]}
+    assert isa_lint.diff_instructions(old, changed) == {"k_a": (1, "s_waitcnt lgkmcnt(0)", "s_waitcnt vmcnt(0)"), "k_b": (2, None, "s_nop 0")}
+    assert isa_lint.diff_instructions(old, {"k_a": old["k_a"], "k_c": ["s_endpgm"]}) == {"k_a": "same", "k_b": "only in old", "k_c": "only in new"}

@@ -3,6 +3,7 @@ states about the instruction stream (§3.1c: the tile-claim atomic stays ONE in-
 do not touch scratch).  Runs on CPU (llvm-objdump / llvm-readelf of the ROCm toolchain); `tests/test_isa_lint.py` asserts on it.
 
     python tools/isa_lint.py [path/to/libenh_hip.so]      # prints the table
+    python tools/isa_lint.py --diff OLD.so NEW.so         # per kernel symbol: same, or the first differing instruction; exit 1 on any difference
 """
 import collections
 import os
@@ -79,6 +80,57 @@ def kernel_stats(so_path=DEFAULT_SO):
     return {dm[n]: dict(stats[n]) for n in names}
 
 
+def kernel_instructions(so_path=DEFAULT_SO):
+    """{mangled symbol: [instruction text]} of every function in the .so's gfx950 code objects: mnemonic and operands only (no addresses, encodings,
+    comments or directives).  Branches print as offsets relative to themselves; the one operand that does depend on where a function's neighbours lie,
+    the literal of the s_add_u32 / s_addc_u32 pair that turns an s_getpc_b64 into the address of a global, is replaced by <pcrel>."""
+    out = {}
+    with tempfile.TemporaryDirectory() as wd:
+        objs = code_objects(so_path, wd)
+        assert objs, f"no gfx950 code object in {so_path}"
+        for o in objs:
+            dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--mcpu=gfx950", o], capture_output=True, text=True, check=True).stdout
+            cur, after_getpc = None, 0
+            for line in dis.splitlines():
+                m = re.match(r"^[0-9a-f]+ <(.+)>:", line)
+                if m:
+                    cur = out.setdefault(m.group(1), [])
+                    continue
+                if cur is None or not line.startswith("\t"):
+                    continue
+                ins = " ".join(line.split("//")[0].split())
+                if after_getpc and re.match(r"s_addc?_u32 ", ins):
+                    ins = re.sub(r", (0x[0-9a-f]+|\d+)$", ", <pcrel>", ins)
+                after_getpc = 2 if ins.startswith("s_getpc_b64") else max(after_getpc - 1, 0)
+                cur.append(ins)
+    return out
+
+
+def diff_instructions(old, new):
+    """compare two {symbol: [instruction text]} dictionaries: {symbol: "same" | "only in old" | "only in new" | (index, old instruction, new instruction)}
+    with the first difference (None for the side that has ended)"""
+    res = {}
+    for sym in sorted(set(old) | set(new)):
+        if sym not in new or sym not in old:
+            res[sym] = "only in old" if sym in old else "only in new"
+            continue
+        a, b = old[sym], new[sym]
+        i = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), None if len(a) == len(b) else min(len(a), len(b)))
+        res[sym] = "same" if i is None else (i, a[i] if i < len(a) else None, b[i] if i < len(b) else None)
+    return res
+
+
+def diff_main(old_so, new_so):
+    res = diff_instructions(kernel_instructions(old_so), kernel_instructions(new_so))
+    dm = _demangle(list(res))
+    for sym, r in res.items():
+        print(f"{dm[sym]}: " + (r if isinstance(r, str) else f"DIFFERS at instruction {r[0]}: {r[1]!r} -> {r[2]!r}"))
+    n_same = sum(r == "same" for r in res.values())
+    n_one = sum(isinstance(r, str) and r != "same" for r in res.values())
+    print(f"isa diff: {n_same} of {len(res)} symbols same, {len(res) - n_same - n_one} differ, {n_one} on one side only")
+    return 0 if n_same == len(res) else 1
+
+
 def persistent_gemm_pairs(stats):
     """(dynamic-schedule symbol, its static-schedule twin) for every persistent GEMM instantiation"""
     pairs = []
@@ -92,6 +144,10 @@ def persistent_gemm_pairs(stats):
 
 
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--diff":
+        if len(sys.argv) != 4:
+            sys.exit("usage: isa_lint.py --diff OLD.so NEW.so")
+        return diff_main(sys.argv[2], sys.argv[3])
     so = sys.argv[1] if len(sys.argv) > 1 else DEFAULT_SO
     st = kernel_stats(so)
     print(f"{len(st)} kernels in {so}")
