@@ -17,6 +17,35 @@
 // kernels (S is recomputed twice) so that no atomics are needed and the result is deterministic.
 #include "attention_common.h"
 
+// ---- the fragment stream of a tile (LDS-DMA kernels) ----------------------------------------------------------------------------------------------
+// A tile's MFMAs take their operand fragments from a stream of counted reads (attention_common.h, att_req_* / att_take_*): fragment I feeds MFMA I.
+// The stream repeats with period P; the first 8 fragments of a period are row fragments (one ds_read_b128), the rest transpose fragments (two
+// ds_read_b64_tr_b16).  A fragment is requested ATT_PF MFMAs ahead of the one that consumes it (4 registers per level), inside RUNS: the first ATT_PF
+// fragments of a run are requested together where it starts — the one place where an MFMA waits for a read issued just in front of it.  A run is the
+// whole tile (WHOLE: fragments are also held across the exponentials between two phases; dQ and dK/dV, three waves per SIMD) or one phase — the row
+// fragments of a block | its transpose fragments (the forward: 126 registers so, 128 = the end of its four-wave class with WHOLE; measured the same).
+// Two levels measured the same as one on dQ (profiles/r07_attention_pipeline.txt).
+#define ATT_PF 1
+__host__ __device__ constexpr bool att_run_start(int k, int P, bool WHOLE) { return k == 0 || (!WHOLE && (k % P == 0 || k % P == 8)); }
+__host__ __device__ constexpr int att_run_end(int I, int NF, int P, bool WHOLE) {
+  int e = I + 1;
+  while (e < NF && !att_run_start(e, P, WHOLE)) ++e;
+  return e;
+}
+// LDS operations the kernel has issued behind fragment I's own when MFMA I takes it
+__host__ __device__ constexpr int att_pending(int I, int NF, int P, bool WHOLE) {
+  int n = 0;
+  for (int k = I + 1; k <= I + ATT_PF && k < att_run_end(I, NF, P, WHOLE); ++k) n += (k % P < 8) ? 1 : 2;
+  return n;
+}
+// what MFMA I requests before it takes its own fragment.  req(integral_constant<int, K>) requests fragment K.
+template <int I, int NF, int P, bool WHOLE, typename REQ>
+__device__ __forceinline__ void att_stream_request(REQ& req) {
+  constexpr int E = att_run_end(I, NF, P, WHOLE);
+  if constexpr (att_run_start(I, P, WHOLE)) att_static_for<I, (I + ATT_PF < E ? I + ATT_PF : E)>(req);
+  if constexpr (I + ATT_PF < E) req(std::integral_constant<int, I + ATT_PF>{});
+}
+
 // =================================================================================================
 // forward
 // =================================================================================================
@@ -70,6 +99,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pre_kernel(const uint16_t* __
   const unsigned ko0 = att_dma_lane_off((int)RS, lane, 0), ko1 = att_dma_lane_off((int)RS, lane, 1);
   att_dma_tile(Kp, RS, 0, smem[0][0], wave_u, ko0, ko1);
   att_dma_tile(Vp, RS, 0, smem[0][1], wave_u, ko0, ko1);
+  unsigned ra[4], ta[2][2];      // this lane's fragment addresses in the stage being read
+  att_ring_addresses(ra, ta, &smem[0][0][0], lane);
 #pragma unroll
   for (int ds = 0; ds < 4; ++ds) att_pin(qf[ds]);
   ATT_LOOP_ENTRY();
@@ -80,16 +111,25 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pre_kernel(const uint16_t* __
       att_dma_tile(Kp, RS, (kt + 1) * 64, smem[st ^ 1][0], wave_u, ko0, ko1);
       att_dma_tile(Vp, RS, (kt + 1) * 64, smem[st ^ 1][1], wave_u, ko0, ko1);
     }
-    const unsigned char* kt_ = smem[st][0];
-    const unsigned char* vt_ = smem[st][1];
     // (Round 5: issuing the tile's fragment reads ahead of their use in a fenced order — all eight K fragments at once, one V fragment behind every S
     // product, counted lgkmcnt waits instead of the compiler's read / wait(0) / MFMA chains — needs 168 registers (three waves per SIMD instead of four)
-    // and measured no faster than the round-4 kernel; the compiler's serial form at four waves is the fastest of the three: profiles/r05_attention_lab.txt §6.)
+    // and measured no faster than the round-4 kernel: profiles/r05_attention_lab.txt §6.  The stream below holds ATT_PF + 1 fragments, not eight.)
+    // Fragment I of the tile's 16 (see "the fragment stream of a tile" above): I < 8: row fragment ds = I % 4 of K, key block kb = I / 4 (-> S);
+    // else transpose fragment (kb, c2, db) = ((I - 8) / 4, ((I - 8) / 2) % 2, I % 2) of V (-> O).
+    constexpr int NF = 16;
+    u32x4 fr[ATT_PF + 1];
+    att_u64 tl[ATT_PF + 1], th[ATT_PF + 1];
+    auto req = [&](auto ic) {
+      constexpr int I = decltype(ic)::value, B = I % (ATT_PF + 1);
+      if constexpr (I < 8) att_req_row<(I >> 2) * 32 * 128>(fr[B], ra[I & 3]);
+      else att_req_tr<ATT_TILE_BYTES + (((I - 8) >> 2) * 32 + 16 * (((I - 8) >> 1) & 1)) * 128>(tl[B], th[B], ta[I & 1][0], ta[I & 1][1]);
+    };
     f32x16 s[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int ds = 0; ds < 4; ++ds) s[kb] = MFMA32(att_frag_row(kt_, kb * 32, ds, l31, hi), qf[ds], ds == 0 ? negm : s[kb]);   // S^T[key][q] - m_ref[q]
+    att_static_for<0, 8>([&](auto ic) {
+      constexpr int I = decltype(ic)::value, kb = I >> 2, ds = I & 3, B = I % (ATT_PF + 1);
+      att_stream_request<I, NF, 16, false>(req);
+      s[kb] = MFMA32(att_take_row<att_pending(I, NF, 16, false)>(fr[B]), qf[ds], ds == 0 ? negm : s[kb]);   // S^T[key][q] - m_ref[q]
+    });
     // four independent v_max3 chains of depth 4 (one dependent chain of 16 leaves the in-order wave waiting on its own previous instruction)
     float mq[4];
 #pragma unroll
@@ -119,20 +159,23 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_pre_kernel(const uint16_t* __
       for (int r = 0; r < 16; ++r) { s[0][r] -= delta; s[1][r] -= delta; negm[r] = -m_ref; }
     }
     // ---- numerators, packed; row sum of the packed values; O^T[d][q] += V^T P^T ----
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int c2 = 0; c2 < 2; ++c2) {
+    s16x8 pb;
+    att_static_for<8, 16>([&](auto ic) {
+      constexpr int I = decltype(ic)::value, kb = (I - 8) >> 2, c2 = ((I - 8) >> 1) & 1, db = I & 1, B = I % (ATT_PF + 1);
+      att_stream_request<I, NF, 16, false>(req);
+      if constexpr (db == 0) {
         float p8[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) p8[j] = __builtin_amdgcn_exp2f(s[kb][c2 * 8 + j]);
         const u32x4 pk = {pack2<OT>(p8[0], p8[1]), pack2<OT>(p8[2], p8[3]), pack2<OT>(p8[4], p8[5]), pack2<OT>(p8[6], p8[7])};
 #pragma unroll
         for (int j = 0; j < 4; ++j) l2[j & 1] += (f32x2){p8[2 * j], p8[2 * j + 1]};      // exact f32 row sum, two lanes of one v_pk_add_f32 (lse stays exact to f32), two chains
-        const s16x8 pb = __builtin_bit_cast(s16x8, pk);
-#pragma unroll
-        for (int db = 0; db < 2; ++db) o[db] = MFMA32(att_frag_tr(vt_, kb * 32 + 16 * c2, db, lane), pb, o[db]);
+        pb = __builtin_bit_cast(s16x8, pk);
       }
+      o[db] = MFMA32(att_take_tr<att_pending(I, NF, 16, false)>(tl[B], th[B]), pb, o[db]);
+    });
+    att_ring_advance(ra, ta, st);
+    ATT_FENCE();                             // (every MFMA of the tile is issued before the wave parks)
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): this wave's share of the next tile has landed
     __syncthreads();
   }
@@ -215,35 +258,54 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const uint16_t* __r
   for (int ds = 0; ds < 4; ++ds) { att_pin(qf[ds]); att_pin(dof[ds]); }
   ATT_LOOP_ENTRY();
   __syncthreads();
+  // The tile's 24 MFMAs take their fragments from a stream of 24 counted reads (attention_common.h, att_req_* / att_take_*), requested ATT_PF
+  // fragments ahead of the MFMA that consumes them — also across the exponentials between the S / dP products and the dQ products and from one key block
+  // to the next; only the first ATT_PF fragments of a tile, behind the barrier that publishes the stage, are awaited with nothing to do.
+  // Fragment I: key block kb = I / 12; j = I % 12 < 8: row fragment ds = j / 2 of K (j even, -> S) or V (j odd, -> dP); else transpose fragment
+  // (c2, db) = ((j - 8) / 2, (j - 8) % 2) of K (-> dQ).  Same products, same order per accumulator as the serial form: the same bits.
+  unsigned ra[4], ta[2][2];      // this lane's fragment addresses in the stage being read
+  att_ring_addresses(ra, ta, &smem[0][0][0], lane);
   for (int kt = 0; kt < nt; ++kt) {
     const int st = kt & 1;
     if (kt + 1 < nt) {
       att_dma_tile(Kp, RS, (kt + 1) * 64, smem[st ^ 1][0], wave_u, ko0, ko1);
       att_dma_tile(Vp, RS, (kt + 1) * 64, smem[st ^ 1][1], wave_u, ko0, ko1);
     }
-    const unsigned char* kt_ = smem[st][0];
-    const unsigned char* vt_ = smem[st][1];
+    constexpr int NF = 24;
+    u32x4 fr[ATT_PF + 1];
+    att_u64 tl[ATT_PF + 1], th[ATT_PF + 1];
+    auto req = [&](auto ic) {
+      constexpr int I = decltype(ic)::value, kb = I / 12, j = I % 12, B = I % (ATT_PF + 1);
+      if constexpr (j < 8) att_req_row<(j & 1) * ATT_TILE_BYTES + kb * 32 * 128>(fr[B], ra[j >> 1]);
+      else att_req_tr<(kb * 32 + 16 * ((j - 8) >> 1)) * 128>(tl[B], th[B], ta[j & 1][0], ta[j & 1][1]);
+    };
+    f32x16 s, dp;
+    float dsv[16];
+    s16x8 dsb;
+    att_static_for<0, NF>([&](auto ic) {
+      constexpr int I = decltype(ic)::value, j = I % 12, B = I % (ATT_PF + 1);
+      att_stream_request<I, NF, 12, true>(req);
+      constexpr int PEND = att_pending(I, NF, 12, true);
+      if constexpr (j < 8) {
+        constexpr int ds = j >> 1;
+        const s16x8 f = att_take_row<PEND>(fr[B]);
+        if constexpr ((j & 1) == 0) s = MFMA32(f, qf[ds], ds == 0 ? negl : s);     // S^T[key][q]  (- lse[q] in MODE 2)
+        else dp = MFMA32(f, dof[ds], ds == 0 ? negd : dp);                         // dP^T[key][q] = V dO^T  (- delta[q] in MODE >= 1)
+        if constexpr (j == 7) {
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      f32x16 s, dp;
-#pragma unroll
-      for (int ds = 0; ds < 4; ++ds) {
-        s = MFMA32(att_frag_row(kt_, kb * 32, ds, l31, hi), qf[ds], ds == 0 ? negl : s);     // S^T[key][q]  (- lse[q] in MODE 2)
-        dp = MFMA32(att_frag_row(vt_, kb * 32, ds, l31, hi), dof[ds], ds == 0 ? negd : dp);  // dP^T[key][q] = V dO^T  (- delta[q] in MODE >= 1)
+          for (int r = 0; r < 16; ++r) {
+            const float pr = MODE == 2 ? __builtin_amdgcn_exp2f(s[r]) : __builtin_amdgcn_exp2f(s[r] * scale_log2 - lse_q);
+            dsv[r] = MODE >= 1 ? pr * dp[r] : pr * (dp[r] - del_q);     // (the factor `scale` of dS is applied once to the finished dQ)
+          }
+        }
+      } else {
+        constexpr int c2 = (j - 8) >> 1, db = j & 1;
+        if constexpr (db == 0) dsb = pack8<OT>(&dsv[c2 * 8]);
+        dq[db] = MFMA32(att_take_tr<PEND>(tl[B], th[B]), dsb, dq[db]);              // dQ^T[d][q] += K^T dS^T
       }
-      float dsv[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pr = MODE == 2 ? __builtin_amdgcn_exp2f(s[r]) : __builtin_amdgcn_exp2f(s[r] * scale_log2 - lse_q);
-        dsv[r] = MODE >= 1 ? pr * dp[r] : pr * (dp[r] - del_q);     // (the factor `scale` of dS is applied once to the finished dQ)
-      }
-#pragma unroll
-      for (int c2 = 0; c2 < 2; ++c2) {
-        const s16x8 dsb = pack8<OT>(&dsv[c2 * 8]);
-#pragma unroll
-        for (int db = 0; db < 2; ++db) dq[db] = MFMA32(att_frag_tr(kt_, kb * 32 + 16 * c2, db, lane), dsb, dq[db]);  // dQ^T[d][q] += K^T dS^T
-      }
-    }
+    });
+    att_ring_advance(ra, ta, st);
+    ATT_FENCE();                             // (every MFMA of the tile is issued before the wave parks)
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): this wave's share of the next tile has landed
     __syncthreads();
   }
@@ -266,9 +328,6 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dq_kernel(const uint16_t* __r
 // loaded from LDS straight into the accumulator registers (the same four 16-byte reads per block as before, no extra registers), which removes the
 // per-element subtraction (and the scale-and-subtract before the exponential).  kscale: the factor of the finished dK (scale, or ln 2 with PRE).
 template <bool CINIT, bool PRE, typename OT>
-#ifndef ATT_DKV_DMA
-#define ATT_DKV_DMA 1
-#endif
 #ifndef ATT_DKV_OCC
 #define ATT_DKV_OCC 2
 #endif
@@ -309,29 +368,20 @@ __global__ __launch_bounds__(256, ATT_DKV_OCC) void attn_bwd_dkv_kernel(const ui
     for (int r = 0; r < 16; ++r) { dk[db][r] = 0.f; dv[db][r] = 0.f; }
 
   const int nt = N / 64;
-#if ATT_DKV_DMA
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);      // Q / dO tiles by LDS-DMA (see attn_fwd_pre_kernel)
   const unsigned qo0 = att_dma_lane_off((int)RS, lane, 0), qo1 = att_dma_lane_off((int)RS, lane, 1);
   const unsigned do0 = att_dma_lane_off((int)OS, lane, 0), do1 = att_dma_lane_off((int)OS, lane, 1);
   float rstat = 0.f;
   att_dma_tile(Qp, RS, 0, smem[0][0], wave_u, qo0, qo1);
   att_dma_tile(dOp, OS, 0, smem[0][1], wave_u, do0, do1);
-#else
-  u32x4 rq[2], rd[2];
-  float rstat = 0.f;
-  att_gload(rq, Qp, RS, 0, t);
-  att_gload(rd, dOp, OS, 0, t);
-#endif
+  unsigned ra[4], ta[2][2];      // this lane's fragment addresses in the stage being read
+  att_ring_addresses(ra, ta, &smem[0][0][0], lane);
   // statistics of the 64 queries of a tile: threads 0-63 fetch lse (kept in the log2 domain), 64-127 delta — through ONE select-addressed load in the
   // straight-line code.  The former `if (t < 64) .. else if (t < 128) ..` put each load in its own divergent block, and the wait-count pass closed
   // that block with s_waitcnt vmcnt(0): every iteration waited for the Q / dO prefetch issued just before it (found in the ISA, round 3).
   const float* statp = ((t & 64) ? delp : lsep) + (t & 63);
   const float stat_mul = (t & 64) ? (CINIT ? -1.0f : 1.0f) : ((CINIT && PRE) ? -1.4426950408889634f : 1.4426950408889634f);   // stored negated where they are C operands
   rstat = statp[0];
-#if !ATT_DKV_DMA
-  att_sstore(rq, smem[0][0], t);
-  att_sstore(rd, smem[0][1], t);
-#endif
   if (t < 128) s_stat[0][t >> 6][t & 63] = rstat * stat_mul;
 #pragma unroll
   for (int ds = 0; ds < 4; ++ds) { att_pin(kf[ds]); att_pin(vf[ds]); }
@@ -340,71 +390,74 @@ __global__ __launch_bounds__(256, ATT_DKV_OCC) void attn_bwd_dkv_kernel(const ui
   for (int qt = 0; qt < nt; ++qt) {
     const int st = qt & 1;
     if (qt + 1 < nt) {
-#if ATT_DKV_DMA
       att_dma_tile(Qp, RS, (qt + 1) * 64, smem[st ^ 1][0], wave_u, qo0, qo1);      // the other stage is free since the barrier that closed tile qt - 1
       att_dma_tile(dOp, OS, (qt + 1) * 64, smem[st ^ 1][1], wave_u, do0, do1);
-#else
-      att_gload(rq, Qp, RS, (qt + 1) * 64, t);
-      att_gload(rd, dOp, OS, (qt + 1) * 64, t);
-#endif
       rstat = statp[(qt + 1) * 64];                 // (scaled when it is stored, after the tile's arithmetic: nothing here waits for the load)
     }
-    const unsigned char* qt_ = smem[st][0];
-    const unsigned char* dot_ = smem[st][1];
+    // The tile's 32 MFMAs take their fragments from a stream of 32 counted reads, requested ATT_PF fragments ahead (see attn_bwd_dq_kernel).  Fragment I:
+    // query block qb = I / 16; j = I % 16 < 8: row fragment ds = j / 2 of Q (j even, -> S) or dO (j odd, -> dP); else transpose fragment
+    // (c2, db) = ((j - 8) / 4, ((j - 8) / 2) % 2) of dO (j even, -> dV) or Q (j odd, -> dK).  The statistics stay plain reads of s_stat, which the LDS-DMA does not write.
+    constexpr int NF = 32;
+    u32x4 fr[ATT_PF + 1];
+    att_u64 tl[ATT_PF + 1], th[ATT_PF + 1];
+    auto req = [&](auto ic) {
+      constexpr int I = decltype(ic)::value, qb = I / 16, j = I % 16, B = I % (ATT_PF + 1);
+      if constexpr (j < 8) att_req_row<(j & 1) * ATT_TILE_BYTES + qb * 32 * 128>(fr[B], ra[j >> 1]);
+      else att_req_tr<((j & 1) ^ 1) * ATT_TILE_BYTES + (qb * 32 + 16 * ((j - 8) >> 2)) * 128>(tl[B], th[B], ta[(j >> 1) & 1][0], ta[(j >> 1) & 1][1]);
+    };
+    f32x16 s, dp, lrow, drow;
+    float pv[16], dsv[16];
+    s16x8 pa, dsa;
+    att_static_for<0, NF>([&](auto ic) {
+      constexpr int I = decltype(ic)::value, qb = I / 16, j = I % 16, B = I % (ATT_PF + 1);
+      att_stream_request<I, NF, 16, true>(req);
+      constexpr int PEND = att_pending(I, NF, 16, true);
+      if constexpr (j == 0) {
 #pragma unroll
-    for (int qb = 0; qb < 2; ++qb) {
-      f32x16 s, dp, lrow;
+        for (int g4 = 0; g4 < 4; ++g4) {           // the statistics of the 16 query rows this lane holds (rows 8 g4 + 4 hi + 0..3 of the block)
+          const int row0 = qb * 32 + 8 * g4 + 4 * hi;
+          const f32x4 l4 = *reinterpret_cast<const f32x4*>(&s_stat[st][0][row0]);
+          const f32x4 d4 = *reinterpret_cast<const f32x4*>(&s_stat[st][1][row0]);
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {           // the statistics of the 16 query rows this lane holds (rows 8 g4 + 4 hi + 0..3 of the block)
-        const int row0 = qb * 32 + 8 * g4 + 4 * hi;
-        const f32x4 l4 = *reinterpret_cast<const f32x4*>(&s_stat[st][0][row0]);
-        const f32x4 d4 = *reinterpret_cast<const f32x4*>(&s_stat[st][1][row0]);
+          for (int k = 0; k < 4; ++k) { lrow[g4 * 4 + k] = l4[k]; dp[g4 * 4 + k] = d4[k]; }
+        }
+        drow = dp;
+        if (!(CINIT && PRE)) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { lrow[g4 * 4 + k] = l4[k]; dp[g4 * 4 + k] = d4[k]; }
-      }
-      const f32x16 drow = dp;
-      if (!(CINIT && PRE)) {
+          for (int r = 0; r < 16; ++r) s[r] = 0.f;
+        } else {
+          s = lrow;                               // -lse (log2 domain) as the C operand
+        }
+        if (!CINIT) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = 0.f;
-      } else {
-        s = lrow;                               // -lse (log2 domain) as the C operand
-      }
-      if (!CINIT) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dp[r] = 0.f;
-      }
-#pragma unroll
-      for (int ds = 0; ds < 4; ++ds) {
-        s = MFMA32(att_frag_row(qt_, qb * 32, ds, l31, hi), kf[ds], s);      // S[q][key]  (- lse[q])
-        dp = MFMA32(att_frag_row(dot_, qb * 32, ds, l31, hi), vf[ds], dp);   // dP[q][key] = dO V^T  (- delta[q])
-      }
-      float pv[16], dsv[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        pv[r] = (CINIT && PRE) ? __builtin_amdgcn_exp2f(s[r]) : __builtin_amdgcn_exp2f(s[r] * scale_log2 - lrow[r]);
-        dsv[r] = CINIT ? pv[r] * dp[r] : pv[r] * (dp[r] - drow[r]);      // the factor of dS is applied once to the finished dK
-      }
-#pragma unroll
-      for (int c2 = 0; c2 < 2; ++c2) {
-        const s16x8 pa = pack8<OT>(&pv[c2 * 8]);
-        const s16x8 dsa = pack8<OT>(&dsv[c2 * 8]);
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-          dv[db] = MFMA32(att_frag_tr(dot_, qb * 32 + 16 * c2, db, lane), pa, dv[db]);  // dV^T[d][key] += dO^T P
-          dk[db] = MFMA32(att_frag_tr(qt_, qb * 32 + 16 * c2, db, lane), dsa, dk[db]);  // dK^T[d][key] += Q^T dS
+          for (int r = 0; r < 16; ++r) dp[r] = 0.f;
         }
       }
-    }
-    if (qt + 1 < nt) {
-#if !ATT_DKV_DMA
-      att_sstore(rq, smem[st ^ 1][0], t);
-      att_sstore(rd, smem[st ^ 1][1], t);
-#endif
-      if (t < 128) s_stat[st ^ 1][t >> 6][t & 63] = rstat * stat_mul;
-    }
-#if ATT_DKV_DMA
-    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): this wave's share of the next tile has landed in LDS
-#endif
+      if constexpr (j < 8) {
+        constexpr int ds = j >> 1;
+        const s16x8 f = att_take_row<PEND>(fr[B]);
+        if constexpr ((j & 1) == 0) s = MFMA32(f, kf[ds], s);      // S[q][key]  (- lse[q])
+        else dp = MFMA32(f, vf[ds], dp);                           // dP[q][key] = dO V^T  (- delta[q])
+        if constexpr (j == 7) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            pv[r] = (CINIT && PRE) ? __builtin_amdgcn_exp2f(s[r]) : __builtin_amdgcn_exp2f(s[r] * scale_log2 - lrow[r]);
+            dsv[r] = CINIT ? pv[r] * dp[r] : pv[r] * (dp[r] - drow[r]);      // the factor of dS is applied once to the finished dK
+          }
+        }
+      } else {
+        constexpr int c2 = (j - 8) >> 2, db = (j >> 1) & 1;
+        if constexpr (((j - 8) & 3) == 0) { pa = pack8<OT>(&pv[c2 * 8]); dsa = pack8<OT>(&dsv[c2 * 8]); }
+        const s16x8 f = att_take_tr<PEND>(tl[B], th[B]);
+        if constexpr ((j & 1) == 0) dv[db] = MFMA32(f, pa, dv[db]);  // dV^T[d][key] += dO^T P
+        else dk[db] = MFMA32(f, dsa, dk[db]);                        // dK^T[d][key] += Q^T dS
+      }
+    });
+    att_ring_advance(ra, ta, st);
+    // ONE wait for everything this wave has asked global memory for — its share of the next tile and the statistic it stores below — behind the tile's last MFMA
+    ATT_FENCE();
+    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0)
+    if (qt + 1 < nt && t < 128) s_stat[st ^ 1][t >> 6][t & 63] = rstat * stat_mul;
     __syncthreads();
   }
   if (!active) return;

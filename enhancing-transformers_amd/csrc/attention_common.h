@@ -1,6 +1,7 @@
 // attention_common.h — helpers shared by the attention kernels (attention.hip: round-1/2 kernels; attention_v2.hip: the software-pipelined round-3 kernels):
 // the swizzled LDS image of a [64][64] bf16 tile, register staging, MFMA operand fragments (row and transpose-read) and the workgroup -> (block, head) map.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 #define ATT_D 64
@@ -38,6 +39,11 @@ __device__ __forceinline__ unsigned att_dma_lane_off(int rs_elems, int lane, int
 }
 __device__ __forceinline__ void att_dma_tile(const uint16_t* __restrict__ base, int64_t rs, int row0, unsigned char* tile, int wave, unsigned lane_off0, unsigned lane_off1) {
   const unsigned char* ub = reinterpret_cast<const unsigned char*>(base + (int64_t)(row0 + wave * 16) * rs);
+  // the lane offsets are made opaque HERE: their widening to 64 bits then happens next to the request, which lets instruction selection take the
+  // scalar-base + 32-bit-vector-offset form of the instruction.  Hoisted out of the tile loop (what the optimizer does with a loop-invariant
+  // widening) every offset occupies a register PAIR for the whole kernel and every request costs a 64-bit vector add into a third pair.
+  asm volatile("" : "+v"(lane_off0));
+  asm volatile("" : "+v"(lane_off1));
   __builtin_amdgcn_global_load_lds((const GLB_AS void*)(ub + lane_off0), (LDS_AS void*)(tile + (wave * 16) * 128), 16, 0, 0);
   __builtin_amdgcn_global_load_lds((const GLB_AS void*)(ub + (size_t)(unsigned)(8 * (int)rs * 2) + lane_off1), (LDS_AS void*)(tile + (wave * 16 + 8) * 128), 16, 0, 0);
 }
@@ -60,6 +66,69 @@ __device__ __forceinline__ s16x8 att_frag_tr(const unsigned char* tile, int rbas
   o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
   return o;
 }
+// ---- fragment reads the kernel counts itself (the LDS-DMA kernels of attention.hip) ---------------------------------------------------------------
+// The compiler's wait-count pass cannot separate a read of the tile ring from the global_load_lds that fills the ring's OTHER stage, and puts
+// s_waitcnt vmcnt(0) in front of the first such read of a tile: the prefetch is drained where it was meant to run under the tile's MFMAs (common.h,
+// lds_tr_read_b64_asm).  These reads are inline asm, which that pass does not see; the kernel owns their ordering:
+//   * a stage is read only behind the vmcnt(0) AND the barrier that close the tile before it, and every read of a tile is taken (waited for) by the
+//     MFMA that consumes it, i.e. before the barrier that lets the next request overwrite the stage;
+//   * att_take_* is the wait: s_waitcnt lgkmcnt(PEND) with the fragment's registers as read-write operands, so the consuming MFMA depends on the
+//     wait through its operand and cannot be scheduled above it (cdna_hip_programming.md §5.7 item 1, form ii), while the vector arithmetic
+//     between the MFMAs stays free to move.  LDS operations complete in order: PEND = the LDS operations the kernel itself issued behind the
+//     fragment's own.  Operations the compiler adds in between (the statistics of dK/dV) only make the wait stricter; no scalar load runs in the loops.
+// tools/isa_lint.py attention_pipeline() checks on the shipped library that no instruction touches a fragment's registers between request and wait.
+typedef unsigned long long att_u64;
+__device__ __forceinline__ unsigned att_lds_addr(const void* p) { return (unsigned)(uintptr_t)(LDS_AS const void*)p; }
+// per-lane byte offsets of the two fragment kinds inside a tile image (the tile-row block and the operand are added as immediates, the stage by att_ring_advance):
+// row fragment ds (att_frag_row with rb = 0) and the two halves of transpose fragment cb (att_frag_tr with rbase = 0)
+__device__ __forceinline__ unsigned att_row_lane_off(int ds, int l31, int hi) { return (unsigned)att_off(l31, ds * 2 + hi); }
+__device__ __forceinline__ unsigned att_tr_lane_off(int cb, int lane, int half) {
+  const int G = lane >> 4, s = lane & 15;
+  return (unsigned)(att_off(4 * (G >> 1) + (s >> 2) + 8 * half, cb * 4 + (G & 1) * 2 + ((s & 3) >> 1)) + (s & 1) * 8);
+}
+// a lane's eight fragment addresses (row fragments ds = 0..3, transpose fragments cb = 0 | 1 x lower | upper half) in stage 0 of a ring of two-tile
+// stages ([stage][operand][ATT_TILE_BYTES]), and their move to the other stage behind a tile read from stage st
+__device__ __forceinline__ void att_ring_addresses(unsigned (&ra)[4], unsigned (&ta)[2][2], const void* ring, int lane) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) ra[i] = att_lds_addr(ring) + att_row_lane_off(i, lane & 31, lane >> 5);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) ta[i >> 1][i & 1] = att_lds_addr(ring) + att_tr_lane_off(i >> 1, lane, i & 1);
+}
+__device__ __forceinline__ void att_ring_advance(unsigned (&ra)[4], unsigned (&ta)[2][2], int st) {
+  const unsigned adv = st ? 0u - 2u * ATT_TILE_BYTES : 2u * ATT_TILE_BYTES;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { ra[i] += adv; ta[i >> 1][i & 1] += adv; }
+}
+template <int OFF>
+__device__ __forceinline__ void att_req_row(u32x4& f, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f) : "v"(addr), "i"(OFF) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void att_req_tr(att_u64& lo, att_u64& hi, unsigned addr_lo, unsigned addr_hi) {
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(addr_lo), "i"(OFF) : "memory");
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(addr_hi), "i"(OFF) : "memory");
+}
+template <int PEND>
+__device__ __forceinline__ s16x8 att_take_row(u32x4& f) {
+  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(f) : "i"(PEND) : "memory");
+  return __builtin_bit_cast(s16x8, f);
+}
+template <int PEND>
+__device__ __forceinline__ s16x8 att_take_tr(att_u64& lo, att_u64& hi) {
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(lo), "+v"(hi) : "i"(PEND) : "memory");
+  typedef __attribute__((ext_vector_type(2))) att_u64 u64x2;
+  const u64x2 o = {lo, hi};
+  return __builtin_bit_cast(s16x8, o);
+}
+// f(integral_constant<int, B>) .. f(integral_constant<int, E - 1>): a loop whose index is a constant expression (immediate offsets, wait counts)
+template <int B, int E, typename F>
+__device__ __forceinline__ void att_static_for(F&& f) {
+  if constexpr (B < E) {
+    f(std::integral_constant<int, B>{});
+    att_static_for<B + 1, E>(f);
+  }
+}
+
 template <typename OT>
 __device__ __forceinline__ s16x8 pack8(const float* p) {
   u32x4 u = {pack2<OT>(p[0], p[1]), pack2<OT>(p[2], p[3]), pack2<OT>(p[4], p[5]), pack2<OT>(p[6], p[7])};

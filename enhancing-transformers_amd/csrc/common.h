@@ -144,7 +144,10 @@ __device__ inline s16x4 lds_tr_read_b64(const void* lds_ptr) {
 // reader of in-flight LDS-DMA data and inserts s_waitcnt vmcnt(0) in front of it, which destroys the load pipeline of
 // kernels that keep global_load_lds in flight across their fragment reads.  With the asm form nothing is inserted: the
 // caller must (a) have waited (vmcnt + barrier) for the data this read needs and (b) wait lgkmcnt before using the result
-// (cdna_hip_programming.md §5.7 item 1) — the t256 GEMM schedule does both explicitly.
+// (cdna_hip_programming.md §5.7 item 1) — the t256 GEMM schedule does both explicitly.  The same holds for PLAIN reads (ds_read_b128) of an array an
+// LDS-DMA request writes: the pass cannot tell the stage being read from the stage being filled.  The attention kernels (attention.hip: forward, dQ,
+// dK/dV — two-stage K / V and Q / dO rings filled by LDS-DMA) therefore read their fragments through the counted asm reads of attention_common.h
+// (att_req_row / att_req_tr, with the offset as an immediate, and att_take_* as the wait).
 __device__ inline void lds_tr_read_b64_asm(unsigned long long& out, const void* lds_ptr) {
   const unsigned addr = (unsigned)(uintptr_t)(LDS_AS const void*)lds_ptr;
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(out) : "v"(addr) : "memory");

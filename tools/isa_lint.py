@@ -4,6 +4,7 @@ do not touch scratch).  Runs on CPU (llvm-objdump / llvm-readelf of the ROCm too
 
     python tools/isa_lint.py [path/to/libenh_hip.so]      # prints the table
     python tools/isa_lint.py --diff OLD.so NEW.so         # per kernel symbol: same, or the first differing instruction; exit 1 on any difference
+    python tools/isa_lint.py --attention [lib.so]         # the tile loops of the attention kernels: waits, exposed fragment reads, fragment registers
 """
 import collections
 import os
@@ -106,6 +107,104 @@ def kernel_instructions(so_path=DEFAULT_SO):
     return out
 
 
+def kernel_listings(so_path=DEFAULT_SO, match="attn_"):
+    """{demangled kernel name: [(address, instruction text, branch target address | None)]} for the functions whose mangled name contains `match`"""
+    out = {}
+    with tempfile.TemporaryDirectory() as wd:
+        for o in code_objects(so_path, wd):
+            dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--mcpu=gfx950", o], capture_output=True, text=True, check=True).stdout
+            cur, start = None, 0
+            for line in dis.splitlines():
+                m = re.match(r"^([0-9a-f]+) <(.+)>:", line)
+                if m:
+                    start = int(m.group(1), 16)
+                    cur = out.setdefault(m.group(2), []) if match in m.group(2) else None
+                    continue
+                if cur is None or not line.startswith("\t") or "//" not in line:
+                    continue
+                text, rest = line.split("//", 1)
+                ins = " ".join(text.split())
+                addr = int(rest.split(":")[0], 16)
+                tgt = None
+                if ins.startswith(("s_cbranch", "s_branch")):
+                    mm = re.search(r"<.+\+0x([0-9a-f]+)>\s*$", rest)
+                    tgt = start + int(mm.group(1), 16) if mm else start
+                cur.append((addr, ins, tgt))
+    dm = _demangle(list(out))
+    return {dm[n]: v for n, v in out.items()}
+
+
+def _vregs(operand_text):
+    regs = set()
+    for a, b in re.findall(r"\bv\[(\d+):(\d+)\]", operand_text):
+        regs.update(range(int(a), int(b) + 1))
+    regs.update(int(a) for a in re.findall(r"\bv(\d+)\b", operand_text))
+    return regs
+
+
+def attention_pipeline(listing):
+    """Facts about the TILE LOOP of one attention kernel (a listing of kernel_listings): the span from the lowest target of a backward branch to the
+    last backward branch.
+      mfma            MFMAs in the loop
+      vm_waits        indices (into the loop) of the s_waitcnt that name vmcnt
+      closing_ok      True if behind the LAST of them, in layout order and on through the back edge, an s_barrier comes before any MFMA
+      exposed         MFMAs whose operand read was issued after the previous MFMA and awaited at once: between the previous MFMA (or the loop's
+                      start) and this one there is a ds_read* and, behind it, an s_waitcnt with lgkmcnt(0)
+      touched         (index, instruction) of every instruction that names a register an LDS read has been asked to write while that read may still
+                      be in flight (LDS operations complete in order; s_waitcnt lgkmcnt(n) leaves the last n in flight).  The asm-issued fragment
+                      reads of attention_common.h are invisible to the compiler's own bookkeeping: this is the check that it did not copy, reuse
+                      or read such a register between request and wait.
+      carried         LDS reads still in flight at a branch or branch target inside the loop (the scan is linear: these are not followed)
+      scalar_loads    s_load* / s_buffer_load* in the loop (they share lgkmcnt and complete out of order: the counted waits assume there are none)"""
+    back = [(a, t) for a, ins, t in listing if t is not None and t <= a]
+    assert back, "no loop"
+    lo, hi = min(t for _, t in back), max(a for a, _ in back)
+    loop = [(a, ins, t) for a, ins, t in listing if lo <= a <= hi]
+    targets = {t for _, _, t in listing if t is not None}
+    res = {"mfma": 0, "vm_waits": [], "closing_ok": False, "exposed": 0, "touched": [], "carried": 0, "scalar_loads": 0}
+    since_read, since_wait0 = False, False      # since the previous MFMA: a ds_read seen; behind it an lgkmcnt(0) wait seen
+    fifo = []                                    # destination registers of the LDS operations in flight, oldest first (empty set: a write)
+    for i, (a, ins, t) in enumerate(loop):
+        op = ins.split()[0]
+        if a in targets or t is not None:
+            res["carried"] += sum(1 for d in fifo if d)
+            fifo = []
+        if op.startswith(("s_load", "s_buffer_load")):
+            res["scalar_loads"] += 1
+        if op == "s_waitcnt":
+            if "vmcnt" in ins:
+                res["vm_waits"].append(i)
+            m = re.search(r"lgkmcnt\((\d+)\)", ins)
+            if m:
+                n = int(m.group(1))
+                fifo = fifo[len(fifo) - n:] if n else []
+                if n == 0 and since_read:
+                    since_wait0 = True
+            continue
+        operands = ins[len(op):]
+        used = _vregs(operands)
+        for d in fifo:
+            if d & used:
+                res["touched"].append((i, ins))
+                break
+        if op.startswith("ds_"):
+            fifo.append(_vregs(operands.split(",")[0]) if op.startswith("ds_read") else set())
+            if op.startswith("ds_read"):
+                since_read, since_wait0 = True, False
+        if op.startswith("v_mfma"):
+            res["mfma"] += 1
+            res["exposed"] += since_wait0
+            since_read, since_wait0 = False, False
+    if res["vm_waits"]:
+        w = res["vm_waits"][-1]
+        for a, ins, t in loop[w + 1:] + loop[:w]:      # (the loop's last instruction branches to its first)
+            if ins.startswith("s_barrier"):
+                res["closing_ok"] = True
+            if ins.startswith(("s_barrier", "v_mfma")):
+                break
+    return res
+
+
 def diff_instructions(old, new):
     """compare two {symbol: [instruction text]} dictionaries: {symbol: "same" | "only in old" | "only in new" | (index, old instruction, new instruction)}
     with the first difference (None for the side that has ended)"""
@@ -148,6 +247,13 @@ def main():
         if len(sys.argv) != 4:
             sys.exit("usage: isa_lint.py --diff OLD.so NEW.so")
         return diff_main(sys.argv[2], sys.argv[3])
+    if len(sys.argv) > 1 and sys.argv[1] == "--attention":
+        for name, listing in sorted(kernel_listings(sys.argv[2] if len(sys.argv) > 2 else DEFAULT_SO).items()):
+            if "_kernel" in name:
+                r = attention_pipeline(listing)
+                print(f"{name.split('(')[0]:60s} mfma {r['mfma']:3d} exposed {r['exposed']:3d} vmcnt waits {len(r['vm_waits'])} closing_ok {r['closing_ok']} "
+                      f"touched {len(r['touched'])} carried {r['carried']} scalar loads {r['scalar_loads']}")
+        return 0
     so = sys.argv[1] if len(sys.argv) > 1 else DEFAULT_SO
     st = kernel_stats(so)
     print(f"{len(st)} kernels in {so}")
