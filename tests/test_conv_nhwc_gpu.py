@@ -3,12 +3,13 @@ weight-grad switch for R1"): every kernel of enhancing/losses/op/conv_nhwc.py ag
 enhancing/losses/vqperceptual.py).
 
 Tolerances: 16-bit outputs must sit at the rounding floor of the exact result in their format (<= 1.25x the floor computed in the test); the f32 weight
-gradient (exact 16-bit products, f32 accumulation over up to ~1e5 pixels, fixed summation order) within 2e-5; pure data movement bit-exact."""
+gradient (exact 16-bit products, f32 accumulation over up to ~1e5 pixels, fixed summation order) within 2e-5; pure data movement bit-exact.  The
+forward / input-gradient / weight-gradient test also holds EVERY element to util.elem_bound against fp64 (border pixels, channel-padding edges)."""
 import pytest
 import torch
 import torch.nn.functional as F
 
-from util import floor16, h16r, rel
+from util import assert_elementwise, elem_bound, floor16, h16r, rel
 
 pytestmark = pytest.mark.gpu
 
@@ -118,10 +119,14 @@ def _conv_forward_dgrad_wgrad(ops, family, B, H, W, Cin, Cout, k, s, p, dt):
     w = torch.randn(Cout, Cin, k, k, generator=g)
     scale = 1.0 / (Cin * k * k) ** 0.5
     ws = h16r(w * scale, dt)                                # what the pack kernel hands to the MFMA
-    xr, wr = x.clone().requires_grad_(True), ws.clone().requires_grad_(True)
+    xr, wr = x.double().requires_grad_(True), ws.double().requires_grad_(True)      # the reference and its autograd in fp64
     yr = F.conv2d(xr, wr, stride=s, padding=p)
     dy = h16r(torch.randn(yr.shape, generator=g), dt)
-    yr.backward(dy)
+    yr.backward(dy.double())
+    # the same three contractions on absolute values: the magnitudes of util.elem_bound
+    xa, wa = x.double().abs().requires_grad_(True), ws.double().abs().requires_grad_(True)
+    ya = F.conv2d(xa, wa, stride=s, padding=p)
+    ya.backward(dy.double().abs())
     xp = torch.zeros(B, H, W, Cp)
     xp[..., :Cin] = _nhwc(x)
     xd = xp.to(dt).cuda().requires_grad_(True)
@@ -136,6 +141,13 @@ def _conv_forward_dgrad_wgrad(ops, family, B, H, W, Cin, Cout, k, s, p, dt):
     e_w = rel(wd.grad, scale * wr.grad)
     print(f"conv {dt} {B}x{H}x{W} {Cin}->{Cout} k{k} s{s} p{p}: y {e_y:.2e} (floor {f_y:.2e})  dx {e_x:.2e} (floor {f_x:.2e})  dw {e_w:.2e}")
     assert e_y <= 1.25 * f_y and e_x <= 1.25 * f_x and e_w <= 2e-5
+    # every element (every border pixel, every channel-padding edge): one 16-bit rounding of an f32 sum of Cin k^2 (y) / at most Cout k^2 (dx) products;
+    # dw an f32 sum over the B Ho Wo output pixels, whatever its slabs
+    what = f"conv {family} {dt} {B}x{H}x{W} {Cin}->{Cout} k{k} s{s} p{p}"
+    w_y = assert_elementwise(_nchw(y.float()), yr.detach(), elem_bound(yr.detach(), ya.detach(), Cin * k * k, dt), what + " y")
+    w_x = assert_elementwise(gx[:, :Cin], xr.grad, elem_bound(xr.grad, xa.grad, Cout * k * k, dt), what + " dx")
+    w_w = assert_elementwise(wd.grad, scale * wr.grad, elem_bound(scale * wr.grad, scale * wa.grad, B * yr.shape[2] * yr.shape[3]), what + " dw")
+    print(f"  max err / element bound: y {w_y:.3f}  dx {w_x:.3f}  dw {w_w:.4f}")
     if Cp > Cin:
         assert not gx[:, Cin:].abs().sum().item()           # gradient of the zero padding channels: zero rows of the transposed weights
 
