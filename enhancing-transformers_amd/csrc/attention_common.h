@@ -1,4 +1,4 @@
-// attention_common.h — helpers shared by the attention kernels (attention.hip: round-1/2 kernels; attention_v2.hip: the software-pipelined round-3 kernels):
+// attention_common.h — helpers shared by the attention kernels (attention.hip / attention_kernels.h; x3.hip / x3_attention.h):
 // the swizzled LDS image of a [64][64] bf16 tile, register staging, MFMA operand fragments (row and transpose-read) and the workgroup -> (block, head) map.
 #pragma once
 #include <type_traits>
@@ -47,6 +47,37 @@ __device__ __forceinline__ void att_dma_tile(const uint16_t* __restrict__ base, 
   __builtin_amdgcn_global_load_lds((const GLB_AS void*)(ub + lane_off0), (LDS_AS void*)(tile + (wave * 16) * 128), 16, 0, 0);
   __builtin_amdgcn_global_load_lds((const GLB_AS void*)(ub + (size_t)(unsigned)(8 * (int)rs * 2) + lane_off1), (LDS_AS void*)(tile + (wave * 16 + 8) * 128), 16, 0, 0);
 }
+// ---- the ragged last tile of an image (token counts that are no multiple of 64: the *_tail_* kernels) ------------------------------------------------
+// Rows row0 .. n_rows - 1 of the tile exist.  Every source row is clamped to the image's last row: nothing outside the tensor (or inside the next
+// image) is read, and the rows of the LDS image past the end hold finite values (their probabilities are exactly 0, and 0 x NaN would be NaN).
+// The lane offsets of att_dma_tile are tile-invariant; this tile computes its own (once per workgroup pass, outside the counted reads).
+__device__ __forceinline__ void att_gload_clamped(u32x4 (&r)[2], const uint16_t* __restrict__ base, int64_t rs, int row0, int n_rows, int t) {
+  const int c = t & 7, r0 = t >> 3;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) r[i] = *reinterpret_cast<const u32x4*>(base + (int64_t)min(row0 + r0 + 32 * i, n_rows - 1) * rs + c * 8);
+}
+__device__ __forceinline__ void att_dma_tile_clamped(const uint16_t* __restrict__ base, int64_t rs, int row0, int n_rows, unsigned char* tile, int wave, int lane) {
+  // (opaque: this tile's address arithmetic stays where the tile is requested.  It is invariant in the tile loop, and hoisted out of it it holds
+  // registers for the whole kernel — the forward went from 126 to 194 that way)
+  asm volatile("" : "+s"(n_rows));
+  const int wrow = min(row0 + wave * 16, n_rows - 1);      // wave-uniform: the scalar base stays inside the image, the lane offsets stay non-negative
+  const int lim = n_rows - 1 - wrow;
+  const unsigned char* ub = reinterpret_cast<const unsigned char*>(base + (int64_t)wrow * rs);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int rr = lane >> 3, p = lane & 7, r = rr + 8 * i;
+    const int c = p ^ ((((r >> 1) & 1) << 2) | ((r >> 2) & 3));      // the swizzle follows the DESTINATION row (att_dma_lane_off)
+    unsigned off = (unsigned)(min(r, lim) * (int)rs + c * 8) * 2u;
+    asm volatile("" : "+v"(off));      // (scalar base + 32-bit vector offset, as att_dma_tile)
+    __builtin_amdgcn_global_load_lds((const GLB_AS void*)(ub + off), (LDS_AS void*)(tile + (wave * 16 + 8 * i) * 128), 16, 0, 0);
+  }
+}
+// what a key row past the end adds to its log2-domain score (through the MFMA C operand): large, negative and FINITE (the attention objects are built
+// with -fno-honor-nans; no infinity is relied on).  exp2 of it is exactly 0, and it never reaches the row maximum: every tile holds a valid key.
+#define ATT_MASK_BIAS (-1.0e30f)
+// accumulator register r of key block kb of a 64-key tile is key kb*32 + 8*(r>>2) + 4*hi + (r&3)
+__device__ __forceinline__ float att_key_bias(int kb, int r, int hi, int n_keys) { return kb * 32 + 8 * (r >> 2) + 4 * hi + (r & 3) < n_keys ? 0.f : ATT_MASK_BIAS; }
+
 // 32x32x16 operand fragment, rows = tile rows rb + (lane&31), k = d: ds*16 + hi*8 + 0..7
 __device__ __forceinline__ s16x8 att_frag_row(const unsigned char* tile, int rb, int ds, int l31, int hi) {
   return *reinterpret_cast<const s16x8*>(tile + att_off(rb + l31, ds * 2 + hi));
@@ -181,122 +212,12 @@ __device__ __forceinline__ bool att_block_coords(int nblk, int n_heads_total, in
   return head < n_heads_total;
 }
 
-
-// The round-1/2 forward pass of one 128-query block (exact running maximum, O rescaled every tile): the body of attn_fwd_kernel, and the FALLBACK of the
-// pipelined kernel of attention_v2.hip for a workgroup whose scores outgrow its fixed reference.  smem: [2][2][ATT_TILE_BYTES] ([stage][K | V]).
-template <typename OT>
-__device__ __forceinline__ void attn_fwd_exact(const uint16_t* __restrict__ qkv, int B, int N, int H, float scale_log2, uint16_t* __restrict__ out,
-                                               float* __restrict__ lse, unsigned char (*smem)[2][ATT_TILE_BYTES], int blk, int head) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int l31 = lane & 31, hi = lane >> 5;
-  const int b = head / H, h = head - b * H;
-  const int q0 = blk * 128 + wave * 32;
-  const int64_t RS = (int64_t)3 * H * ATT_D;
-  const uint16_t* Qp = qkv + (int64_t)b * N * RS + h * ATT_D;
-  const uint16_t* Kp = Qp + H * ATT_D;
-  const uint16_t* Vp = Kp + H * ATT_D;
-
-  const bool active = q0 < N;  // N % 64 == 0: a wave's 32 queries are all in or all out
-  const int qrow = active ? q0 + l31 : l31;
-  s16x8 qf[4];
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds) qf[ds] = *reinterpret_cast<const s16x8*>(Qp + (int64_t)qrow * RS + ds * 16 + hi * 8);
-
-  f32x16 o[2];
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
-  float m_run = -__builtin_inff(), l_part = 0.f;
-
-  const int nt = N / 64;
-  u32x4 rk[2], rv[2];
-  att_gload(rk, Kp, RS, 0, t);
-  att_gload(rv, Vp, RS, 0, t);
-  att_sstore(rk, smem[0][0], t);
-  att_sstore(rv, smem[0][1], t);
-#pragma unroll
-  for (int ds = 0; ds < 4; ++ds) att_pin(qf[ds]);
-  ATT_LOOP_ENTRY();
-  __syncthreads();
-  for (int kt = 0; kt < nt; ++kt) {
-    const int st = kt & 1;
-    if (kt + 1 < nt) {
-      att_gload(rk, Kp, RS, (kt + 1) * 64, t);
-      att_gload(rv, Vp, RS, (kt + 1) * 64, t);
-    }
-    const unsigned char* kt_ = smem[st][0];
-    const unsigned char* vt_ = smem[st][1];
-    // ---- S^T[key][q] = K Q^T ----
-    f32x16 s[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
-#pragma unroll
-      for (int ds = 0; ds < 4; ++ds) s[kb] = MFMA32(att_frag_row(kt_, kb * 32, ds, l31, hi), qf[ds], s[kb]);
-    }
-    // ---- online softmax for this lane's query column ----
-    // Round 4 (the kernel runs at the speed of its VECTOR instruction stream, profiles/r04_attention_lab.txt): the row maximum through v_max3 (16
-    // instructions instead of 32 v_max + canonicalisations) and one v_permlane32_swap instead of an LDS round trip; and the running maximum is a
-    // REFERENCE that is raised — O and l rescaled, a wave-uniform branch — only on the first tile and when some row's tile maximum exceeds it by more
-    // than 2^8: the 32 multiplies of O per tile are gone in all but a handful of tiles (numerators stay below 2^8; bf16's relative precision does not
-    // depend on that scale, lse = m + log2(l) is exact either way; cdna_hip_programming.md T13: no product is pending across the rescale here).
-    float mx = max3(s[0][0], s[0][1], s[0][2]);
-#pragma unroll
-    for (int r = 3; r < 15; r += 2) mx = max3(mx, s[0][r], s[0][r + 1]);
-    mx = max3(mx, s[0][15], s[1][0]);
-#pragma unroll
-    for (int r = 1; r < 15; r += 2) mx = max3(mx, s[1][r], s[1][r + 1]);
-    mx = xhalf_max(__builtin_fmaxf(mx, s[1][15]));
-    const float mt = mx * scale_log2;
-    if (kt == 0 || __builtin_amdgcn_ballot_w64(mt - m_run > 8.0f) != 0) {
-      const float m_new = fmaxf(m_run, mt);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-      m_run = m_new;
-      l_part *= alpha;
-#pragma unroll
-      for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-    }
-    float p[2][16];
-    float psum = 0.f;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        p[kb][r] = __builtin_amdgcn_exp2f(s[kb][r] * scale_log2 - m_run);
-        psum += p[kb][r];
-      }
-    l_part += psum;
-    // ---- O^T[d][q] += V^T P^T ----
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-      for (int c2 = 0; c2 < 2; ++c2) {
-        const s16x8 pb = pack8<OT>(&p[kb][c2 * 8]);
-#pragma unroll
-        for (int db = 0; db < 2; ++db) o[db] = MFMA32(att_frag_tr(vt_, kb * 32 + 16 * c2, db, lane), pb, o[db]);
-      }
-    if (kt + 1 < nt) {
-      att_sstore(rk, smem[st ^ 1][0], t);
-      att_sstore(rv, smem[st ^ 1][1], t);
-    }
-    __syncthreads();
-  }
-  const float l = l_part + __shfl_xor(l_part, 32, 64);
-  const float inv = 1.0f / l;
-  if (!active) return;
-  uint16_t* op = out + ((int64_t)b * N + q0 + l31) * (H * ATT_D) + h * ATT_D;
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int g4 = 0; g4 < 4; ++g4) {
-      const int d0 = db * 32 + 8 * g4 + 4 * hi;
-      u32x2 w = {pack2<OT>(o[db][g4 * 4 + 0] * inv, o[db][g4 * 4 + 1] * inv), pack2<OT>(o[db][g4 * 4 + 2] * inv, o[db][g4 * 4 + 3] * inv)};
-      *reinterpret_cast<u32x2*>(op + d0) = w;
-    }
-  if (hi == 0) lse[((int64_t)b * H + h) * N + q0 + l31] = (m_run + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;
-}
-
+// ---- host side ------------------------------------------------------------------------------------------------------------------------------------
+#define ATT_LOG2E 1.4426950408889634f
+#define ATT_LN2 0.6931471805599453f
+// the tail forms' launches (attention_tail.hip, x3_tail.hip), behind the argument checks of the C ABI functions that call them for N % 64 != 0
+int enh_attention_tail_forward(const enh_h16* qkv, int B, int N, int H, float scale, int q_prescaled, enh_h16* out, float* lse, int dtype, void* stream);
+int enh_attention_tail_backward(const enh_h16* qkv, const enh_h16* out, const enh_h16* dout, const float* lse, int B, int N, int H, float scale, int q_prescaled,
+                                enh_h16* dqkv, float* delta_ws, int dtype, void* stream);
+int enh_attention_tail_forward_x3(const enh_bf16* qkv_hi, const enh_bf16* qkv_lo, int B, int N, int H, float scale, enh_bf16* out3, enh_bf16* out_bf16, float* lse,
+                                  void* stream);

@@ -482,9 +482,13 @@ def attention_set_kernel(fwd: int = 0, dq: int = 0, dkv: int = 0) -> None:
 
 def attention_forward(qkv, B: int, N: int, H: int, scale: float, out, lse, q_prescaled: bool = False):
     """q_prescaled: the q third of qkv holds q * scale * log2(e) (include/enh_hip.h)"""
-    # (labelled with the symbol rocprofv3 reports: family 5 — the default — serves pre-scaled q, family 1 everything else)
+    # (labelled with the symbol rocprofv3 reports: family 5 — the default — serves pre-scaled q, family 1 everything else; a token count that is no
+    # multiple of 64 runs the tail form of its q convention whatever family is selected)
     fam = _ATT_FAMILY[0] or 5
-    name = "attn_fwd_pre_kernel" if (fam == 5 and q_prescaled) else "attn_fwd_kernel"
+    if N % 64:
+        name = "attn_fwd_tail_pre_kernel" if q_prescaled else "attn_fwd_tail_kernel"
+    else:
+        name = "attn_fwd_pre_kernel" if (fam == 5 and q_prescaled) else "attn_fwd_kernel"
     dt = _dt(qkv, out)
     _timed(f"{name}<{_OT_NAME[dt]}>", 4.0 * B * H * N * N * 64,
            lambda: _check(lib().enh_attention_forward(_p(qkv, H16, "qkv"), B, N, H, scale, int(q_prescaled), _p(out, H16, "out"), _p(lse, F32, "lse"),
@@ -493,7 +497,7 @@ def attention_forward(qkv, B: int, N: int, H: int, scale: float, out, lse, q_pre
 
 def attention_backward(qkv, out, dout, lse, B: int, N: int, H: int, scale: float, dqkv, delta_ws, q_prescaled: bool = False):
     dt = _dt(qkv, out, dout, dqkv)
-    _timed("attn_bwd (dq+dkv kernels)", 10.0 * B * H * N * N * 64,
+    _timed("attn_bwd_tail (dq+dkv kernels)" if N % 64 else "attn_bwd (dq+dkv kernels)", 10.0 * B * H * N * N * 64,
            lambda: _check(lib().enh_attention_backward(_p(qkv, H16, "qkv"), _p(out, H16, "out"), _p(dout, H16, "dout"), _p(lse, F32, "lse"), B, N, H,
                                                        scale, int(q_prescaled), _p(dqkv, H16, "dqkv"), _p(delta_ws, F32, "delta_ws"), dt, _stream()),
                           "enh_attention_backward"))
@@ -868,7 +872,7 @@ def ln_fwd_x3(x, w, b, y3, mean, rstd, y_bf16=None, y_f32=None):
 
 def attention_forward_x3(qkv_hi, qkv_lo, B: int, N: int, H: int, scale: float, out3, out_bf16, lse):
     # executed MFMA work: three passes of the 4 N^2 64 algorithmic FLOP per (image, head)
-    _timed("attn_fwd_x3_kernel", 3 * 4.0 * B * H * N * N * 64,
+    _timed("attn_fwd_tail_x3_kernel" if N % 64 else "attn_fwd_x3_kernel", 3 * 4.0 * B * H * N * N * 64,
            lambda: _check(lib().enh_attention_forward_x3(_p(qkv_hi, BF16, "qkv_hi"), _p(qkv_lo, BF16, "qkv_lo"), B, N, H, scale, _p(out3, BF16, "out3"),
                                                          _p(out_bf16, BF16, "out_bf16"), _p(lse, F32, "lse"), _stream()), "enh_attention_forward_x3"))
 

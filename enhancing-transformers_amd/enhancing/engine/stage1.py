@@ -15,6 +15,7 @@ PyTorch is used for device memory, streams and ``torch.distributed`` only.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -643,10 +644,19 @@ class Stage1Engine:
         return io["xrec"].clone()
 
     # ---- training: forward (activations saved) / backward, used fused by training_step and split by autograd -----
+    def _check_train_rows(self, B: int) -> None:
+        """The weight gradients contract over the B * N token rows, and the 16-bit GEMM takes K % 8 == 0 only.  Any token count N runs (image_size /
+        patch_size need not give a multiple of 64, or of 8), so the rule falls on the batch: checked here, before the first launch of a training
+        forward, instead of surfacing as a GEMM error halfway through the backward.  Inference takes any B."""
+        if self.half and (B * self.n_tok) % 8 != 0:
+            raise ValueError(f"training needs B * N % 8 == 0 (the weight-gradient GEMMs contract over the B * N token rows in groups of 8): got B = {B}, "
+                             f"N = {self.n_tok} tokens per image, B * N = {B * self.n_tok}; use a batch size that is a multiple of {8 // math.gcd(8, self.n_tok)}")
+
     def encode_train(self, img: torch.Tensor) -> dict:
         """first half of forward_train: encoder + pre_quant with the activations saved -> state dict with h (quantizer input, f32 [M, embed_dim])"""
         img = self._check_img(img)
         B = img.shape[0]
+        self._check_train_rows(B)
         eb = self._encode_tokens(img, save=True, x3=self.encoder_precision == "x3")
         h = self._pre_quant(eb, B)
         self._fwd_serial = getattr(self, "_fwd_serial", 0) + 1
@@ -655,6 +665,7 @@ class Stage1Engine:
     def decode_train(self, st: dict, zq16: torch.Tensor, zq32: Optional[torch.Tensor] = None) -> dict:
         """second half: post_quant + decoder + to_pixel from the quantized tokens [M, embed_dim] (operand dtype of this precision mode), saved; zq32: the same
         tokens in f32 for the x3 decoder (decoder_precision)"""
+        self._check_train_rows(st["B"])
         st.update(zq16=zq16, pix=self._decode_tokens(zq16, st["B"], save=True, zq32=zq32 if self.decoder_precision == "x3" else None))
         return st
 

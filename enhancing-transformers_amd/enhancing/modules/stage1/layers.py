@@ -88,7 +88,8 @@ class PatchConvParams(nn.Module):
 
 
 class Attention(nn.Module):
-    """bias-free to_qkv [3*inner, dim], to_out [dim, inner] + bias; inner = heads * 64 (layers.py:108-120)."""
+    """bias-free to_qkv [3*inner, dim], to_out [dim, inner] + bias; inner = heads * 64 (layers.py:108-120).  The fused kernels take any number of tokens
+    (a multiple of 64 runs the aligned kernels, anything else their tail forms: include/enh_hip.h); only dim_head is fixed."""
 
     def __init__(self, dim: int, heads: int = 8, dim_head: int = 64) -> None:
         super().__init__()
@@ -132,6 +133,10 @@ def _pair(v) -> Tuple[int, int]:
 
 
 class _ViTBase(nn.Module):
+    """image_size: any multiple of patch_size (square; patch_size % 4 == 0 for the patch kernels).  The token count N = (image_size / patch_size)^2 is
+    free — 224 / 16 (196), 224 / 8 (784), 160 / 8 (400), 96 / 8 (144) run like 256 / 8 (1024).  Training needs B * N % 8 == 0 (the weight-gradient
+    GEMMs contract over the token rows; Stage1Engine raises a ValueError otherwise: N = 196 takes an even batch); inference takes any batch."""
+
     def __init__(self, image_size, patch_size, dim: int, depth: int, heads: int, mlp_dim: int, channels: int, dim_head: int) -> None:
         super().__init__()
         self.image_size, self.patch_size = _pair(image_size), _pair(patch_size)

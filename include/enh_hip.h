@@ -223,7 +223,9 @@ int enh_debug_occupy_cus(int n_wg, float ms, void* stream);
  * ------------------------------------------------------------------------------------------------
  * qkv [B,N,3*H*64] 16-bit (`dtype`) packed exactly as to_qkv emits it (q | k | v thirds, head-major, layers.py:123-124);
  * out [B,N,H*64] 16-bit in the 'b n (h d)' layout to_out consumes (layers.py:130); lse [B,H,N] f32 =
- * row log-sum-exp of the scaled scores (saved for backward).  dim_head = 64, N % 64 == 0.
+ * row log-sum-exp of the scaled scores (saved for backward).  dim_head = 64; N any positive int: every (image, head) attends over its own keys
+ * 0 .. N-1.  N % 64 == 0 runs the aligned kernels; any other N their TAIL forms (attn_fwd_tail_* / attn_bwd_tail_*: the ragged last 64-row tile is
+ * read with its rows clamped to the image, its keys >= N get probability exactly 0, stores are per row) — nothing outside the tensors is read or written.
  * q_prescaled = 1: the q third already holds q * scale * log2(e) (the caller folded the softmax scale into the projection's q rows, once, in
  * fp32 before the 16-bit rounding).  The score products are then log2-domain logits and the kernels feed -max / -lse / -delta through the MFMA C
  * operand instead of spending vector instructions on them (the kernels are vector-issue bound, profiles/r03_attention_lab.txt).  Semantics are
@@ -239,7 +241,9 @@ int enh_attention_forward(const enh_h16* qkv, int B, int N, int H, float scale, 
  *   dq : 1 round-2 arithmetic, 3 -delta (-lse too when q is pre-scaled) as MFMA C operands [default since round 5]
  *   dkv: 1 round-2 arithmetic, 2 -delta (-lse too when q is pre-scaled) as MFMA C operands [default]
  * (the software-pipelined round-3 kernels and the eight-wave antiphase kernels of round 4 were measured slower and are deleted.)
- * Same results up to rounding: every family passes the same parity and bit-reproducibility tests. */
+ * Same results up to rounding: every family passes the same parity and bit-reproducibility tests.
+ * The families are the ALIGNED kernels.  With N % 64 != 0 the selection is accepted and ignored: there is one tail kernel per pass and q convention
+ * (the tail form of the default family; forward with plain q: of family 1), and it runs whatever is selected here. */
 int enh_attention_set_kernel(int fwd, int dq, int dkv);
 /* dqkv [B,N,3*H*64] 16-bit ; delta_ws [B,H,N] f32 scratch.  With ENH_DT_F16 the caller keeps dout inside fp16's range (loss scale): p o (dP - delta) is
  * packed to fp16 before the dQ / dK products. */
@@ -273,7 +277,8 @@ int enh_layernorm_forward_x3(const float* x, const float* w, const float* b, int
                              float* y_f32, float* mean, float* rstd, void* stream);
 /* enh_attention_forward on split operands: qkv_hi / qkv_lo [B,N,3*H*64] (unscaled q); S = Q K^T and O = P V as three MFMA passes each,
  * softmax statistics in fp32.  out3 [B,N,3*H*64] = the x3 row [hi | lo | hi] of the 'b n (h d)' output (A operand of to_out);
- * out_bf16 optional [B,N,H*64] (= the hi plane, what enh_attention_backward reads); lse as enh_attention_forward. */
+ * out_bf16 optional [B,N,H*64] (= the hi plane, what enh_attention_backward reads); lse as enh_attention_forward.  N any positive int (N % 64 != 0:
+ * attn_fwd_tail_x3_kernel, as above). */
 int enh_attention_forward_x3(const enh_bf16* qkv_hi, const enh_bf16* qkv_lo, int B, int N, int H, float scale, enh_bf16* out3,
                              enh_bf16* out_bf16, float* lse, void* stream);
 
