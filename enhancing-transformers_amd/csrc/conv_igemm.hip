@@ -21,7 +21,9 @@
 // partial slabs are added in a fixed order (deterministic, no atomics).
 // Register-staged double buffer (the gather needs per-lane predication, which global_load_lds cannot do), 128 x 128 x 64 tile,
 // 4 waves of 64 x 64 (v_mfma_f32_16x16x32_bf16), 2 workgroups per CU.  C and N multiples of 8; any grid size.
+// The K loops are shared with the dense GEMM kernels: t128_loop.h (128-row kernels), w256_loop.h (256 / 512-row kernels).
 #include "gemm_tiles.h"
+#include "t128_loop.h"
 #include "w256_loop.h"
 
 // conv_pointwise.hip: the dense 1 x 1 geometries with an 8-channel side (the discriminator's first layer) as streaming kernels
@@ -48,14 +50,27 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
 }
 
+// GEMM row M = pixel (B, Y, X) of the logical grid (three unsigned variables of the caller), by two 32-bit divisions (the launcher requires fewer
+// than 2^31 GEMM rows): a 64-bit one costs ~5x the instructions, and a strided epilogue does four per lane.  (A macro: as an inline function, which
+// evaluates M before the grid size, it compiled the setup of the two wide kernels to other code.)
+#define CONV_ROW_PIXEL(G, M, B, Y, X)                                                                                             \
+  do {                                                                                                                            \
+    const unsigned hw_ = (unsigned)(G).Hm * (unsigned)(G).Wm, m_ = (unsigned)(M);                                                 \
+    B = m_ / hw_;                                                                                                                 \
+    const unsigned rem_ = m_ - B * hw_;                                                                                           \
+    Y = rem_ / (unsigned)(G).Wm; X = rem_ - Y * (unsigned)(G).Wm;                                                                 \
+  } while (0)
+
 // output element offset (in pixels) of GEMM row m
 __device__ __forceinline__ int64_t conv_out_pixel(const enh_conv_geom& g, int64_t m) {
-  // 32-bit divisions (the launcher requires fewer than 2^31 GEMM rows): a 64-bit one costs ~5x the instructions, and a strided epilogue does four per lane
-  const unsigned hw = (unsigned)g.Hm * (unsigned)g.Wm, mm = (unsigned)m;
-  const unsigned b = mm / hw, rem = mm - b * hw;
-  const unsigned y = rem / (unsigned)g.Wm, x = rem - y * (unsigned)g.Wm;
+  unsigned b, y, x;
+  CONV_ROW_PIXEL(g, m, b, y, x);
   return ((int64_t)b * g.HO + (int64_t)y * g.os + g.oph) * g.WO + (int64_t)x * g.os + g.opw;
 }
+
+// the result rows are consecutive pixels of the output tensor: GEMM row m is output pixel m.  (A macro: as an inline function it compiled
+// conv_splitk_finish_kernel's branch on it to other code.)
+#define CONV_DENSE(G) ((G).os == 1 && (G).HO == (G).Hm && (G).WO == (G).Wm && (G).oph == 0 && (G).opw == 0)
 
 // the five epilogue modes on four consecutive output columns (bias b4, saved activation ax, addend ad as they were loaded)
 template <typename OT>
@@ -84,7 +99,7 @@ template <typename OT>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& args, f32x4 (&acc)[4][4], int64_t m0, int64_t n0, int wm, int wn, int lg, int l16,
                                               unsigned char* stage) {
   const enh_conv_geom& g = args.g;
-  const bool dense = g.os == 1 && g.HO == g.Hm && g.WO == g.Wm && g.oph == 0 && g.opw == 0;
+  const bool dense = CONV_DENSE(g);
   // wave-uniform: the wave's 64 columns all exist and the rows are consecutive output pixels -> its 64 x 64 block leaves through LDS (see below; the
   // strided rows of a stride-2 input gradient gain nothing from whole-row stores and pay for eight pixel decompositions per lane: 377 -> 412 us)
   const bool staged = dense && n0 + wn * 64 + 64 <= g.N;
@@ -121,24 +136,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& args, f32x4 (&acc)
       const int64_t n = n0 + wn * 64 + j * 16 + lg * 4;
       if (n >= g.N) continue;   // N % 8 == 0: the 4 columns are in or out together
       float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      const uint32_t d0 = ad[i][j].x, d1 = ad[i][j].y;
-      const float e0 = unpack1<OT>((uint16_t)(d0 & 0xffffu)), e1 = unpack1<OT>((uint16_t)(d0 >> 16));
-      const float e2 = unpack1<OT>((uint16_t)(d1 & 0xffffu)), e3 = unpack1<OT>((uint16_t)(d1 >> 16));
-      if (args.mode == 0) {
-        v[0] = fmaxf(v[0] + b4[j].x, 0.f); v[1] = fmaxf(v[1] + b4[j].y, 0.f); v[2] = fmaxf(v[2] + b4[j].z, 0.f); v[3] = fmaxf(v[3] + b4[j].w, 0.f);
-      } else if (args.mode == 1) {
-        const uint32_t a0 = ax[i][j].x, a1 = ax[i][j].y;
-        v[0] = (a0 & 0x7fffu) && !(a0 & 0x8000u) ? v[0] + e0 : 0.f;
-        v[1] = ((a0 >> 16) & 0x7fffu) && !(a0 >> 31) ? v[1] + e1 : 0.f;
-        v[2] = (a1 & 0x7fffu) && !(a1 & 0x8000u) ? v[2] + e2 : 0.f;
-        v[3] = ((a1 >> 16) & 0x7fffu) && !(a1 >> 31) ? v[3] + e3 : 0.f;
-      } else if (args.mode == 3) {
-        v[0] += b4[j].x; v[1] += b4[j].y; v[2] += b4[j].z; v[3] += b4[j].w;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = (v[r] > 0.f ? v[r] : v[r] * args.p0) * args.p1;
-      } else if (args.mode == 4) {
-        v[0] += args.p0 * e0; v[1] += args.p0 * e1; v[2] += args.p0 * e2; v[3] += args.p0 * e3;
-      }
+      conv_epi_value<OT>(args, v, b4[j], ax[i][j], ad[i][j]);
       const u32x2 o_ = {pack2<OT>(v[0], v[1]), pack2<OT>(v[2], v[3])};
       if (staged) {
         const int row = i * 16 + l16;
@@ -150,7 +148,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& args, f32x4 (&acc)
   }
   if (staged) {
     // The accumulator layout offers 8 bytes per lane, 16 rows x 32 B per store instruction; through a wave-private XOR-swizzled 8-KiB LDS tile the block
-    // leaves as 16 bytes per lane, whole 128-byte row segments (gemm.hip gemm_epilogue32_loops has the measurements: 3.1-3.9 -> ~5 TB/s of stores).
+    // leaves as 16 bytes per lane, whole 128-byte row segments (gemm_tiles.h gemm_epilogue32_loops has the measurements: 3.1-3.9 -> ~5 TB/s of stores).
     // Rows that do not exist (orow < 0 above) were skipped by their writer lanes and are skipped by their reader lanes.
     const int lane = lg * 16 + l16;
 #pragma unroll
@@ -189,17 +187,14 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs args)
   for (int i = 0; i < 4; ++i) {
     const int64_t row = m0 + r0 + 32 * i;
     if (row < args.M) {
-      const unsigned hw = (unsigned)g.Hm * (unsigned)g.Wm, rr = (unsigned)row;      // < 2^31 rows (launcher): 32-bit divisions
-      const unsigned b = rr / hw, rem = rr - b * hw;
-      const int y = (int)(rem / (unsigned)g.Wm), x = (int)(rem - (unsigned)y * (unsigned)g.Wm);
-      py[i] = y * g.gs; px[i] = x * g.gs;
+      unsigned b, y, x;
+      CONV_ROW_PIXEL(g, row, b, y, x);
+      py[i] = (int)y * g.gs; px[i] = (int)x * g.gs;
       pb[i] = (int64_t)b * g.Hs * g.Ws;
     } else { py[i] = -(1 << 28); px[i] = -(1 << 28); pb[i] = 0; }   // every tap of an out-of-range row falls outside the image -> zeros
   }
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
-  // (a second register set for the gathered operand — loads two K steps ahead — was measured SLOWER: 285-383 vs 405 TF/s; the allocator then
-  //  fills all 256 registers and spills)
-  u32x4 ra[4], rb[4];
+  u32x4 ra[4], rb[4];   // one register set (t128_loop.h says why)
   auto gather = [&](int64_t k0) {
     const int64_t kk = k0 + c * 8;
     const int tap = (int)(kk / g.C), ch = (int)(kk - (int64_t)tap * g.C);
@@ -219,42 +214,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs args)
   };
 
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  if (nk > 0) {
-    gather(0);
-    tile_sstore<false>(ra, smem, t);
-    tile_sstore<false>(rb, smem + G_TILE_BYTES, t);
-  }
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int stage = kt & 1;
-    if (kt + 1 < nk) gather((int64_t)(kt + 1) * G_BK);
-    const unsigned char* sa = smem + stage * (2 * G_TILE_BYTES);
-    const unsigned char* sb = sa + G_TILE_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      s16x8 fa[4], fb[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = tile_frag<false>(sa, wm * 64 + i * 16, ks, lg, l16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fb[j] = tile_frag<false>(sb, wn * 64 + j * 16, ks, lg, l16);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = mfma16<OT>(fb[j], fa[i], acc[i][j]);
-    }
-    if (kt + 1 < nk) {
-      unsigned char* na = smem + (stage ^ 1) * (2 * G_TILE_BYTES);
-      tile_sstore<false>(ra, na, t);
-      tile_sstore<false>(rb, na + G_TILE_BYTES, t);
-    }
-    __syncthreads();
-  }
+#define T128_GATHER(KT) gather((int64_t)(KT) * G_BK)
+  T128_REG_MAINLOOP(false, false, nk);
+#undef T128_GATHER
   conv_epilogue<OT>(args, acc, m0, n0, wm, wn, lg, l16, smem + wave * 8192);   // the stages are free: no LDS read follows the loop's last barrier
 }
 
@@ -262,8 +224,8 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs args)
 // LDS-DMA form of the same convolution for C % 64 == 0 (every 3x3 / 1x1 layer of the discriminator past the first, the VGG16 trunk): a 64-deep K step
 // then lies inside ONE tap, so the gather is "row pointer + a tap offset that is uniform for the workgroup", and global_load_lds (16 B per lane straight
 // into the swizzled LDS image, no staging registers, no ds_write pass) can fetch it — the zero padding by pointing the lanes whose tap falls outside
-// the image at a zero page instead of predicating them.  K loop = gemm_bf16_pipe2_kernel's (gemm.hip): one mid-iteration barrier, the loads of stage
-// kt+2 spread one per two MFMAs, fragments of the next half-step read under the MFMAs of the current one.
+// the image at a zero page instead of predicating them.  K loop = the "pipe2" loop of t128_loop.h, which gemm_pipe2_kernel (gemm_kernels.h) runs too:
+// one mid-iteration barrier, the loads of stage kt+2 spread one per two MFMAs, fragments of the next half-step read under the MFMAs of the current one.
 // =================================================================================================
 __device__ __attribute__((aligned(16))) uint32_t g_conv_zero_page[4] = {0u, 0u, 0u, 0u};
 
@@ -296,10 +258,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_glds_kernel(const ConvArgs 
     coff[i] = c * 8;
     const int64_t row = m0 + r;
     if (row < args.M) {
-      const unsigned hw = (unsigned)g.Hm * (unsigned)g.Wm, rr = (unsigned)row;      // < 2^31 rows (launcher): 32-bit divisions
-      const unsigned b = rr / hw, rem = rr - b * hw;
-      const int y = (int)(rem / (unsigned)g.Wm), x = (int)(rem - (unsigned)y * (unsigned)g.Wm);
-      py[i] = y * g.gs; px[i] = x * g.gs; pb[i] = (int64_t)b * g.Hs * g.Ws;
+      unsigned b, y, x;
+      CONV_ROW_PIXEL(g, row, b, y, x);
+      py[i] = (int)y * g.gs; px[i] = (int)x * g.gs; pb[i] = (int64_t)b * g.Hs * g.Ws;
     } else { py[i] = -(1 << 28); px[i] = -(1 << 28); pb[i] = 0; }
     int64_t co = n0 + r;                       // B operand (weights [N][K]): rows beyond N are clamped, their products land in columns that are never stored
     if (co > g.N - 1) co = g.N - 1;
@@ -319,76 +280,28 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_glds_kernel(const ConvArgs 
       ap[i] = ok ? args.X + (pb[i] + (int64_t)sy * g.Ws + sx) * g.C + ch0 + coff[i] : zero;
     }
   };
-#define CG_LOAD(PTR, BUF, WHICH, I)                                                                                                          \
-  __builtin_amdgcn_global_load_lds((const GLB_AS void*)(PTR), (LDS_AS void*)(smem + (BUF) * (2 * G_TILE_BYTES) + (WHICH) * G_TILE_BYTES + (wave * 4 + (I)) * 1024), 16, 0, ENH_GLDS_AUX)
-#define CG_READ(FA, FB, BUF, KS)                                                                                         \
-  do {                                                                                                                   \
-    const unsigned char* sa_ = smem + (BUF) * (2 * G_TILE_BYTES);                                                        \
-    const unsigned char* sb_ = sa_ + G_TILE_BYTES;                                                                       \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) FA[i_] = tile_frag<false>(sa_, wm * 64 + i_ * 16, KS, lg, l16);     \
-    _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) FB[j_] = tile_frag<false>(sb_, wn * 64 + j_ * 16, KS, lg, l16);     \
-  } while (0)
-
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   s16x8 fa0[4], fb0[4], fa1[4], fb1[4];
   const uint16_t* ap[4];
-
-  if (nk > 0) {
-    a_ptrs(0, ap);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { CG_LOAD(ap[i], 0, 0, i); CG_LOAD(bsrc[i], 0, 1, i); bsrc[i] += G_BK; }
-    if (nk > 1) {
-      a_ptrs(1, ap);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { CG_LOAD(ap[i], 1, 0, i); CG_LOAD(bsrc[i], 1, 1, i); bsrc[i] += G_BK; }
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // stage 0 landed (stage 1's 8 loads may be outstanding)
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    CG_READ(fa0, fb0, 0, 0);
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-  }
-  int buf = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    CG_READ(fa1, fb1, buf, 1);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        acc[i][j] = mfma16<OT>(fb0[j], fa0[i], acc[i][j]);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) lgkmcnt(0): F1 in registers, my share of stage kt+1 landed
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (kt + 1 < nk) CG_READ(fa0, fb0, buf ^ 1, 0);
-    const bool more = kt + 2 < nk;
-    if (more) a_ptrs(kt + 2, ap);
-    __builtin_amdgcn_sched_barrier(0);
-    // second half: the 8 loads of stage kt+2 (into the buffer stage kt just vacated) one per two MFMAs
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
-        acc[i][jj * 2] = mfma16<OT>(fb1[jj * 2], fa1[i], acc[i][jj * 2]);
-        acc[i][jj * 2 + 1] = mfma16<OT>(fb1[jj * 2 + 1], fa1[i], acc[i][jj * 2 + 1]);
-        if (more) {
-          if (jj == 0) CG_LOAD(ap[i], buf, 0, i);
-          else { CG_LOAD(bsrc[i], buf, 1, i); bsrc[i] += G_BK; }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): next F0 has arrived under the MFMAs above
-    buf ^= 1;
-  }
-#undef CG_LOAD
-#undef CG_READ
+  // the requests of a stage go out as A0, B0, A1, B1, ..: A slab I under the first MFMA pair of row-block I, B slab I under the second
+#define CG_LOAD_B(STAGE, I) do { T128_P2_LOAD(bsrc[I], STAGE, 1, I); bsrc[I] += G_BK; } while (0)
+#define T128_P2_STAGE(S)                                                                                                 \
+  do {                                                                                                                   \
+    a_ptrs(S, ap);                                                                                                       \
+    unsigned char* const st_ = smem + (S) * T128_STAGE_BYTES;                                                            \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) { T128_P2_LOAD(ap[i], st_, 0, i); CG_LOAD_B(st_, i); }                  \
+  } while (0)
+#define T128_P2_POINTERS(KT, EXISTS) do { if (EXISTS) a_ptrs(KT, ap); } while (0)
+#define T128_P2_REQUEST(STAGE, I, JJ)                                                                                    \
+  do {                                                                                                                   \
+    if ((JJ) == 0) T128_P2_LOAD(ap[I], STAGE, 0, I);                                                                     \
+    else CG_LOAD_B(STAGE, I);                                                                                            \
+  } while (0)
+  T128_P2_MAINLOOP(false, false, nk);
+#undef CG_LOAD_B
+#undef T128_P2_STAGE
+#undef T128_P2_POINTERS
+#undef T128_P2_REQUEST
   if (args.ws) {   // split over K: the f32 partial tile goes to this split's slab as it lies in the accumulators (16 bytes per lane)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -419,7 +332,7 @@ __global__ __launch_bounds__(256) void conv_splitk_finish_kernel(const ConvArgs 
     const f32x4 b = *reinterpret_cast<const f32x4*>(args.ws + ((int64_t)s_ * args.M + m) * g.N + n);
     a[0] += b[0]; a[1] += b[1]; a[2] += b[2]; a[3] += b[3];
   }
-  const bool dense = g.os == 1 && g.HO == g.Hm && g.WO == g.Wm && g.oph == 0 && g.opw == 0;
+  const bool dense = CONV_DENSE(g);
   const int64_t orow = (dense ? m : conv_out_pixel(g, m)) * g.N;
   float v[4] = {a[0], a[1], a[2], a[3]};
   const float4 b4 = ((args.mode == 0 || args.mode == 3) && args.bias) ? *reinterpret_cast<const float4*>(args.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -448,7 +361,7 @@ template <typename OT, int NJ>
 __device__ __forceinline__ void conv_epilogue32(const ConvArgs& args, f32x16 (&acc)[4][NJ], int64_t mw, int64_t nw, int lane, float* wave_bias, unsigned char* stage) {
   const enh_conv_geom& g = args.g;
   const int l31 = lane & 31, hi = lane >> 5;
-  const bool dense = g.os == 1 && g.HO == g.Hm && g.WO == g.Wm && g.oph == 0 && g.opw == 0;
+  const bool dense = CONV_DENSE(g);
   const bool has_bias = (args.mode == 0 || args.mode == 3) && args.bias;
   const float4 bv = (lane < NJ * 8 && has_bias) ? *reinterpret_cast<const float4*>(args.bias + nw + lane * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
   const bool want_aux = args.mode == 1, want_add = (args.mode == 1 || args.mode == 4) && args.add;
@@ -495,6 +408,37 @@ __device__ __forceinline__ void conv_epilogue32(const ConvArgs& args, f32x16 (&a
   }
 }
 
+// ---- pixel staging state of the two wide kernels (conv_igemm_w256_kernel, conv_igemm_w512_kernel), written once ------------------------------------
+// A staging lane keeps, per 1-KiB piece u of its wave's 128 pixels, an element offset rowoff[u] and a packed (y, x) pyx[u]; the wave keeps the tap of
+// the stage the NEXT request belongs to in scalar registers: s_ch, s_jx, s_jy (channel block, tap), s_dy, s_dx (its pixel offset), s_off (its element
+// offset).  In scope where these expand: g, args, m0, wave, lane, zero (the zero page), int rowoff[16], pyx[16] and the scalar state.
+// pixel (b, y, x) of this lane's row of piece 0 by one pair of 32-bit divisions; the rows of pieces 1..15 are 8 pixels further each
+#define CONV_WIDE_PIXEL_FIRST() unsigned pb, py_, px_; CONV_ROW_PIXEL(g, (unsigned)m0 + wave * 128 + (lane >> 3), pb, py_, px_)
+// piece U (row R of the sub-tile, logical chunk CHUNK of the row image), then on to the pixel of piece U + 1
+#define CONV_WIDE_PIXEL_PIECE(U, R, CHUNK)                                                                                        \
+  do {                                                                                                                            \
+    const bool exists = (int64_t)m0 + wave * 128 + (R) < args.M;                                                                  \
+    rowoff[U] = exists ? (int)(((pb * g.Hs + py_ * g.gs) * g.Ws + px_ * g.gs) * g.C) + (CHUNK) * 8 : 0;                           \
+    pyx[U] = exists ? (int)(((py_ * g.gs) << 16) | (px_ * g.gs)) : 0x40004000; /* no tap of a row that does not exist is inside the image */  \
+    px_ += 8;                                                                                                                     \
+    while (px_ >= (unsigned)g.Wm) { px_ -= (unsigned)g.Wm; ++py_; }                                                               \
+    while (py_ >= (unsigned)g.Hm) { py_ -= (unsigned)g.Hm; ++pb; }                                                                \
+  } while (0)
+// the tap state moves one K stage (64 channels) on: through the channels of a tap, then the taps of a row, then the rows
+#define CONV_WIDE_TAP_ADVANCE()                                                                                                   \
+  do {                                                                                                                            \
+    s_ch += G_BK;                                                                                                                 \
+    if (s_ch == g.C) { s_ch = 0; if (++s_jx == g.ntx) { s_jx = 0; ++s_jy; } s_dy = g.oy0 + s_jy * g.sty; s_dx = g.ox0 + s_jx * g.stx; } \
+    s_off = (s_dy * g.Ws + s_dx) * g.C + s_ch;                                                                                    \
+  } while (0)
+// piece U of the current tap from BASE to the LDS address DST; lanes whose tap falls outside LIM_Y x LIM_X read the zero page
+#define CONV_WIDE_REQUEST(BASE, LIM_Y, LIM_X, DST, U)                                                                             \
+  do {                                                                                                                            \
+    const unsigned sy_ = (unsigned)((pyx[U] >> 16) + s_dy), sx_ = (unsigned)((pyx[U] & 0xffff) + s_dx);                           \
+    const uint16_t* p_ = (sy_ < (LIM_Y) && sx_ < (LIM_X)) ? (BASE) + (rowoff[U] + s_off) : zero;                                  \
+    __builtin_amdgcn_global_load_lds((const GLB_AS void*)p_, (LDS_AS void*)(DST), 16, 0, ENH_GLDS_AUX);                           \
+  } while (0)
+
 template <typename OT, int NJ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv_igemm_w256_kernel(const ConvArgs args) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // [2 slots][A0 | A1 | B0 | B1] + bias strips
@@ -516,23 +460,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const uint16_t* const zero = reinterpret_cast<const uint16_t*>(g_conv_zero_page);
   int rowoff[16], pyx[16];
   {
-    // pixel (b, y, x) of this lane's row of piece 0 by one 32-bit division; the rows of pieces 1..15 are 8 pixels further each
-    const unsigned hw = (unsigned)g.Hm * (unsigned)g.Wm;
-    const unsigned row0 = (unsigned)m0 + wave * 128 + (lane >> 3);
-    unsigned pb = row0 / hw, prem = row0 - pb * hw;
-    unsigned py_ = prem / (unsigned)g.Wm, px_ = prem - py_ * (unsigned)g.Wm;
+    CONV_WIDE_PIXEL_FIRST();
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int r = u * 8 + (lane >> 3), pc = lane & 7;    // row of the sub-tile, physical chunk ; logical chunk of the row image:
       const int c = pc ^ ((r >> 1) & 7);
       if (stage_a) {
-        const bool exists = (int64_t)m0 + wave * 128 + r < args.M;
-        rowoff[u] = exists ? (int)(((pb * g.Hs + py_ * g.gs) * g.Ws + px_ * g.gs) * g.C) + c * 8 : 0;
-        pyx[u] = exists ? (int)(((py_ * g.gs) << 16) | (px_ * g.gs)) : 0x40004000;   // every tap of a row that does not exist falls outside the image
-        px_ += 8;
-        while (px_ >= (unsigned)g.Wm) { px_ -= (unsigned)g.Wm; ++py_; }
-        while (py_ >= (unsigned)g.Hm) { py_ -= (unsigned)g.Hm; ++pb; }
-      } else {
+        CONV_WIDE_PIXEL_PIECE(u, r, c);
+      } else {   // a weight row is a "pixel" at (0, 0) of a 1 x 1 image whose tap never moves
         rowoff[u] = (int)((n0 + (wave - 2) * 128 + r) * args.K) + c * 8;
         pyx[u] = 0;
       }
@@ -543,22 +478,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int s_dy = stage_a ? g.oy0 : 0, s_dx = stage_a ? g.ox0 : 0;
   int s_off = stage_a ? (s_dy * g.Ws + s_dx) * g.C : 0;
   const unsigned lim_y = stage_a ? (unsigned)g.Hs : 1u, lim_x = stage_a ? (unsigned)g.Ws : 1u;
-#define W256_ADVANCE()                                                                                                            \
-  do {                                                                                                                            \
-    if (stage_a) {                                                                                                                \
-      s_ch += G_BK;                                                                                                               \
-      if (s_ch == g.C) { s_ch = 0; if (++s_jx == g.ntx) { s_jx = 0; ++s_jy; } s_dy = g.oy0 + s_jy * g.sty; s_dx = g.ox0 + s_jx * g.stx; } \
-      s_off = (s_dy * g.Ws + s_dx) * g.C + s_ch;                                                                                  \
-    } else s_off += G_BK;                                                                                                         \
-  } while (0)
-#define CW_ISSUE_ONE(SLOT, U)                                                                                                     \
-  do {                                                                                                                            \
-    {                                                                                                                             \
-      const unsigned sy_ = (unsigned)((pyx[U] >> 16) + s_dy), sx_ = (unsigned)((pyx[U] & 0xffff) + s_dx);                         \
-      const uint16_t* p_ = (sy_ < lim_y && sx_ < lim_x) ? gbase + (rowoff[U] + s_off) : zero;                                     \
-      __builtin_amdgcn_global_load_lds((const GLB_AS void*)p_, (LDS_AS void*)(my_sub + (SLOT) * CW_SLOT + (U) * 1024), 16, 0, ENH_GLDS_AUX);  \
-    }                                                                                                                             \
-  } while (0)
+#define W256_ADVANCE() do { if (stage_a) CONV_WIDE_TAP_ADVANCE(); else s_off += G_BK; } while (0)
+#define CW_ISSUE_ONE(SLOT, U) CONV_WIDE_REQUEST(gbase, lim_y, lim_x, my_sub + (SLOT) * CW_SLOT + (U) * 1024, U)
   f32x16 acc[4][NJ];
   s16x8 fa0[4], fb0[4], fa1[4], fb1[4];
 #define W256_NJ NJ
@@ -607,20 +528,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const uint16_t* const zero = reinterpret_cast<const uint16_t*>(g_conv_zero_page);
   int rowoff[16], pyx[16], boff[4];
   {
-    const unsigned hw = (unsigned)g.Hm * (unsigned)g.Wm;
-    const unsigned row0 = (unsigned)m0 + wave * 128 + (lane >> 3);
-    unsigned pb = row0 / hw, prem = row0 - pb * hw;
-    unsigned py_ = prem / (unsigned)g.Wm, px_ = prem - py_ * (unsigned)g.Wm;
+    CONV_WIDE_PIXEL_FIRST();
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int r = u * 8 + (lane >> 3), pc = lane & 7;
       const int c = pc ^ ((r >> 1) & 7);
-      const bool exists = (int64_t)m0 + wave * 128 + r < args.M;
-      rowoff[u] = exists ? (int)(((pb * g.Hs + py_ * g.gs) * g.Ws + px_ * g.gs) * g.C) + c * 8 : 0;
-      pyx[u] = exists ? (int)(((py_ * g.gs) << 16) | (px_ * g.gs)) : 0x40004000;   // every tap of a row that does not exist falls outside the image
-      px_ += 8;
-      while (px_ >= (unsigned)g.Wm) { px_ -= (unsigned)g.Wm; ++py_; }
-      while (py_ >= (unsigned)g.Hm) { py_ -= (unsigned)g.Hm; ++pb; }
+      CONV_WIDE_PIXEL_PIECE(u, r, c);
     }
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
@@ -634,18 +547,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int s_ch = 0, s_jx = 0, s_jy = 0, s_k = 0;
   int s_dy = g.oy0, s_dx = g.ox0;
   int s_off = (s_dy * g.Ws + s_dx) * g.C;
-#define W256_ADVANCE()                                                                                                            \
-  do {                                                                                                                            \
-    s_k += G_BK; s_ch += G_BK;                                                                                                    \
-    if (s_ch == g.C) { s_ch = 0; if (++s_jx == g.ntx) { s_jx = 0; ++s_jy; } s_dy = g.oy0 + s_jy * g.sty; s_dx = g.ox0 + s_jx * g.stx; } \
-    s_off = (s_dy * g.Ws + s_dx) * g.C + s_ch;                                                                                    \
-  } while (0)
-#define CX_ISSUE_A(SLOT, U)                                                                                                       \
-  do {                                                                                                                            \
-    const unsigned sy_ = (unsigned)((pyx[U] >> 16) + s_dy), sx_ = (unsigned)((pyx[U] & 0xffff) + s_dx);                           \
-    const uint16_t* p_ = (sy_ < (unsigned)g.Hs && sx_ < (unsigned)g.Ws) ? args.X + (rowoff[U] + s_off) : zero;                    \
-    __builtin_amdgcn_global_load_lds((const GLB_AS void*)p_, (LDS_AS void*)(my_a + (SLOT) * CX_SLOT + (U) * 1024), 16, 0, ENH_GLDS_AUX);     \
-  } while (0)
+#define W256_ADVANCE() do { s_k += G_BK; CONV_WIDE_TAP_ADVANCE(); } while (0)
+#define CX_ISSUE_A(SLOT, U) CONV_WIDE_REQUEST(args.X, (unsigned)g.Hs, (unsigned)g.Ws, my_a + (SLOT) * CX_SLOT + (U) * 1024, U)
 #define CX_ISSUE_B(SLOT, V)                                                                                                       \
   __builtin_amdgcn_global_load_lds((const GLB_AS void*)(args.Wt + (boff[V] + s_k)), (LDS_AS void*)(my_b + (SLOT) * CX_SLOT + (V) * 1024), 16, 0, ENH_GLDS_AUX)
   f32x16 acc[4][4];
@@ -714,8 +617,7 @@ static ConvWideTile conv_wide_tile(const ConvArgs& a) {
   if (g_conv_variant == 3) return wide;
   // per-shape choice (B = 16 layer table, profiles/r04_conv_layers.txt): with dense output rows the large tiles win 1.2-1.4x (760 -> 930, 764 -> 1052 TF/s);
   // the parity classes of a stride-2 input gradient (1-4 taps: two to eight K stages per tile) do not amortise the deeper prologue (408 -> 326)
-  const bool dense = g.os == 1 && g.HO == g.Hm && g.WO == g.Wm && g.oph == 0 && g.opw == 0;
-  if (!dense) return CONV_WIDE_NONE;
+  if (!CONV_DENSE(g)) return CONV_WIDE_NONE;
   const int64_t tiles = wide == CONV_WIDE_256x256 ? ((a.M + 255) / 256) * (g.N / 256) : ((a.M + 511) / 512) * (g.N / 128);
   return tiles >= enh_device_cus() ? wide : CONV_WIDE_NONE;   // below one tile per CU the 128-row kernels (four times the workgroups, two per CU) fill the chip better
 }
@@ -870,7 +772,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_igemm_kernel(const ConvWgra
     pb[i] = (int)b; py[i] = (int)(rem / g.Wm); px[i] = (int)(rem - (int64_t)py[i] * g.Wm);
   }
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
-  u32x4 ra[4], rb[4];   // one register set (a second one, as conv_igemm_kernel has for its gathered operand, spills here: 12 pixel-state registers)
+  u32x4 ra[4], rb[4];   // one register set, as in conv_igemm_kernel (a second one spills there, and here there are 12 pixel-state registers besides)
   auto gather = [&](int64_t k0) {
     tile_gload<true>(ra, args.DY, g.N, m0, g.N, k0, k_end, t);
 #pragma unroll
@@ -891,42 +793,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_igemm_kernel(const ConvWgra
   };
 
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  if (nk > 0) {
-    gather(k_begin);
-    tile_sstore<true>(ra, smem, t);
-    tile_sstore<true>(rb, smem + G_TILE_BYTES, t);
-  }
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int stage = kt & 1;
-    if (kt + 1 < nk) gather(k_begin + (int64_t)(kt + 1) * G_BK);
-    const unsigned char* sa = smem + stage * (2 * G_TILE_BYTES);
-    const unsigned char* sb = sa + G_TILE_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      s16x8 fa[4], fb[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = tile_frag<true>(sa, wm * 64 + i * 16, ks, lg, l16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fb[j] = tile_frag<true>(sb, wn * 64 + j * 16, ks, lg, l16);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = mfma16<OT>(fb[j], fa[i], acc[i][j]);
-    }
-    if (kt + 1 < nk) {
-      unsigned char* na = smem + (stage ^ 1) * (2 * G_TILE_BYTES);
-      tile_sstore<true>(ra, na, t);
-      tile_sstore<true>(rb, na + G_TILE_BYTES, t);
-    }
-    __syncthreads();
-  }
+#define T128_GATHER(KT) gather(k_begin + (int64_t)(KT) * G_BK)
+  T128_REG_MAINLOOP(true, true, nk);
+#undef T128_GATHER
   gemm_epilogue<OT>(args.e, acc, m0, n0, wm, wn, lg, l16, split);
 }
 

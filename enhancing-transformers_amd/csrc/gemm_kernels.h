@@ -17,6 +17,8 @@
 //   gemm_pipe2_kernel  128x128x64 tile, 4 waves (2x2, each 4x4 v_mfma_f32_16x16x32_bf16), two 32-KiB LDS stages filled by
 //                           global_load_lds, K-loop software-pipelined around one mid-iteration barrier; 2 workgroups per CU.  Default.
 //   gemm_kernel        register-staged 128x128x64 fallback for K not a multiple of 64 (zero-fills partial tiles).
+// The K loops are written once and shared with the convolutions (conv_igemm.hip): w256_loop.h for the 256-wide family, t128_loop.h for the two
+// 128x128x64 kernels.
 // All LDS images are XOR-swizzled so that staging writes, ds_read_b128 fragments and the transpose reads are bank-conflict free under
 // the gfx950 bank model (MI355X_MICROARCH.md §LDS; checked by tools/lds_bank_check.py; SQ_LDS_BANK_CONFLICT = 0 measured).
 // The MFMA is issued with swapped operands (D = B_frag x A_frag) so each lane ends up with 4 CONSECUTIVE output columns of one row: the
@@ -27,6 +29,7 @@
 #include "common.h"
 
 #include "gemm_launch.h"
+#include "t128_loop.h"
 #include "w256_loop.h"
 
 template <typename OT, bool TA, bool TB>
@@ -46,50 +49,16 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs args) {
   const int nk = (int)((k_end - k_begin + G_BK - 1) / G_BK);
 
   u32x4 ra[4], rb[4];
-
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  if (nk > 0) {
-    tile_gload<TA>(ra, args.A, args.lda, m0, args.M, k_begin, k_end, t);
-    tile_gload<TB>(rb, args.B, args.ldb, n0, args.N, k_begin, k_end, t);
-    tile_sstore<TA>(ra, smem, t);
-    tile_sstore<TB>(rb, smem + G_TILE_BYTES, t);
-  }
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int stage = kt & 1;
-    if (kt + 1 < nk) {
-      const int64_t k0 = k_begin + (int64_t)(kt + 1) * G_BK;
-      tile_gload<TA>(ra, args.A, args.lda, m0, args.M, k0, k_end, t);
-      tile_gload<TB>(rb, args.B, args.ldb, n0, args.N, k0, k_end, t);
-    }
-    const unsigned char* sa = smem + stage * (2 * G_TILE_BYTES);
-    const unsigned char* sb = sa + G_TILE_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      s16x8 fa[4], fb[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = tile_frag<TA>(sa, wm * 64 + i * 16, ks, lg, l16);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fb[j] = tile_frag<TB>(sb, wn * 64 + j * 16, ks, lg, l16);
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = mfma16<OT>(fb[j], fa[i], acc[i][j]);
-    }
-    if (kt + 1 < nk) {
-      unsigned char* na = smem + (stage ^ 1) * (2 * G_TILE_BYTES);
-      tile_sstore<TA>(ra, na, t);
-      tile_sstore<TB>(rb, na + G_TILE_BYTES, t);
-    }
-    __syncthreads();
-  }
-
+  // K step KT of this split: partial tiles (rows / columns past M / N, k past k_end) are zero-filled
+#define T128_GATHER(KT)                                                                                                  \
+  do {                                                                                                                   \
+    const int64_t k0 = k_begin + (int64_t)(KT) * G_BK;                                                                   \
+    tile_gload<TA>(ra, args.A, args.lda, m0, args.M, k0, k_end, t);                                                      \
+    tile_gload<TB>(rb, args.B, args.ldb, n0, args.N, k0, k_end, t);                                                      \
+  } while (0)
+  T128_REG_MAINLOOP(TA, TB, nk);
+#undef T128_GATHER
   gemm_epilogue<OT>(args, acc, m0, n0, wm, wn, lg, l16, split);
 }
 
@@ -121,17 +90,8 @@ __device__ __forceinline__ const uint16_t* glds_src_ptr(const uint16_t* __restri
 }
 
 // =================================================================================================
-// "pipe2": 128 x 128 x 64 tile, 4 waves, two LDS stages, direct-to-LDS loads — with the K-loop software-pipelined
-// around ONE mid-iteration barrier:
-//     read F1 = fragments (kt, k 32..63)            | LDS latency of F1 hides under ...
-//     16 MFMAs on F0 = fragments (kt, k 0..31)      | ... these MFMAs
-//     lgkmcnt(0) ; vmcnt(0) ; s_barrier             <- every wave now holds ALL of stage kt in registers, and its
-//                                                      share of stage kt+1 (issued one full iteration ago) has landed
-//     global_load_lds stage kt+2 -> the buffer of stage kt   (free: nobody reads it any more)
-//     read F0 = fragments (kt+1, k 0..31)           | latency hides under ...
-//     16 MFMAs on F1                                | ... these MFMAs
-// so loads get a whole iteration to arrive with only two 32-KiB buffers (two workgroups per CU), and no ds_read
-// latency is exposed in steady state.  Raw s_barrier + explicit waits: __syncthreads() would drain differently.
+// "pipe2": 128 x 128 x 64 tile, 4 waves, two LDS stages, direct-to-LDS loads, running the K loop of t128_loop.h (software-pipelined around ONE
+// mid-iteration barrier; the schedule is described there).  The 8 requests of a stage go out as A slabs 0-3, then B slabs 0-3.
 // =================================================================================================
 template <typename OT, bool TA, bool TB>
 __global__ __launch_bounds__(256, 2) void gemm_pipe2_kernel(const GemmArgs args) {
@@ -158,84 +118,25 @@ __global__ __launch_bounds__(256, 2) void gemm_pipe2_kernel(const GemmArgs args)
     step[i] = TA ? (int64_t)G_BK * args.lda : (int64_t)G_BK;
     step[4 + i] = TB ? (int64_t)G_BK * args.ldb : (int64_t)G_BK;
   }
-#define P2_ISSUE(BUF)                                                                                                    \
-  do {                                                                                                                   \
-    unsigned char* base_ = smem + (BUF) * (2 * G_TILE_BYTES);                                                            \
-    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) {                                                                   \
-      __builtin_amdgcn_global_load_lds((const GLB_AS void*)src[i_],                                                      \
-                                       (LDS_AS void*)(base_ + (i_ >> 2) * G_TILE_BYTES + (wave * 4 + (i_ & 3)) * 1024), 16, 0, ENH_GLDS_AUX); \
-      src[i_] += step[i_];                                                                                               \
-    }                                                                                                                    \
-  } while (0)
-#define P2_READ(FA, FB, BUF, KS)                                                                                         \
-  do {                                                                                                                   \
-    const unsigned char* sa_ = smem + (BUF) * (2 * G_TILE_BYTES);                                                        \
-    const unsigned char* sb_ = sa_ + G_TILE_BYTES;                                                                       \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) FA[i_] = tile_frag<TA>(sa_, wm * 64 + i_ * 16, KS, lg, l16);        \
-    _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) FB[j_] = tile_frag<TB>(sb_, wn * 64 + j_ * 16, KS, lg, l16);        \
-  } while (0)
-#define P2_MMA(FA, FB)                                                                                                   \
-  do {                                                                                                                   \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                                     \
-      _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                                   \
-        acc[i_][j_] = mfma16<OT>(FB[j_], FA[i_], acc[i_][j_]); \
-  } while (0)
-
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   s16x8 fa0[4], fb0[4], fa1[4], fb1[4];
-
-  if (nk > 0) {
-    P2_ISSUE(0);
-    if (nk > 1) {
-      P2_ISSUE(1);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // stage 0 landed (stage 1's 8 loads may be outstanding)
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    P2_READ(fa0, fb0, 0, 0);
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): same state on both edges into the loop header
-  }
-  int buf = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    P2_READ(fa1, fb1, buf, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    P2_MMA(fa0, fb0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0): F1 in registers, my share of stage kt+1 landed
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (kt + 1 < nk) P2_READ(fa0, fb0, buf ^ 1, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    // second half: the 8 global_load_lds of stage kt+2 are spread one per two MFMAs instead of issued as a burst — a
-    // burst is back-pressured by the texture addresser (~64 B/clk/CU) and the in-order wave cannot issue MFMAs meanwhile
-    const bool more = kt + 2 < nk;
-    unsigned char* nbase = smem + buf * (2 * G_TILE_BYTES);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
-        const int ld = i * 2 + jj;  // load slot 0..7
-        acc[i][jj * 2] = mfma16<OT>(fb1[jj * 2], fa1[i], acc[i][jj * 2]);
-        acc[i][jj * 2 + 1] = mfma16<OT>(fb1[jj * 2 + 1], fa1[i], acc[i][jj * 2 + 1]);
-        if (more) {
-          __builtin_amdgcn_global_load_lds((const GLB_AS void*)src[ld], (LDS_AS void*)(nbase + (ld >> 2) * G_TILE_BYTES + (wave * 4 + (ld & 3)) * 1024), 16, 0, ENH_GLDS_AUX);
-          src[ld] += step[ld];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0) only: next F0 has arrived under the MFMAs above (builtin, so the
-                                         // compiler's wait-count pass sees it and adds no conservative wait at the loop top)
-    buf ^= 1;
-  }
-#undef P2_ISSUE
-#undef P2_READ
-#undef P2_MMA
+  // load slot LD = 0..7 of a K step (A slabs 0-3, B slabs 0-3) into the stage at STAGE; the slot's pointer moves to the next K step
+#define P2_LOAD(STAGE, LD)                                                                                               \
+  do {                                                                                                                   \
+    T128_P2_LOAD(src[LD], STAGE, (LD) >> 2, (LD) & 3);                                                                   \
+    src[LD] += step[LD];                                                                                                 \
+  } while (0)
+#define T128_P2_STAGE(S)                                                                                                 \
+  do {                                                                                                                   \
+    _Pragma("unroll") for (int i_ = 0; i_ < 8; ++i_) P2_LOAD(smem + (S) * T128_STAGE_BYTES, i_);                         \
+  } while (0)
+#define T128_P2_POINTERS(KT, EXISTS)   // nothing to do: the pointers step as they are used
+#define T128_P2_REQUEST(STAGE, I, JJ) P2_LOAD(STAGE, (I) * 2 + (JJ))
+  T128_P2_MAINLOOP(TA, TB, nk);
+#undef P2_LOAD
+#undef T128_P2_STAGE
+#undef T128_P2_POINTERS
+#undef T128_P2_REQUEST
   gemm_epilogue<OT>(args, acc, m0, n0, wm, wn, lg, l16, split);
 }
 

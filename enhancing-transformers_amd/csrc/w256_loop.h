@@ -1,6 +1,6 @@
 // w256_loop.h — the two-slot, one-wave-per-SIMD K loop of the 256-wide kernels, written once.  It is run by gemm_w256_body (gemm_kernels.h) and by
 // conv_igemm_w256_kernel, conv_igemm_w512_kernel and conv_wgrad_w256_kernel (conv_igemm.hip); the persistent gemm_w256p_kernel runs its K-step inside
-// a tile loop of its own, gemm_w256r_kernel uses its MFMA and fragment-read forms.
+// a tile loop of its own, gemm_w256r_kernel uses its MFMA and fragment-read forms.  (The two K loops of the 128 x 128 x 64 kernels: t128_loop.h.)
 //
 // "w256": a 256 x 256 x 64 workgroup tile (512 x 128 in conv_igemm_w512_kernel), FOUR waves of 128 x 128 — one wave per SIMD, 256 accumulator
 // registers (AGPRs) + ~170 VGPRs.  Round-2 design, measured step by step in tools/probe/gemm_lab.cpp (profiles/r02_gemm_lab.txt):
