@@ -57,6 +57,7 @@ extern "C" int enh_attention_forward(const enh_h16* qkv, int B, int N, int H, fl
   int fam = g_att_fwd ? g_att_fwd : ATT_DEFAULT_FWD;
   if (fam == 5 && !q_prescaled) fam = 1;                         // -m_ref as a C operand needs log2-domain products
   const float sl2 = q_prescaled ? 1.0f : scale * ATT_LOG2E;       // pre-scaled q: the products are log2-domain scores already
+  enh_note_kernel(fam == 5 ? "attn_fwd_pre_kernel" : "attn_fwd_kernel", dtype);
   if (fam == 5) ENH_DT_DISPATCH(dtype, (attn_fwd_pre_kernel<OT><<<grid, 256, 0, (hipStream_t)stream>>>(qkv, B, N, H, out, lse)));
   else ENH_DT_DISPATCH(dtype, (attn_fwd_kernel<OT><<<grid, 256, 0, (hipStream_t)stream>>>(qkv, B, N, H, sl2, out, lse)));
   return enh_check_launch("enh_attention_forward");

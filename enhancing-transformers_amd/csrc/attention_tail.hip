@@ -10,6 +10,7 @@
 int enh_attention_tail_forward(const enh_h16* qkv, int B, int N, int H, float scale, int q_prescaled, enh_h16* out, float* lse, int dtype, void* stream) {
   const int64_t nblk = (N + 127) / 128, heads = (int64_t)B * H;
   const dim3 grid((unsigned)(((heads + 7) / 8) * 8 * nblk));  // 1-D: see att_block_coords
+  enh_note_kernel(q_prescaled ? "attn_fwd_tail_pre_kernel" : "attn_fwd_tail_kernel", dtype);
   if (q_prescaled) ENH_DT_DISPATCH(dtype, (attn_fwd_tail_pre_kernel<OT><<<grid, 256, 0, (hipStream_t)stream>>>(qkv, B, N, H, out, lse)));
   else ENH_DT_DISPATCH(dtype, (attn_fwd_tail_kernel<OT><<<grid, 256, 0, (hipStream_t)stream>>>(qkv, B, N, H, scale * ATT_LOG2E, out, lse)));
   return enh_check_launch("enh_attention_forward");

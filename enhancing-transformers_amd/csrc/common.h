@@ -28,6 +28,9 @@ typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4_t;
 
 void enh_set_error(const char* fmt, ...);
 int enh_check_launch(const char* what);
+// what enh_last_kernel() names (gemm.hip, beside the GEMM's own record): `name` is a string literal, the kernel template whose one argument is the operand
+// type of `dtype`.  The launch path stores the two words per thread and formats nothing.
+void enh_note_kernel(const char* name, int dtype);
 int enh_zero_f32_launch(float* p, int64_t n, hipStream_t s);   // p[0..n) = 0 as a kernel launch (graph-safe; see common.cpp)
 #define ENH_MAX_DEVICES 64
 int enh_current_device();   // hipGetDevice of the calling thread, clamped to [0, ENH_MAX_DEVICES)

@@ -143,10 +143,11 @@ static bool gemm_persistent(const GemmPlan& pl, int trans_a, int64_t K, int mode
   return mode == EPI_BF16 || mode == EPI_BF16_BIAS_TANH || mode == EPI_BF16_DTANH || mode == EPI_F32_BIAS_RES || mode == EPI_F32;
 }
 
-// ... and, of those, the A-in-registers form: bf16 / bf16 + bias + tanh / f32 outputs, an even number (>= 6) of K stages
+// ... and, of those, the A-in-registers form: bf16 / bf16 + bias + tanh / f32 outputs and the x3 split epilogues, an even number (>= 6) of K stages
 static bool gemm_regstaged(int64_t K, int mode) {
   const int64_t nst = K / G_BK;
-  return g_kernel_override != 8 && (mode == EPI_BF16 || mode == EPI_BF16_BIAS_TANH || mode == EPI_F32) && nst % 2 == 0 && nst >= 6;
+  return g_kernel_override != 8 && (mode == EPI_BF16 || mode == EPI_BF16_BIAS_TANH || mode == EPI_F32 || mode == EPI_BF16_SPLIT || mode == EPI_BF16_TANH_SPLIT) &&
+         nst % 2 == 0 && nst >= 6;
 }
 
 extern "C" const char* enh_gemm_h16_variant_mode(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, int epi_mode) {
@@ -165,6 +166,49 @@ extern "C" size_t enh_gemm_h16_workspace_bytes(int trans_a, int trans_b, int64_t
   const GemmPlan p1 = gemm_plan(trans_a, trans_b, M, N, K, 1), p2 = gemm_plan(trans_a, trans_b, M, N, K, 2);   // (either kind of split: the caller sizes once)
   const int splits = p1.splits > p2.splits ? p1.splits : p2.splits;
   return splits > 1 ? (size_t)splits * (size_t)M * (size_t)N * sizeof(float) : 0;
+}
+
+// ---- one route from a call to a launch: every entry point fills its epilogue fields into gemm_args(), plans a GemmLaunch and ends in gemm_enqueue() ----
+// operands, shape, tile order and the tile grid of `family`; one K slice; every epilogue field zero
+static GemmArgs gemm_args(const enh_h16* A, int64_t lda, const enh_h16* B, int64_t ldb, int64_t M, int64_t N, int64_t K, int family) {
+  const int bm = family == 7 ? G4_BM : G_BM, bn = family == 7 ? G4_BN : G_BN;
+  GemmArgs g = {};
+  g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
+  if (g_grp_rows > 0) { g.grp_rows = g_grp_rows; g.col_fast = g_col_fast; }
+  else { g.col_fast = K >= 2048 ? 1 : 0; g.grp_rows = g.col_fast ? 4 : 8; }
+  g.nbm = (int)((M + bm - 1) / bm);
+  g.nbn = (int)((N + bn - 1) / bn);
+  g.k_per_split = (K + G_BK - 1) / G_BK * G_BK;
+  g.splits = 1;
+  return g;
+}
+// persistent form of the w256 family: one workgroup per CU walks the tiles; L.mode chooses between w256p and w256r
+static int gemm_make_persistent(GemmArgs& g, GemmLaunch& L, const char* what) {
+  const int64_t tiles = (int64_t)g.nbm * g.nbn, n_cu = cu_budget();
+  const int64_t wgs = tiles < n_cu ? tiles : n_cu;
+  L.dyn = g_dyn_schedule && wgs >= 8 ? 1 : 0;     // (every XCD queue needs a workgroup that serves it)
+  if (L.dyn) {
+    g.tile_ctr = next_tile_counters();
+    ENH_REQUIRE(g.tile_ctr, ENH_E_BADARG, "%s: tile counters unavailable", what);
+  }
+  L.form = gemm_regstaged(g.K, L.mode) ? 2 : 1;
+  L.grid = (unsigned)wgs;
+  return ENH_OK;
+}
+// the main kernel of the thread's most recent timed entry point: a copy of the GEMM's launch record, or a literal's address (attention), plus the dtype
+static thread_local struct { const char* name; int dtype; GemmLaunch gemm; } g_last = {};
+void enh_note_kernel(const char* name, int dtype) { g_last.name = name; g_last.dtype = dtype; }
+extern "C" const char* enh_last_kernel(void) {
+  static thread_local char buf[96];
+  buf[0] = 0;
+  if (g_last.name) snprintf(buf, sizeof(buf), "%s<%s>", g_last.name, g_last.dtype == ENH_DT_F16 ? "F16" : "BF16");
+  else if (g_last.gemm.grid) ENH_DT_DISPATCH(g_last.dtype, (gemm_launch_name<OT>(g_last.gemm, buf, sizeof(buf))));
+  return buf;
+}
+// launch, and remember what was launched
+static void gemm_enqueue(const GemmArgs& g, const GemmLaunch& L, int dtype, hipStream_t s) {
+  if (dtype == ENH_DT_F16) gemm_launch<F16>(g, L, s); else gemm_launch<BF16>(g, L, s);
+  g_last.name = nullptr; g_last.dtype = dtype; g_last.gemm = L;
 }
 
 // colpart != null: the caller (enh_gemm_bf16_dtanh_colsum) has checked that the persistent tanh' kernel serves this call
@@ -191,20 +235,11 @@ static int gemm_h16_impl(const enh_h16* A, int64_t lda, int trans_a, const enh_h
   if (split_kind == 2 && pl.splits > 1 && workspace_bytes < (size_t)pl.splits * (size_t)M * (size_t)N * sizeof(float))
     pl = gemm_plan(trans_a, trans_b, M, N, K, 0);      // (the forward kind is an optimisation: a workspace sized for something else means "do not split")
   const int family = pl.family;
-  const int bm = family == 7 ? G4_BM : G_BM;
-  const int bn = family == 7 ? G4_BN : G_BN;
 
-  GemmArgs g;
-  g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
+  GemmArgs g = gemm_args(A, lda, B, ldb, M, N, K, family);
   g.bias = bias; g.act = act; g.aux = aux; g.ldaux = ldaux; g.res = res; g.ldres = ldres; g.res_rows = res_rows;
-  g.accumulate = accumulate; g.c_f32 = c_f32; g.c_bf16 = c_bf16; g.ldc = ldc; g.ws = nullptr;
+  g.accumulate = accumulate; g.c_f32 = c_f32; g.c_bf16 = c_bf16; g.ldc = ldc;
   g.colpart = colpart;
-  g.c2 = g.c3 = g.clo = nullptr; g.ldc2 = g.ldc3 = g.ldlo = 0;
-  g.tile_ctr = nullptr;
-  if (g_grp_rows > 0) { g.grp_rows = g_grp_rows; g.col_fast = g_col_fast; }
-  else { g.col_fast = K >= 2048 ? 1 : 0; g.grp_rows = g.col_fast ? 4 : 8; }
-  g.nbm = (int)((M + bm - 1) / bm);
-  g.nbn = (int)((N + bn - 1) / bn);
   const int64_t tiles = (int64_t)g.nbm * g.nbn;
   ENH_REQUIRE(tiles < (1ll << 30), ENH_E_SHAPE, "enh_gemm_h16: grid too large");
   g.k_per_split = pl.k_per_split;
@@ -222,28 +257,20 @@ static int gemm_h16_impl(const enh_h16* A, int64_t lda, int trans_a, const enh_h
     }
   }
   hipStream_t s = (hipStream_t)stream;
-  GemmLaunch L;
+  GemmLaunch L = {};
   L.family = family; L.trans_a = trans_a ? 1 : 0; L.trans_b = trans_b ? 1 : 0;
-  L.mode = epi_mode(g); L.form = 0; L.dyn = 0; L.lab = 0;
+  L.mode = epi_mode(g);
   L.grid = (unsigned)(tiles * pl.splits);
   if (family == 7) {
     if (g_w256_lab && dtype == ENH_DT_BF16 && trans_a && trans_b && L.mode == EPI_WS) L.lab = g_w256_lab;   // measurement only (enh_debug_gemm_lab)
     // (the persistent epilogues use 16-byte accesses everywhere: operands that only meet the API's weaker alignment rules take the one-tile kernel)
     const bool p_aligned = aligned16(c_bf16) && aligned16(aux) && aligned16(res) && aligned16(bias) && (!c_bf16 || ldc % 8 == 0) && (!aux || ldaux % 8 == 0);
     if (!L.lab && gemm_persistent(pl, trans_a, K, L.mode) && (!res || res_rows == M) && p_aligned) {
-      // persistent form: one workgroup per CU walks the tiles
-      const int n_cu = cu_budget();
-      const int64_t wgs = tiles < n_cu ? tiles : n_cu;
-      L.dyn = g_dyn_schedule && wgs >= 8 ? 1 : 0;     // (every XCD queue needs a workgroup that serves it)
-      if (L.dyn) {
-        g.tile_ctr = next_tile_counters();
-        ENH_REQUIRE(g.tile_ctr, ENH_E_BADARG, "enh_gemm_h16: tile counters unavailable");
-      }
-      L.form = gemm_regstaged(K, L.mode) ? 2 : 1;
-      L.grid = (unsigned)wgs;
+      const int rc = gemm_make_persistent(g, L, "enh_gemm_h16");
+      if (rc) return rc;
     }
   }
-  if (dtype == ENH_DT_F16) gemm_launch<F16>(g, L, s); else gemm_launch<BF16>(g, L, s);
+  gemm_enqueue(g, L, dtype, s);
   if (two_pass) {
     const int64_t MN = M * N;
     const dim3 rg((unsigned)((MN / 4 + 255) / 256));
@@ -322,26 +349,14 @@ extern "C" int enh_gemm_bf16_split(const enh_h16* A, int64_t lda, const enh_h16*
   ENH_REQUIRE((act == ENH_ACT_NONE && !bias) || (act == ENH_ACT_TANH && bias), ENH_E_BADARG, "enh_gemm_bf16_split: plain (no bias) or bias + tanh");
   ENH_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ldhi % 8 == 0 && ldlo % 8 == 0 && (!hi2 || ldhi2 % 8 == 0) && (!hi3 || ldhi3 % 8 == 0) && aligned16(A) && aligned16(B) &&
               aligned16(hi) && aligned16(lo) && aligned16(hi2) && aligned16(hi3) && aligned16(bias), ENH_E_SHAPE, "enh_gemm_bf16_split: 16-byte alignment / ld %% 8");
-  GemmArgs g;
-  g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.M = M; g.N = N; g.K = K;
-  g.bias = bias; g.act = act; g.aux = nullptr; g.ldaux = 0; g.res = nullptr; g.ldres = 0; g.res_rows = 0;
-  g.accumulate = 0; g.c_f32 = nullptr; g.c_bf16 = hi; g.ldc = ldhi; g.ws = nullptr; g.colpart = nullptr;
+  GemmArgs g = gemm_args(A, lda, B, ldb, M, N, K, 7);
+  g.bias = bias; g.act = act; g.c_bf16 = hi; g.ldc = ldhi;
   g.c2 = hi2; g.ldc2 = ldhi2; g.c3 = hi3; g.ldc3 = ldhi3; g.clo = lo; g.ldlo = ldlo;
-  g.tile_ctr = nullptr;
-  if (g_grp_rows > 0) { g.grp_rows = g_grp_rows; g.col_fast = g_col_fast; }
-  else { g.col_fast = K >= 2048 ? 1 : 0; g.grp_rows = g.col_fast ? 4 : 8; }
-  g.nbm = (int)(M / 256); g.nbn = (int)(N / 256);
-  g.k_per_split = K; g.splits = 1;
-  const int64_t tiles = (int64_t)g.nbm * g.nbn;
-  const int64_t nst_ = K / G_BK;
-  const int regst = (g_kernel_override != 8 && nst_ % 2 == 0 && nst_ >= 6) ? 1 : 0;
-  const int n_cu = cu_budget();
-  const int64_t wgs = tiles < n_cu ? tiles : n_cu;
-  const int dyn = g_dyn_schedule && wgs >= 8 ? 1 : 0;
-  if (dyn) {
-    g.tile_ctr = next_tile_counters();
-    ENH_REQUIRE(g.tile_ctr, ENH_E_BADARG, "enh_gemm_bf16_split: tile counters unavailable");
-  }
-  gemm_split_launch_bf16(g, regst, dyn, act == ENH_ACT_TANH ? 1 : 0, (unsigned)wgs, (hipStream_t)stream);
+  GemmLaunch L = {};
+  L.family = 7;
+  L.mode = act == ENH_ACT_TANH ? EPI_BF16_TANH_SPLIT : EPI_BF16_SPLIT;
+  const int rc = gemm_make_persistent(g, L, "enh_gemm_bf16_split");
+  if (rc) return rc;
+  gemm_enqueue(g, L, ENH_DT_BF16, (hipStream_t)stream);
   return enh_check_launch("enh_gemm_bf16_split");
 }

@@ -2,3 +2,4 @@
 #include "gemm_kernels.h"
 
 template void gemm_launch<F16>(const GemmArgs&, const GemmLaunch&, hipStream_t);
+template void gemm_launch_name<F16>(const GemmLaunch&, char*, size_t);

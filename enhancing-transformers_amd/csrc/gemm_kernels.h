@@ -939,8 +939,33 @@ void gemm_launch(const GemmArgs& g, const GemmLaunch& L, hipStream_t s) {
 #undef W2_LAB_GO
     return;
   }
+  if constexpr (OT::id == 0) if (L.mode >= EPI_BF16_SPLIT) {   // the x3 split epilogues: bf16 operands, B stored [N][K], persistent forms only
+    static const gemm_fn stable[2][2][2] = {   // [form - 1][dyn][mode - EPI_BF16_SPLIT]
+        {{gemm_w256p_kernel<BF16, false, false, EPI_BF16_SPLIT, false>, gemm_w256p_kernel<BF16, false, false, EPI_BF16_TANH_SPLIT, false>},
+         {gemm_w256p_kernel<BF16, false, false, EPI_BF16_SPLIT, true>, gemm_w256p_kernel<BF16, false, false, EPI_BF16_TANH_SPLIT, true>}},
+        {{gemm_w256r_kernel<BF16, false, EPI_BF16_SPLIT, false>, gemm_w256r_kernel<BF16, false, EPI_BF16_TANH_SPLIT, false>},
+         {gemm_w256r_kernel<BF16, false, EPI_BF16_SPLIT, true>, gemm_w256r_kernel<BF16, false, EPI_BF16_TANH_SPLIT, true>}}};
+    static const bool s_attr = [] {
+      for (int i = 0; i < 8; ++i) (void)hipFuncSetAttribute(reinterpret_cast<const void*>((&stable[0][0][0])[i]), hipFuncAttributeMaxDynamicSharedMemorySize, W2P_LDS_BYTES);
+      return true;
+    }();
+    (void)s_attr;
+    hipLaunchKernelGGL(stable[L.form - 1][L.dyn][L.mode - EPI_BF16_SPLIT], grid, dim3(256), (size_t)W2P_LDS_BYTES, s, g);
+    return;
+  }
   const int prow = 2 * L.dyn + (L.trans_b ? 1 : 0);
   if (L.form == 2) hipLaunchKernelGGL(rtable[prow][L.mode], grid, dim3(256), (size_t)W2P_LDS_BYTES, s, g);
   else if (L.form == 1) hipLaunchKernelGGL(ptable[prow][L.mode], grid, dim3(256), (size_t)(L.mode == EPI_BF16_DTANH ? W2P_LDS_BYTES_DTANH : W2P_LDS_BYTES), s, g);
   else hipLaunchKernelGGL(table[layout][L.mode], grid, dim3(256), (size_t)(2 * W2_SLOT + W2_BIAS_BYTES), s, g);
+}
+
+// The symbol of the kernel gemm_launch<OT> enqueues for L, composed from the fields that index its tables.
+template <typename OT>
+void gemm_launch_name(const GemmLaunch& L, char* buf, size_t n) {
+  const char *ot = OT::id == 0 ? "BF16" : "F16", *ta = L.trans_a ? "true" : "false", *tb = L.trans_b ? "true" : "false", *dyn = L.dyn ? "true" : "false";
+  if (L.family != 7) snprintf(buf, n, "%s<%s, %s, %s>", L.family == 3 ? "gemm_pipe2_kernel" : "gemm_kernel", ot, ta, tb);
+  else if (OT::id == 0 && L.lab) snprintf(buf, n, "gemm_w256_lab_kernel<%d>", L.lab);
+  else if (L.form == 2) snprintf(buf, n, "gemm_w256r_kernel<%s, %s, %d, %s>", ot, tb, L.mode, dyn);
+  else if (L.form == 1) snprintf(buf, n, "gemm_w256p_kernel<%s, false, %s, %d, %s>", ot, tb, L.mode, dyn);
+  else snprintf(buf, n, "gemm_w256_kernel<%s, %s, %s, %d>", ot, ta, tb, L.mode);
 }

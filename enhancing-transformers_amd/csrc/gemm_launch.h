@@ -8,7 +8,7 @@
 struct GemmLaunch {
   int family;            // 0 = register-staged fallback, 3 = pipe2 (128 x 128), 7 = w256 (256 x 256)
   int trans_a, trans_b;
-  int mode;              // EPI_* of the call (w256 family: a template parameter of the kernel)
+  int mode;              // EPI_* of the call (w256 family: a template parameter of the kernel; the x3 split modes: bf16, persistent forms, trans_b = 0 only)
   int form;              // w256 family: 0 = one tile per workgroup, 1 = persistent (w256p), 2 = persistent with A staged through registers (w256r)
   int dyn;               // persistent forms: 1 = tiles claimed from the per-XCD queues, 0 = static partition
   unsigned grid;         // workgroups
@@ -17,5 +17,6 @@ struct GemmLaunch {
 // enqueue the kernel the plan names on `s` (no error check: the caller ends with enh_check_launch)
 template <typename OT>
 void gemm_launch(const GemmArgs& g, const GemmLaunch& L, hipStream_t s);
-// the x3 split epilogues (bf16 only): [A-in-registers form][schedule][plain | bias + tanh]
-void gemm_split_launch_bf16(const GemmArgs& g, int regstaged, int dyn, int tanh_mode, unsigned wgs, hipStream_t s);
+// ... and that kernel's symbol as a profiler prints it (template arguments, no parameter list), for enh_last_kernel()
+template <typename OT>
+void gemm_launch_name(const GemmLaunch& L, char* buf, size_t n);

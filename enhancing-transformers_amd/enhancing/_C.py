@@ -5,6 +5,9 @@ contiguity (the reference's native ops do the same with CHECK_CUDA / CHECK_CONTI
 enhancing/losses/op/fused_bias_act.cpp:9-15), passes raw ``data_ptr()`` values plus the current HIP
 stream, and raises ``RuntimeError`` with ``enh_last_error()`` on a non-zero return code.
 
+Timing labels (``KernelTimer``) of the GEMM and attention-forward calls are not worked out here: the library names the kernel it launched
+(``enh_last_kernel()``), so the planner in csrc/gemm.hip has no second copy on this side.
+
 There is NO fallback: if the shared library is missing or a tensor is not on a ROCm device the call
 fails loudly.
 """
@@ -31,6 +34,7 @@ _vp, _i64, _i32, _f32, _sz = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_float, _c.c
 # name -> (restype, argtypes); must list every symbol include/enh_hip.h declares (checked by tests)
 SIGNATURES = {
     "enh_last_error": (_c.c_char_p, []),
+    "enh_last_kernel": (_c.c_char_p, []),
     "enh_abi_version": (_i32, []),
     "enh_vq_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "enh_vq_workspace_bytes_d": (_sz, [_i64, _i32, _i32, _i32]),
@@ -117,7 +121,7 @@ SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 18  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 19  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -148,13 +152,11 @@ def lib():
         if sched:
             if sched not in ("static", "dynamic") or L.enh_gemm_set_scheduler(int(sched == "dynamic")) != 0:
                 raise RuntimeError(f"ENH_GEMM_SCHEDULER={sched!r}: expected static | dynamic")
-            _DYN_SCHEDULE[0] = sched == "dynamic"
         att = os.environ.get("ENH_ATTN_KERNEL")       # "fwd,dq,dkv" families, e.g. "1,1,1" (0 = library default; include/enh_hip.h enh_attention_set_kernel)
         if att:
             f, q, k = (int(x) for x in att.split(","))
             if L.enh_attention_set_kernel(f, q, k) != 0:
                 raise RuntimeError(L.enh_last_error().decode())
-            _ATT_FAMILY[:] = [f, q, k]
         conv = os.environ.get("ENH_CONV_KERNEL")      # A/B: "reg" register-staged everywhere | "t128" no 256-row kernels | "t256" 256-row wherever the shape allows
         if conv:
             if conv not in CONV_KERNELS or L.enh_conv_set_kernel(CONV_KERNELS[conv]) != 0:
@@ -205,11 +207,14 @@ class KernelTimer:
         self.records = {}
         self.units = {}      # name -> "flop" (bf16 MFMA work), "flop_f32" (exact-f32 MFMA work) or "byte" (algorithmic HBM bytes)
 
-    def run(self, name: str, work: float, fn, unit: str = "flop") -> None:
+    def run(self, name: Optional[str], work: float, fn, unit: str = "flop") -> None:
+        """name=None: the label is the symbol of the kernel the library launched in fn() (enh_last_kernel), asked for outside the event pair"""
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
         fn()
         e.record()
+        if name is None:
+            name = lib().enh_last_kernel().decode()
         self.records.setdefault(name, []).append((s, e, work))
         self.units[name] = unit
 
@@ -225,7 +230,7 @@ class KernelTimer:
 TIMER: Optional[KernelTimer] = None
 
 
-def _timed(name: str, work: float, fn, unit: str = "flop") -> None:
+def _timed(name: Optional[str], work: float, fn, unit: str = "flop") -> None:
     if TIMER is None:
         fn()
     else:
@@ -356,22 +361,7 @@ def gemm(a, b, M: int, N: int, K: int, trans_a: bool = False, trans_b: bool = Fa
             act, _p(aux, H16, "aux"), aux.stride(0) if aux is not None else 0, _p(res, F32, "res"),
             res.stride(0) if res is not None else 0, res_rows if res is not None else 0, int(accumulate),
             _p(out_f32, F32, "out_f32"), _p(out_bf16, H16, "out_bf16"), ldc, _p(ws), ws_bytes if ws is not None else 0, dt, _stream())
-    if TIMER is None:
-        _check(lib().enh_gemm_h16_ws(*args), "enh_gemm_h16")
-    else:  # label with the symbol rocprofv3 will report, e.g. "gemm_pipe2_kernel<BF16, false, true>" / "gemm_w256_kernel<F16, false, false, 1>"
-        mode = _epi_mode_label(accumulate, ws is not None, out_f32 is not None, out_bf16 is not None, bias is not None, act, res is not None)
-        # (a position-table residual, res_rows != M, is not the persistent kernel's case: ask with the generic mode)
-        fam = lib().enh_gemm_h16_variant_mode(int(trans_a), int(trans_b), M, N, K, 0 if (res is not None and res_rows != M) else mode).decode()
-        ot = _OT_NAME[dt]                                   # the kernels' first template argument: the operand type tag (csrc/common.h)
-        targs = f"{ot}, {'true' if trans_a else 'false'}, {'true' if trans_b else 'false'}"
-        dyn = "true" if _DYN_SCHEDULE[0] else "false"      # the persistent kernels' last template argument: the tile schedule (gemm_kernels.h DYN)
-        if fam == "gemm_w256r_kernel":   # template <OT, TB, EPI, DYN>: A is never transposed there
-            targs = f"{ot}, {'true' if trans_b else 'false'}, {mode}, {dyn}"
-        elif fam == "gemm_w256p_kernel":
-            targs += f", {mode}, {dyn}"
-        elif fam == "gemm_w256_kernel":   # the epilogue mode is a template parameter (gemm_tiles.h epi_mode(), mirrored here for the label only)
-            targs += f", {mode}"
-        TIMER.run(f"{fam}<{targs}>", 2.0 * M * N * K, lambda: _check(lib().enh_gemm_h16_ws(*args), "enh_gemm_h16"))
+    _timed(None, 2.0 * M * N * K, lambda: _check(lib().enh_gemm_h16_ws(*args), "enh_gemm_h16"))
 
 
 def gemm_dtanh_colsum(a, b, M: int, N: int, K: int, aux, out_bf16, colsum_out, trans_b: bool = True, accumulate_colsum: bool = True):
@@ -382,14 +372,8 @@ def gemm_dtanh_colsum(a, b, M: int, N: int, K: int, aux, out_bf16, colsum_out, t
     dt = _dt(a, b, aux, out_bf16)
     args = (_p(a, H16, "A"), a.stride(0), _p(b, H16, "B"), b.stride(0), int(trans_b), M, N, K, _p(aux, H16, "aux"), aux.stride(0),
             _p(out_bf16, H16, "out_bf16"), out_bf16.stride(0), _p(colsum_out, F32, "colsum"), int(accumulate_colsum), _p(ws), ws.numel(), dt, _stream())
-    call = lambda: _check(lib().enh_gemm_h16_dtanh_colsum(*args), "enh_gemm_h16_dtanh_colsum")
-    if TIMER is None:
-        call()
-    else:   # labelled with the GEMM kernel's symbol (the partial-row second pass and, off the tile grid, the column-sum kernel ride along)
-        fam = lib().enh_gemm_h16_variant_mode(0, int(trans_b), M, N, K, 3).decode()
-        dyn = ", true>" if _DYN_SCHEDULE[0] else ", false>"
-        TIMER.run(f"{fam}<{_OT_NAME[dt]}, false, {'true' if trans_b else 'false'}" + ((", 3" + (dyn if fam == "gemm_w256p_kernel" else ">")) if "w256" in fam else ">"),
-                  2.0 * M * N * K, call)
+    # (labelled with the GEMM kernel's symbol: the partial-row second pass and, off the tile grid, the column-sum kernel ride along)
+    _timed(None, 2.0 * M * N * K, lambda: _check(lib().enh_gemm_h16_dtanh_colsum(*args), "enh_gemm_h16_dtanh_colsum"))
 
 
 def set_cu_budget(n: int) -> None:
@@ -415,10 +399,6 @@ def device_cus() -> int:
 _DEVICE_CUS = [None]
 
 
-_OT_NAME = {DT_BF16: "BF16", DT_F16: "F16"}      # operand type tags as they appear in the kernels' symbol names
-_DYN_SCHEDULE = [True]      # mirrors the library's default (enh_gemm_set_scheduler), for timing labels only
-
-
 CONV_KERNELS = {"auto": 0, "reg": 1, "t128": 2, "t256": 3}
 
 
@@ -429,29 +409,12 @@ def conv_set_kernel(name: str) -> None:
 
 def gemm_set_scheduler(dynamic: bool) -> None:
     _check(lib().enh_gemm_set_scheduler(int(bool(dynamic))), "enh_gemm_set_scheduler")
-    _DYN_SCHEDULE[0] = bool(dynamic)
 
 
 def occupy_cus(n_wg: int, ms: float, stream=None) -> None:
     """measurement aid: hold n_wg CUs for ms milliseconds on `stream` (a torch stream; default: the current one)"""
     st = ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
     _check(lib().enh_debug_occupy_cus(int(n_wg), float(ms), st), "enh_debug_occupy_cus")
-
-
-def _epi_mode_label(accumulate, have_ws, f32, bf16, bias, act, res) -> int:
-    """EPI_* enum value gemm.hip's epi_mode() selects (0 generic, 1 bf16, 2 bf16+bias+tanh, 3 bf16+dtanh, 4 f32+bias+res, 5 f32, 6 split-K workspace,
-    7 split-K atomics) — used only to label timings with the symbol name a profiler reports"""
-    if accumulate and f32 and not bf16 and not bias and act == ACT_NONE and not res:
-        return 6 if have_ws else 7    # (only when the shape is actually split; an unsplit accumulate call is generic)
-    if not accumulate:
-        if bf16 and not f32:
-            if not bias and act == ACT_NONE and not res: return 1
-            if bias and act == ACT_TANH and not res: return 2
-            if not bias and act == ACT_DTANH and not res: return 3
-        if f32 and not bf16 and act == ACT_NONE:
-            if bias and res: return 4
-            if not bias and not res: return 5
-    return 0
 
 
 _GEMM_WS = {}
@@ -471,26 +434,15 @@ def _gemm_workspace(device, nbytes: int):
 # ------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------
-_ATT_FAMILY = [0, 0, 0]
-
-
 def attention_set_kernel(fwd: int = 0, dq: int = 0, dkv: int = 0) -> None:
     """A/B aid: kernel family per pass (include/enh_hip.h enh_attention_set_kernel)"""
     _check(lib().enh_attention_set_kernel(fwd, dq, dkv), "enh_attention_set_kernel")
-    _ATT_FAMILY[:] = [fwd, dq, dkv]
 
 
 def attention_forward(qkv, B: int, N: int, H: int, scale: float, out, lse, q_prescaled: bool = False):
     """q_prescaled: the q third of qkv holds q * scale * log2(e) (include/enh_hip.h)"""
-    # (labelled with the symbol rocprofv3 reports: family 5 — the default — serves pre-scaled q, family 1 everything else; a token count that is no
-    # multiple of 64 runs the tail form of its q convention whatever family is selected)
-    fam = _ATT_FAMILY[0] or 5
-    if N % 64:
-        name = "attn_fwd_tail_pre_kernel" if q_prescaled else "attn_fwd_tail_kernel"
-    else:
-        name = "attn_fwd_pre_kernel" if (fam == 5 and q_prescaled) else "attn_fwd_kernel"
     dt = _dt(qkv, out)
-    _timed(f"{name}<{_OT_NAME[dt]}>", 4.0 * B * H * N * N * 64,
+    _timed(None, 4.0 * B * H * N * N * 64,
            lambda: _check(lib().enh_attention_forward(_p(qkv, H16, "qkv"), B, N, H, scale, int(q_prescaled), _p(out, H16, "out"), _p(lse, F32, "lse"),
                                                       dt, _stream()), "enh_attention_forward"))
 
@@ -835,20 +787,13 @@ def gemm_split_fused(M: int, N: int, K: int) -> bool:
     return bool(lib().enh_gemm_bf16_split_fused(M, N, K))
 
 
-def _split_label(K: int, mode: int) -> str:
-    """the symbol rocprofv3 reports for an enh_gemm_bf16_split call (the A-in-registers form serves an even number >= 6 of K stages)"""
-    dyn = "true" if _DYN_SCHEDULE[0] else "false"
-    nst = K // 64
-    return f"gemm_w256r_kernel<BF16, false, {mode}, {dyn}>" if (nst % 2 == 0 and nst >= 6) else f"gemm_w256p_kernel<BF16, false, false, {mode}, {dyn}>"
-
-
 def _poff(t: torch.Tensor, elems: int):
     return ctypes.c_void_p(t.data_ptr() + elems * t.element_size())
 
 
 def gemm_split2(a, b, M: int, N: int, K: int, hi, lo):
     """hi = bf16(a b^T), lo = bf16(a b^T - hi): mm(...) -> f32 followed by split2, without the f32 round trip (bit-identical)"""
-    _timed(_split_label(K, 8), 2.0 * M * N * K,
+    _timed(None, 2.0 * M * N * K,
            lambda: _check(lib().enh_gemm_bf16_split(_p(a, BF16, "A"), a.stride(0), _p(b, BF16, "B"), b.stride(0), M, N, K, None, ACT_NONE,
                                                     _p(hi, BF16, "hi"), hi.stride(0), _p(lo, BF16, "lo"), lo.stride(0), None, 0, None, 0, _stream()), "enh_gemm_bf16_split"))
 
@@ -858,7 +803,7 @@ def gemm_split3_tanh(a, b, M: int, N: int, K: int, bias, y3, y_hi=None):
     if not (y3.is_cuda and y3.is_contiguous() and y3.dtype == BF16 and y3.shape[-1] == 3 * N):
         raise RuntimeError("y3 must be a contiguous bf16 [M, 3N] device tensor")
     ld3 = y3.stride(0)
-    _timed(_split_label(K, 9), 2.0 * M * N * K,
+    _timed(None, 2.0 * M * N * K,
            lambda: _check(lib().enh_gemm_bf16_split(_p(a, BF16, "A"), a.stride(0), _p(b, BF16, "B"), b.stride(0), M, N, K, _p(bias, F32, "bias"), ACT_TANH,
                                                     _poff(y3, 0), ld3, _poff(y3, N), ld3, _poff(y3, 2 * N), ld3,
                                                     _p(y_hi, BF16, "y_hi"), y_hi.stride(0) if y_hi is not None else 0, _stream()), "enh_gemm_bf16_split"))

@@ -52,7 +52,13 @@ typedef uint16_t enh_h16;  /* raw 16-bit float bits: bfloat16 or binary16, per t
 typedef enh_h16 enh_bf16;  /* raw bfloat16 bits (bf16-only entries) */
 
 const char* enh_last_error(void);
-#define ENH_ABI_VERSION 18  /* bumped whenever a signature below changes; the bindings check it at load */
+/* The symbol — as a profiler prints it: template arguments, no parameter list, e.g. "gemm_w256r_kernel<F16, false, 2, true>" — of the main kernel that
+ * the calling thread's most recent enh_gemm_h16 / enh_gemm_h16_ws / enh_gemm_h16_dtanh_colsum / enh_gemm_bf16_split / enh_attention_forward call
+ * enqueued: the GEMM or attention kernel, not the helpers that ride along (split-K second pass, column sums).  "" before the first such call.  The
+ * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
+ * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
+const char* enh_last_kernel(void);
+#define ENH_ABI_VERSION 19  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
