@@ -77,8 +77,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmF32Args g) {
   }
 }
 
-// ---- attention, fp32, one thread per query (or key) row; qkv packed [B, N, 3*H*64] like the bf16 path ----
-#define A_D 64
+// ---- attention, fp32, one thread per query (or key) row; qkv packed [B, N, 3*H*D] like the 16-bit path;
+// D = dim_head, a template argument (32 | 64 | 96 | 128: enh_attention_*_f32_dh) ----
+template <int A_D>
 __global__ __launch_bounds__(64) void attn_f32_fwd_kernel(const float* __restrict__ qkv, int N, int H, float scale, float* __restrict__ out,
                                                           float* __restrict__ lse) {
   const int b = blockIdx.z, h = blockIdx.y, i = blockIdx.x * 64 + threadIdx.x;
@@ -114,6 +115,7 @@ __global__ __launch_bounds__(64) void attn_f32_fwd_kernel(const float* __restric
   lse[((int64_t)b * H + h) * N + i] = m + logf(l);
 }
 
+template <int A_D>
 __global__ void attn_f32_delta_kernel(const float* __restrict__ o, const float* __restrict__ d_o, int64_t BN, int N, int H, float* __restrict__ delta) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (b*N + q) * H + h
   if (idx >= BN * H) return;
@@ -125,6 +127,7 @@ __global__ void attn_f32_delta_kernel(const float* __restrict__ o, const float* 
 }
 
 // dQ_i = sum_j dS_ij K_j ,  dS_ij = P_ij (dO_i . V_j - delta_i) * scale
+template <int A_D>
 __global__ __launch_bounds__(64) void attn_f32_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o, const float* __restrict__ lse,
                                                          const float* __restrict__ delta, int N, int H, float scale, float* __restrict__ dqkv) {
   const int b = blockIdx.z, h = blockIdx.y, i = blockIdx.x * 64 + threadIdx.x;
@@ -156,6 +159,7 @@ __global__ __launch_bounds__(64) void attn_f32_dq_kernel(const float* __restrict
 }
 
 // dV_j = sum_i P_ij dO_i ; dK_j = sum_i dS_ij Q_i
+template <int A_D>
 __global__ __launch_bounds__(64) void attn_f32_dkv_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o, const float* __restrict__ lse,
                                                           const float* __restrict__ delta, int N, int H, float scale, float* __restrict__ dqkv) {
   const int b = blockIdx.z, h = blockIdx.y, j = blockIdx.x * 64 + threadIdx.x;
@@ -233,22 +237,53 @@ extern "C" int enh_gemm_f32(const float* A, int64_t lda, int trans_a, const floa
   return enh_check_launch("enh_gemm_f32");
 }
 
+template <int D>
+static int attention_forward_f32_d(const float* qkv, int B, int N, int H, float scale, float* out, float* lse, void* stream, const char* what) {
+  attn_f32_fwd_kernel<D><<<dim3((N + 63) / 64, H, B), 64, 0, (hipStream_t)stream>>>(qkv, N, H, scale, out, lse);
+  return enh_check_launch(what);
+}
+template <int D>
+static int attention_backward_f32_d(const float* qkv, const float* out, const float* dout, const float* lse, int B, int N, int H, float scale, float* dqkv,
+                                    float* delta_ws, void* stream, const char* what) {
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t BN = (int64_t)B * N;
+  attn_f32_delta_kernel<D><<<(int)((BN * H + 255) / 256), 256, 0, s>>>(out, dout, BN, N, H, delta_ws);
+  const dim3 grid((N + 63) / 64, H, B);
+  attn_f32_dq_kernel<D><<<grid, 64, 0, s>>>(qkv, dout, lse, delta_ws, N, H, scale, dqkv);
+  attn_f32_dkv_kernel<D><<<grid, 64, 0, s>>>(qkv, dout, lse, delta_ws, N, H, scale, dqkv);
+  return enh_check_launch(what);
+}
+
 extern "C" int enh_attention_forward_f32(const float* qkv, int B, int N, int H, float scale, float* out, float* lse, void* stream) {
   ENH_REQUIRE(qkv && out && lse && B > 0 && N > 0 && H > 0 && scale > 0.f, ENH_E_BADARG, "enh_attention_forward_f32: bad argument");
-  attn_f32_fwd_kernel<<<dim3((N + 63) / 64, H, B), 64, 0, (hipStream_t)stream>>>(qkv, N, H, scale, out, lse);
-  return enh_check_launch("enh_attention_forward_f32");
+  return attention_forward_f32_d<64>(qkv, B, N, H, scale, out, lse, stream, "enh_attention_forward_f32");
 }
 
 extern "C" int enh_attention_backward_f32(const float* qkv, const float* out, const float* dout, const float* lse, int B, int N, int H, float scale,
                                           float* dqkv, float* delta_ws, void* stream) {
   ENH_REQUIRE(qkv && out && dout && lse && dqkv && delta_ws && B > 0 && N > 0 && H > 0 && scale > 0.f, ENH_E_BADARG, "enh_attention_backward_f32: bad argument");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t BN = (int64_t)B * N;
-  attn_f32_delta_kernel<<<(int)((BN * H + 255) / 256), 256, 0, s>>>(out, dout, BN, N, H, delta_ws);
-  const dim3 grid((N + 63) / 64, H, B);
-  attn_f32_dq_kernel<<<grid, 64, 0, s>>>(qkv, dout, lse, delta_ws, N, H, scale, dqkv);
-  attn_f32_dkv_kernel<<<grid, 64, 0, s>>>(qkv, dout, lse, delta_ws, N, H, scale, dqkv);
-  return enh_check_launch("enh_attention_backward_f32");
+  return attention_backward_f32_d<64>(qkv, out, dout, lse, B, N, H, scale, dqkv, delta_ws, stream, "enh_attention_backward_f32");
+}
+
+extern "C" int enh_attention_forward_f32_dh(const float* qkv, int B, int N, int H, int D, float scale, float* out, float* lse, void* stream) {
+  ENH_REQUIRE(D == 32 || D == 64 || D == 96 || D == 128, ENH_E_SHAPE, "enh_attention_forward_f32_dh: dim_head must be 32, 64, 96 or 128, got %d", D);
+  ENH_REQUIRE(qkv && out && lse && B > 0 && N > 0 && H > 0 && scale > 0.f, ENH_E_BADARG, "enh_attention_forward_f32_dh: bad argument");
+  const char* what = "enh_attention_forward_f32_dh";
+  if (D == 32) return attention_forward_f32_d<32>(qkv, B, N, H, scale, out, lse, stream, what);
+  if (D == 64) return attention_forward_f32_d<64>(qkv, B, N, H, scale, out, lse, stream, what);
+  if (D == 96) return attention_forward_f32_d<96>(qkv, B, N, H, scale, out, lse, stream, what);
+  return attention_forward_f32_d<128>(qkv, B, N, H, scale, out, lse, stream, what);
+}
+
+extern "C" int enh_attention_backward_f32_dh(const float* qkv, const float* out, const float* dout, const float* lse, int B, int N, int H, int D, float scale,
+                                             float* dqkv, float* delta_ws, void* stream) {
+  ENH_REQUIRE(D == 32 || D == 64 || D == 96 || D == 128, ENH_E_SHAPE, "enh_attention_backward_f32_dh: dim_head must be 32, 64, 96 or 128, got %d", D);
+  ENH_REQUIRE(qkv && out && dout && lse && dqkv && delta_ws && B > 0 && N > 0 && H > 0 && scale > 0.f, ENH_E_BADARG, "enh_attention_backward_f32_dh: bad argument");
+  const char* what = "enh_attention_backward_f32_dh";
+  if (D == 32) return attention_backward_f32_d<32>(qkv, out, dout, lse, B, N, H, scale, dqkv, delta_ws, stream, what);
+  if (D == 64) return attention_backward_f32_d<64>(qkv, out, dout, lse, B, N, H, scale, dqkv, delta_ws, stream, what);
+  if (D == 96) return attention_backward_f32_d<96>(qkv, out, dout, lse, B, N, H, scale, dqkv, delta_ws, stream, what);
+  return attention_backward_f32_d<128>(qkv, out, dout, lse, B, N, H, scale, dqkv, delta_ws, stream, what);
 }
 
 extern "C" int enh_colsum_f32(const float* x, int64_t M, int64_t N, int64_t ldx, float* out, int accumulate, void* stream) {

@@ -62,6 +62,8 @@ SIGNATURES = {
     "enh_attention_set_kernel": (_i32, [_i32, _i32, _i32]),
     "enh_attention_forward": (_i32, [_vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i32, _vp]),
     "enh_attention_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i32, _vp]),
+    "enh_attention_forward_dh": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i32, _vp]),
+    "enh_attention_backward_dh": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i32, _vp]),
     "enh_patchify": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "enh_unpatchify_loss": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "enh_colsum_h16": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _vp]),
@@ -99,6 +101,8 @@ SIGNATURES = {
     "enh_gemm_f32": (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _i64, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp]),
     "enh_attention_forward_f32": (_i32, [_vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
     "enh_attention_backward_f32": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "enh_attention_forward_f32_dh": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "enh_attention_backward_f32_dh": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
     "enh_colsum_f32": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _vp]),
     "enh_patch_perm_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "enh_unpatchify_loss_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
@@ -121,7 +125,7 @@ SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 19  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 20  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -439,20 +443,32 @@ def attention_set_kernel(fwd: int = 0, dq: int = 0, dkv: int = 0) -> None:
     _check(lib().enh_attention_set_kernel(fwd, dq, dkv), "enh_attention_set_kernel")
 
 
-def attention_forward(qkv, B: int, N: int, H: int, scale: float, out, lse, q_prescaled: bool = False):
-    """q_prescaled: the q third of qkv holds q * scale * log2(e) (include/enh_hip.h)"""
+def attention_forward(qkv, B: int, N: int, H: int, scale: float, out, lse, q_prescaled: bool = False, dim_head: int = 64):
+    """q_prescaled: the q third of qkv holds q * scale * log2(e) (include/enh_hip.h).  dim_head: 64 (the tuned kernels, enh_attention_forward) or
+    32 | 96 | 128 (enh_attention_forward_dh); anything else is the library's shape error."""
     dt = _dt(qkv, out)
-    _timed(None, 4.0 * B * H * N * N * 64,
-           lambda: _check(lib().enh_attention_forward(_p(qkv, H16, "qkv"), B, N, H, scale, int(q_prescaled), _p(out, H16, "out"), _p(lse, F32, "lse"),
-                                                      dt, _stream()), "enh_attention_forward"))
+    if dim_head == 64:
+        _timed(None, 4.0 * B * H * N * N * 64,
+               lambda: _check(lib().enh_attention_forward(_p(qkv, H16, "qkv"), B, N, H, scale, int(q_prescaled), _p(out, H16, "out"), _p(lse, F32, "lse"),
+                                                          dt, _stream()), "enh_attention_forward"))
+        return
+    _timed(None, 4.0 * B * H * N * N * dim_head,
+           lambda: _check(lib().enh_attention_forward_dh(_p(qkv, H16, "qkv"), B, N, H, dim_head, scale, int(q_prescaled), _p(out, H16, "out"),
+                                                         _p(lse, F32, "lse"), dt, _stream()), "enh_attention_forward_dh"))
 
 
-def attention_backward(qkv, out, dout, lse, B: int, N: int, H: int, scale: float, dqkv, delta_ws, q_prescaled: bool = False):
+def attention_backward(qkv, out, dout, lse, B: int, N: int, H: int, scale: float, dqkv, delta_ws, q_prescaled: bool = False, dim_head: int = 64):
     dt = _dt(qkv, out, dout, dqkv)
-    _timed("attn_bwd_tail (dq+dkv kernels)" if N % 64 else "attn_bwd (dq+dkv kernels)", 10.0 * B * H * N * N * 64,
-           lambda: _check(lib().enh_attention_backward(_p(qkv, H16, "qkv"), _p(out, H16, "out"), _p(dout, H16, "dout"), _p(lse, F32, "lse"), B, N, H,
-                                                       scale, int(q_prescaled), _p(dqkv, H16, "dqkv"), _p(delta_ws, F32, "delta_ws"), dt, _stream()),
-                          "enh_attention_backward"))
+    if dim_head == 64:
+        _timed("attn_bwd_tail (dq+dkv kernels)" if N % 64 else "attn_bwd (dq+dkv kernels)", 10.0 * B * H * N * N * 64,
+               lambda: _check(lib().enh_attention_backward(_p(qkv, H16, "qkv"), _p(out, H16, "out"), _p(dout, H16, "dout"), _p(lse, F32, "lse"), B, N, H,
+                                                           scale, int(q_prescaled), _p(dqkv, H16, "dqkv"), _p(delta_ws, F32, "delta_ws"), dt, _stream()),
+                              "enh_attention_backward"))
+        return
+    _timed(f"attn_dh_bwd_dq_kernel<{dim_head}> + attn_dh_bwd_dkv_kernel<{dim_head}>", 10.0 * B * H * N * N * dim_head,
+           lambda: _check(lib().enh_attention_backward_dh(_p(qkv, H16, "qkv"), _p(out, H16, "out"), _p(dout, H16, "dout"), _p(lse, F32, "lse"), B, N, H,
+                                                          dim_head, scale, int(q_prescaled), _p(dqkv, H16, "dqkv"), _p(delta_ws, F32, "delta_ws"), dt,
+                                                          _stream()), "enh_attention_backward_dh"))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -750,19 +766,25 @@ def ln_bwd(dy, x, w, mean, rstd, dres, dx, dx_operand, dw, db, dx_colsum=None):
     layernorm_backward(dy, x, w, mean, rstd, dres, dx, dx_operand if dx_operand.dtype in H16 else None, dw, db, dx_colsum)
 
 
-def attn_fwd(qkv, B, N, H, scale, out, lse, q_prescaled: bool = False):
+def attn_fwd(qkv, B, N, H, scale, out, lse, q_prescaled: bool = False, dim_head: int = 64):
     if qkv.dtype in H16:
-        attention_forward(qkv, B, N, H, scale, out, lse, q_prescaled)
-    else:
+        attention_forward(qkv, B, N, H, scale, out, lse, q_prescaled, dim_head)
+    elif dim_head == 64:
         _check(lib().enh_attention_forward_f32(_p(qkv, F32, "qkv"), B, N, H, scale, _p(out, F32, "out"), _p(lse, F32, "lse"), _stream()), "enh_attention_forward_f32")
-
-
-def attn_bwd(qkv, out, dout, lse, B, N, H, scale, dqkv, delta_ws, q_prescaled: bool = False):
-    if qkv.dtype in H16:
-        attention_backward(qkv, out, dout, lse, B, N, H, scale, dqkv, delta_ws, q_prescaled)
     else:
+        _check(lib().enh_attention_forward_f32_dh(_p(qkv, F32, "qkv"), B, N, H, dim_head, scale, _p(out, F32, "out"), _p(lse, F32, "lse"), _stream()),
+               "enh_attention_forward_f32_dh")
+
+
+def attn_bwd(qkv, out, dout, lse, B, N, H, scale, dqkv, delta_ws, q_prescaled: bool = False, dim_head: int = 64):
+    if qkv.dtype in H16:
+        attention_backward(qkv, out, dout, lse, B, N, H, scale, dqkv, delta_ws, q_prescaled, dim_head)
+    elif dim_head == 64:
         _check(lib().enh_attention_backward_f32(_p(qkv, F32, "qkv"), _p(out, F32, "out"), _p(dout, F32, "dout"), _p(lse, F32, "lse"), B, N, H, scale,
                                                 _p(dqkv, F32, "dqkv"), _p(delta_ws, F32, "delta_ws"), _stream()), "enh_attention_backward_f32")
+    else:
+        _check(lib().enh_attention_backward_f32_dh(_p(qkv, F32, "qkv"), _p(out, F32, "out"), _p(dout, F32, "dout"), _p(lse, F32, "lse"), B, N, H, dim_head,
+                                                   scale, _p(dqkv, F32, "dqkv"), _p(delta_ws, F32, "delta_ws"), _stream()), "enh_attention_backward_f32_dh")
 
 
 # ------------------------------------------------------------------------------------------------

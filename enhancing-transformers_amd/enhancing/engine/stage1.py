@@ -129,11 +129,12 @@ def backward_unit_order(enc_depth: int, dec_depth: int) -> List[str]:
 class _Tower:
     """One pre-norm transformer stack (reference layers.py:135-150) as a static kernel schedule."""
 
-    def __init__(self, store: ParamStore, prefix: str, dim: int, depth: int, heads: int, mlp: int, n_tok: int) -> None:
+    def __init__(self, store: ParamStore, prefix: str, dim: int, depth: int, heads: int, mlp: int, n_tok: int, dim_head: int = 64) -> None:
         self.s, self.prefix = store, prefix
         self.dim, self.depth, self.heads, self.mlp, self.n_tok = dim, depth, heads, mlp, n_tok
-        self.inner = heads * 64
-        self.scale = 64 ** -0.5
+        self.dim_head = dim_head      # per tower: 64 runs the tuned attention kernels, 32 | 96 | 128 the attn_dh_* family (include/enh_hip.h)
+        self.inner = heads * dim_head
+        self.scale = dim_head ** -0.5
         self._bufs: Dict[Tuple[int, bool], dict] = {}
         t = prefix + "transformer."
         self.L = []
@@ -228,10 +229,17 @@ class _Tower:
                             xf3=e(M, 3 * self.dim))
         return cache[B]
 
+    def require_x3(self, what: str = "precision") -> None:
+        """the split-bf16 attention (csrc/x3.hip) is a dim_head = 64 kernel: an explicit x3 request for a tower of another width is an error, never a silent single pass"""
+        if self.dim_head != 64:
+            raise ValueError(f"{what}='x3': the x3 (split-bf16) attention exists for dim_head = 64 only, the {self.prefix.rstrip('.')} has dim_head = "
+                             f"{self.dim_head}; use the engine's single-pass precision (or precision='fp32' for parity runs)")
+
     def forward_x3(self, B: int, save: bool, want_f32: bool = False) -> dict:
         """forward() with every product formed from split-bf16 operands (reference layers.py:118-132,145-150 in ~fp32 precision on the bf16 matrix
         cores).  With save=True the arena receives exactly what the bf16 forward would have saved (the hi planes), so backward() is unchanged —
         except that q is NOT pre-scaled here (recorded in the buffer dict)."""
+        self.require_x3()
         s, b, X, W3 = self.s, self.bufs(B, save), self.x3_bufs(B), self.x3_weights()
         if s.precision != "bf16" and save:
             raise RuntimeError("the x3 forward saves bf16 hi planes for a bf16 backward: training with an x3 tower needs precision='bf16'")
@@ -279,7 +287,7 @@ class _Tower:
             A = b["layers"][i if save else 0]
             _C.ln_fwd(x, s.w[P["ln1_w"]], s.w[P["ln1_b"]], A["a1"], A["mean1"], A["rstd1"])
             _C.mm(A["a1"], self.wqkv_fwd[i] if self.q_prescaled else s.wa[P["wqkv"]], M, 3 * inner, dim, A["qkv"])
-            _C.attn_fwd(A["qkv"], B, self.n_tok, self.heads, self.scale, A["o"], A["lse"], self.q_prescaled)
+            _C.attn_fwd(A["qkv"], B, self.n_tok, self.heads, self.scale, A["o"], A["lse"], self.q_prescaled, dim_head=self.dim_head)
             _C.mm(A["o"], s.wa[P["wout"]], M, dim, inner, A["x_mid"], bias=s.w[P["bout"]], res=x, res_rows=M)
             _C.ln_fwd(A["x_mid"], s.w[P["ln2_w"]], s.w[P["ln2_b"]], A["a2"], A["mean2"], A["rstd2"])
             _C.mm(A["a2"], s.wa[P["w1"]], M, mlp, dim, A["hid"], bias=s.w[P["b1"]], act=_C.ACT_TANH)
@@ -323,7 +331,7 @@ class _Tower:
             # ---- attention: x_mid = to_out(attn(to_qkv(a1))) + x_in ----
             _C.mm(gB16, A["o"], dim, inner, M, g[P["wout"]], trans_a=True, trans_b=True, accumulate=True)
             _C.mm(gB16, s.wa[P["wout"]], M, inner, dim, b["do16"], trans_b=True)
-            _C.attn_bwd(A["qkv"], A["o"], b["do16"], A["lse"], B, self.n_tok, self.heads, self.scale, b["dqkv16"], b["delta"], q_pre)
+            _C.attn_bwd(A["qkv"], A["o"], b["do16"], A["lse"], B, self.n_tok, self.heads, self.scale, b["dqkv16"], b["delta"], q_pre, dim_head=self.dim_head)
             _C.mm(b["dqkv16"], A["a1"], 3 * inner, dim, M, g[P["wqkv"]], trans_a=True, trans_b=True, accumulate=True)
             _C.mm(b["dqkv16"], s.wa[P["wqkv"]], M, dim, 3 * inner, dA, trans_b=True)
             _C.ln_bwd(dA, b["x"][i], s.w[P["ln1_w"]], A["mean1"], A["rstd1"], gB, gA, gA16, g[P["ln1_w"]], g[P["ln1_b"]],
@@ -423,7 +431,10 @@ class Stage1Engine:
           encoder_precision  "bf16" | "x3": training / reconstruct / forward (ENH_ENCODER_PRECISION, default "bf16": the measured headline path)
           codes_precision    "bf16" | "x3": encode_codes, i.e. the tokens stage 2 consumes (ENH_CODES_PRECISION, default "x3")
           decoder_precision  "bf16" | "x3": post_quant .. to_pixel of training / reconstruct / decode (ENH_DECODER_PRECISION, default "bf16"); with both towers
-                             on x3 the whole forward — codes, reconstruction, losses — is within ~1e-5 of the fp32 reference (the backward stays bf16)"""
+                             on x3 the whole forward — codes, reconstruction, losses — is within ~1e-5 of the fp32 reference (the backward stays bf16)
+        Head width: each tower takes its own dim_head in {32, 64, 96, 128} from its module (layers.py Attention).  x3 is a dim_head = 64 kernel: for a
+        tower of another width an explicit "x3" here (or in the ENH_*_PRECISION variables) is a ValueError, and codes_precision defaults to the engine's
+        single pass also under bf16."""
         import os
         precision = precision or os.environ.get("ENH_PRECISION", "fp16")
         if precision not in OPERAND_DTYPE:
@@ -433,12 +444,18 @@ class Stage1Engine:
         # per-part precision of the forward: "x3" or the engine's own single-pass operand format (spelled as `precision`; "bf16" is accepted as that
         # spelling under fp16 too, for the environment variables of earlier rounds).  Under fp16 the codes default to the single fp16 pass: it meets the
         # 1e-3 clause on its own; x3 stays available as the instrument (encode_codes(precision="x3")).
+        # (x3 is a dim_head = 64 kernel: with another encoder width the default for the codes under bf16 is the engine's single pass, and an explicit x3 is an error below)
+        enc_dh, dec_dh = (getattr(t.transformer, "dim_head", 64) for t in (model.encoder, model.decoder))
         self.encoder_precision = encoder_precision or os.environ.get("ENH_ENCODER_PRECISION", precision)
-        self.codes_precision = codes_precision or os.environ.get("ENH_CODES_PRECISION", "x3" if precision == "bf16" else precision)
+        self.codes_precision = codes_precision or os.environ.get("ENH_CODES_PRECISION", "x3" if precision == "bf16" and enc_dh == 64 else precision)
         self.decoder_precision = decoder_precision or os.environ.get("ENH_DECODER_PRECISION", precision)
         for name, v in (("encoder_precision", self.encoder_precision), ("codes_precision", self.codes_precision), ("decoder_precision", self.decoder_precision)):
             if v not in ("bf16", "fp16", "fp32", "x3"):
                 raise ValueError(f"{name} must be 'x3' or the engine's precision, got {v!r}")
+        for name, v, dh, tower in (("encoder_precision", self.encoder_precision, enc_dh, "encoder"), ("codes_precision", self.codes_precision, enc_dh, "encoder"),
+                                   ("decoder_precision", self.decoder_precision, dec_dh, "decoder")):
+            if v == "x3" and dh != 64:
+                raise ValueError(f"{name}='x3': the x3 (split-bf16) attention exists for dim_head = 64 only, the {tower} has dim_head = {dh}")
         if precision != "bf16" and "x3" in (self.encoder_precision, self.decoder_precision):
             raise ValueError("x3 towers in the TRAINING forward save bf16 hi planes for a bf16 backward: they need precision='bf16' (fp16 meets the tolerance in one pass)")
         self.adt = OPERAND_DTYPE[precision]
@@ -458,8 +475,8 @@ class Stage1Engine:
         self.patch, self.size, self.C = enc.patch_size[0], enc.image_size[0], enc.channels
         self.n_tok = enc.num_patches
         self.pd = enc.patch_dim
-        self.enc = _Tower(self.store, "encoder.", enc.dim, enc.transformer.depth, enc.transformer.heads, enc.transformer.mlp_dim, self.n_tok)
-        self.dec = _Tower(self.store, "decoder.", dec.dim, dec.transformer.depth, dec.transformer.heads, dec.transformer.mlp_dim, self.n_tok)
+        self.enc = _Tower(self.store, "encoder.", enc.dim, enc.transformer.depth, enc.transformer.heads, enc.transformer.mlp_dim, self.n_tok, enc_dh)
+        self.dec = _Tower(self.store, "decoder.", dec.dim, dec.transformer.depth, dec.transformer.heads, dec.transformer.mlp_dim, self.n_tok, dec_dh)
         self.enc.first_bias_grad = self.store.grad["encoder.to_patch_embedding.0.bias"]
         self.dec.first_bias_grad = self.store.grad["post_quant.bias"]
         self.q = q
@@ -539,6 +556,8 @@ class Stage1Engine:
         """patch-embed GEMM (+bias +pos table) -> encoder tower.  reference layers.py:177-182.  x3: on split-bf16 operands (product path only)."""
         B, s, io = img.shape[0], self.store, self._io_bufs(img.shape[0])
         M = B * self.n_tok
+        if x3:
+            self.enc.require_x3()
         if x3 and self.half:
             X = self._x3_io(B)
             _C.patchify_any(img, self.patch, X["patches32"])
@@ -568,6 +587,7 @@ class Stage1Engine:
         pp = self.patch * self.patch
         io["bias_pix"].view(self.C, pp).copy_(s.w["decoder.to_pixel.1.bias"].view(self.C, 1).expand(self.C, pp))
         if zq32 is not None and self.half:
+            self.dec.require_x3("decoder_precision")
             X = self._x3_io(B)
             _C.split3(zq32, X["zq3"])
             _C.mm(X["zq3"], X["wpost"], M, self.dec.dim, 3 * self.ed, self.dec.input_buffer(B, save), bias=s.w["post_quant.bias"],

@@ -87,16 +87,25 @@ class PatchConvParams(nn.Module):
         self.weight, self.bias = donor.weight, donor.bias
 
 
+DIM_HEADS = (32, 64, 96, 128)      # head widths the fused attention kernels are built for (include/enh_hip.h, enh_attention_forward_dh)
+
+
 class Attention(nn.Module):
-    """bias-free to_qkv [3*inner, dim], to_out [dim, inner] + bias; inner = heads * 64 (layers.py:108-120).  The fused kernels take any number of tokens
-    (a multiple of 64 runs the aligned kernels, anything else their tail forms: include/enh_hip.h); only dim_head is fixed."""
+    """bias-free to_qkv [3*inner, dim], to_out [dim, inner] + bias; inner = heads * dim_head, scale = dim_head ** -0.5 (layers.py:108-120).
+    dim_head is 32, 64, 96 or 128: 64 runs the tuned kernels (csrc/attention_kernels.h), the other three the attn_dh_* family (csrc/attention_dh.h);
+    any other width is a ValueError (80 and the other multiples of 16 need padded output blocks).  The fused kernels take any number of tokens.
+    The reference drops to_out when heads == 1 and dim_head == dim (layers.py:112); the engine always projects, so at the new widths that combination
+    is refused rather than given a parameter the reference does not have."""
 
     def __init__(self, dim: int, heads: int = 8, dim_head: int = 64) -> None:
         super().__init__()
-        if dim_head != 64:
-            raise ValueError("the fused gfx950 attention kernel is specialised for dim_head = 64 (every reference config)")
+        if dim_head not in DIM_HEADS:
+            raise ValueError(f"the fused gfx950 attention kernels are built for dim_head in {DIM_HEADS}, got {dim_head}")
+        if dim_head != 64 and heads == 1 and dim_head == dim:
+            raise ValueError("heads == 1 with dim_head == dim has no to_out projection in the reference (layers.py:112); the engine always projects: "
+                             "use more heads or another dim_head")
         inner = dim_head * heads
-        self.heads, self.scale = heads, dim_head ** -0.5
+        self.heads, self.dim_head, self.scale = heads, dim_head, dim_head ** -0.5
         self.to_qkv = LinearParams(dim, inner * 3, bias=False)
         self.to_out = LinearParams(inner, dim)
 
@@ -121,7 +130,7 @@ class Transformer(nn.Module):
 
     def __init__(self, dim: int, depth: int, heads: int, dim_head: int, mlp_dim: int) -> None:
         super().__init__()
-        self.dim, self.depth, self.heads, self.mlp_dim = dim, depth, heads, mlp_dim
+        self.dim, self.depth, self.heads, self.dim_head, self.mlp_dim = dim, depth, heads, dim_head, mlp_dim
         self.layers = nn.ModuleList([
             nn.ModuleList([PreNorm(dim, Attention(dim, heads=heads, dim_head=dim_head)), PreNorm(dim, FeedForward(dim, mlp_dim))])
             for _ in range(depth)])
@@ -135,7 +144,8 @@ def _pair(v) -> Tuple[int, int]:
 class _ViTBase(nn.Module):
     """image_size: any multiple of patch_size (square; patch_size % 4 == 0 for the patch kernels).  The token count N = (image_size / patch_size)^2 is
     free — 224 / 16 (196), 224 / 8 (784), 160 / 8 (400), 96 / 8 (144) run like 256 / 8 (1024).  Training needs B * N % 8 == 0 (the weight-gradient
-    GEMMs contract over the token rows; Stage1Engine raises a ValueError otherwise: N = 196 takes an even batch); inference takes any batch."""
+    GEMMs contract over the token rows; Stage1Engine raises a ValueError otherwise: N = 196 takes an even batch); inference takes any batch.
+    dim_head: 32 | 64 | 96 | 128, per tower (the encoder and the decoder may differ), as in the reference (layers.py:154-155,186-187); see Attention."""
 
     def __init__(self, image_size, patch_size, dim: int, depth: int, heads: int, mlp_dim: int, channels: int, dim_head: int) -> None:
         super().__init__()

@@ -53,12 +53,12 @@ typedef enh_h16 enh_bf16;  /* raw bfloat16 bits (bf16-only entries) */
 
 const char* enh_last_error(void);
 /* The symbol — as a profiler prints it: template arguments, no parameter list, e.g. "gemm_w256r_kernel<F16, false, 2, true>" — of the main kernel that
- * the calling thread's most recent enh_gemm_h16 / enh_gemm_h16_ws / enh_gemm_h16_dtanh_colsum / enh_gemm_bf16_split / enh_attention_forward call
+ * the calling thread's most recent enh_gemm_h16 / enh_gemm_h16_ws / enh_gemm_h16_dtanh_colsum / enh_gemm_bf16_split / enh_attention_forward(_dh) call
  * enqueued: the GEMM or attention kernel, not the helpers that ride along (split-K second pass, column sums).  "" before the first such call.  The
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 19  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 20  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -255,6 +255,19 @@ int enh_attention_set_kernel(int fwd, int dq, int dkv);
  * packed to fp16 before the dQ / dK products. */
 int enh_attention_backward(const enh_h16* qkv, const enh_h16* out, const enh_h16* dout, const float* lse,
                            int B, int N, int H, float scale, int q_prescaled, enh_h16* dqkv, float* delta_ws, int dtype, void* stream);
+/* The same two calls with the head width as an argument D = dim_head — the reference's Attention takes it as a constructor argument
+ * (layers.py:108-120; ViTEncoder / ViTDecoder pass it on, layers.py:154-155,186-187).  Layouts as above with 64 -> D: qkv / dqkv [B,N,3*H*D] packed
+ * q | k | v head-major, out / dout [B,N,H*D], lse / delta_ws [B,H,N] f32; q_prescaled, scale and the meaning of dqkv's q third as above.
+ *   D = 64            forwards to enh_attention_forward / enh_attention_backward: the same kernels (enh_attention_set_kernel, tail forms), the same bits
+ *   D = 32 | 96 | 128 the attn_dh_* kernels (csrc/attention_dh.h): one kernel per pass for ANY N >= 1 and both q conventions — every tile is read with
+ *                     its rows clamped to the image, keys >= N get probability exactly 0, stores are per row; dQ and dK/dV are separate kernels without
+ *                     atomics (bit-reproducible); enh_attention_set_kernel does not apply
+ *   anything else     ENH_E_SHAPE (80 and the other multiples of 16 would need padded output blocks)
+ * The split-bf16 (x3) attention below exists for D = 64 only. */
+int enh_attention_forward_dh(const enh_h16* qkv, int B, int N, int H, int D, float scale, int q_prescaled, enh_h16* out, float* lse,
+                             int dtype, void* stream);
+int enh_attention_backward_dh(const enh_h16* qkv, const enh_h16* out, const enh_h16* dout, const float* lse,
+                              int B, int N, int H, int D, float scale, int q_prescaled, enh_h16* dqkv, float* delta_ws, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * "x3" split-bf16 operands — the parity-grade ENCODER forward (round 4).  The reference's forward is fp32 end to end
@@ -450,6 +463,10 @@ int enh_gemm_f32(const float* A, int64_t lda, int trans_a, const float* B, int64
 int enh_attention_forward_f32(const float* qkv, int B, int N, int H, float scale, float* out, float* lse, void* stream);
 int enh_attention_backward_f32(const float* qkv, const float* out, const float* dout, const float* lse, int B, int N, int H, float scale,
                                float* dqkv, float* delta_ws, void* stream);
+/* the same with dim_head = D in {32, 64, 96, 128} (else ENH_E_SHAPE): the layouts of enh_attention_forward_dh in f32; D = 64 is the kernel above */
+int enh_attention_forward_f32_dh(const float* qkv, int B, int N, int H, int D, float scale, float* out, float* lse, void* stream);
+int enh_attention_backward_f32_dh(const float* qkv, const float* out, const float* dout, const float* lse, int B, int N, int H, int D, float scale,
+                                  float* dqkv, float* delta_ws, void* stream);
 int enh_colsum_f32(const float* x, int64_t M, int64_t N, int64_t ldx, float* out, int accumulate, void* stream);
 /* to_patches = 1: img [B,C,H,W] -> patches [M, C*p*p] ; 0: the inverse scatter */
 int enh_patch_perm_f32(const float* src, float* dst, int B, int C, int H, int W, int p, int to_patches, void* stream);
