@@ -168,15 +168,19 @@ __global__ void cast_f32_h16_kernel(const float* __restrict__ x, uint16_t* __res
 // AdamW, decoupled weight decay, bias correction (torch.optim.AdamW semantics; vitvqgan.py:160).  skip: optional device flag — non-zero = this step's
 // gradients held an inf / nan (enh_nonfinite_flag): nothing is written, the step is dropped the way torch.cuda.amp.GradScaler.step drops it under the
 // reference's --use_amp (main.py:25,52).
-template <typename OT>
+// CLIP: the two gradient-clipping operands are live — clip_coef (optional device scalar, torch.nn.utils.clip_grad_norm_'s coefficient from
+// enh_grad_clip_coef) multiplies the gradient scale after the loss-scale division, clip_value > 0 clamps the unscaled gradient to +-clip_value before the
+// moments (a nan stays a nan, as with torch.clamp).  CLIP = false is the kernel without them, instruction for instruction.
+template <typename OT, bool CLIP>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, uint16_t* __restrict__ p16, int64_t n, float lr, float beta1,
                              float beta2, float eps, float wd, float gscale, float inv_bc1, float inv_sqrt_bc2, const float* __restrict__ skip,
-                             const float* __restrict__ loss_scale) {
+                             const float* __restrict__ loss_scale, const float* __restrict__ clip_coef, float clip_value) {
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= n) return;
   if (skip && *skip != 0.f) return;
   if (loss_scale) gscale /= *loss_scale;      // GradScaler's unscale, folded into the step (the scale is a power of two: exact)
+  if (CLIP && clip_coef) gscale *= *clip_coef;
   float pv[4], gv[4], mv[4], vv[4];
   const bool full = i + 3 < n;
   if (full) {
@@ -192,7 +196,8 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const float gg = gv[k] * gscale;
+    float gg = gv[k] * gscale;
+    if (CLIP && clip_value > 0.f) gg = gg > clip_value ? clip_value : (gg < -clip_value ? -clip_value : gg);
     pv[k] = pv[k] * (1.0f - lr * wd);
     mv[k] = mv[k] * beta1 + gg * (1.0f - beta1);
     vv[k] = vv[k] * beta2 + gg * gg * (1.0f - beta2);
@@ -333,13 +338,20 @@ extern "C" int enh_cast_f32_h16(const float* x, enh_h16* y, int64_t n, int dtype
 
 extern "C" int enh_adamw_step(float* p, const float* g, float* m, float* v, enh_h16* p_bf16, int64_t n, int step,
                               float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                              const float* skip_flag, const float* loss_scale_dev, int dtype, void* stream) {
+                              const float* skip_flag, const float* loss_scale_dev, const float* clip_coef_dev, float clip_value, int dtype,
+                              void* stream) {
   ENH_REQUIRE_DT(dtype, "enh_adamw_step");
-  ENH_REQUIRE(p && g && m && v && n > 0 && step >= 1, ENH_E_BADARG, "enh_adamw_step: bad argument");
+  ENH_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value >= 0.f, ENH_E_BADARG, "enh_adamw_step: bad argument");
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   const int64_t n4 = (n + 3) / 4;
-  ENH_DT_DISPATCH(dtype, (adamw_kernel<OT><<<(int)((n4 + 255) / 256), 256, 0, (hipStream_t)stream>>>(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay,
-                                                                                            grad_scale, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)), skip_flag, loss_scale_dev)));
+  const int grid = (int)((n4 + 255) / 256);
+  const float inv_bc1 = (float)(1.0 / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  if (clip_coef_dev || clip_value > 0.f)
+    ENH_DT_DISPATCH(dtype, (adamw_kernel<OT, true><<<grid, 256, 0, (hipStream_t)stream>>>(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, grad_scale, inv_bc1,
+                                                                                         inv_sqrt_bc2, skip_flag, loss_scale_dev, clip_coef_dev, clip_value)));
+  else
+    ENH_DT_DISPATCH(dtype, (adamw_kernel<OT, false><<<grid, 256, 0, (hipStream_t)stream>>>(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, grad_scale, inv_bc1,
+                                                                                          inv_sqrt_bc2, skip_flag, loss_scale_dev, nullptr, 0.f)));
   return enh_check_launch("enh_adamw_step");
 }
 
@@ -387,6 +399,83 @@ extern "C" int enh_nonfinite_flag(const float* x, int64_t n, float* flag, void* 
   const int grid = (int)(want < 2048 ? want : 2048);
   nonfinite_flag_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, n, flag);
   return enh_check_launch("enh_nonfinite_flag");
+}
+
+// Gradient-norm clipping (torch.nn.utils.clip_grad_norm_, Lightning's gradient_clip_val / track_grad_norm of the trainer the reference runs under,
+// main.py:51-61) over one flat gradient, without leaving the device.
+// Sum of a workgroup's 256 doubles in a fixed order: xor butterflies inside each wave (every lane ends with the same tree, whatever the data), then the four
+// wave sums through LDS, added 0 + 1 + 2 + 3.  The result is valid in thread 0.
+__device__ __forceinline__ double block_sum_f64_fixed(double a, double* s_wave) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = a;
+  __syncthreads();
+  return ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+// part[blockIdx.x] = this workgroup's share of sum x_i^2 (f64); flag (optional) = 1 on any inf / nan — nonfinite_flag_kernel's pass (the same 16-byte loads,
+// grid-stride loop, exponent test, tail handling and plain store) with the squares riding along.  Per thread the four squares of one load are added in f32
+// and the load's sum joins an f64 accumulator, so the rounding of the sum does not grow with n: at most 4 f32 roundings (2^-24 each, positive summands)
+// whatever the buffer size; workgroup and final reductions are f64 in a fixed order.  No atomics: the same bits on every run.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ x, int64_t n, double* __restrict__ part, float* __restrict__ flag) {
+  __shared__ double s_wave[4];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
+  const uint32_t* __restrict__ u = reinterpret_cast<const uint32_t*>(x);
+  const int64_t n4 = n & ~(int64_t)3;
+  uint32_t any = 0u;
+  double acc = 0.0;
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n4; i += stride) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(u + i);
+    const u32x4 e = (v >> 23) & 0xffu;
+    any |= (uint32_t)(e[0] == 0xffu) | (uint32_t)(e[1] == 0xffu) | (uint32_t)(e[2] == 0xffu) | (uint32_t)(e[3] == 0xffu);
+    const float a = __uint_as_float(v[0]), b = __uint_as_float(v[1]), c = __uint_as_float(v[2]), d = __uint_as_float(v[3]);
+    acc += (double)((a * a + b * b) + (c * c + d * d));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (unsigned)(n - n4)) {      // the (at most three) tail elements
+    const uint32_t t = u[n4 + threadIdx.x];
+    any |= (uint32_t)(((t >> 23) & 0xffu) == 0xffu);
+    const float a = __uint_as_float(t);
+    acc += (double)(a * a);
+  }
+  if (flag && __builtin_amdgcn_ballot_w64(any != 0u) != 0 && (threadIdx.x & 63) == 0) *flag = 1.0f;
+  const double t = block_sum_f64_fixed(acc, s_wave);
+  if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// out[0] = total_norm = sqrt(sum of the partials) * grad_scale / (*loss_scale or 1), out[1] = min(1, max_norm / (total_norm + 1e-6)); one workgroup.
+// Thread t adds the partials t, t + 256, ... in ascending order, then the fixed-order workgroup sum.  The scalar tail is f64, rounded once to f32.
+// A non-finite norm follows plain arithmetic, as in torch: norm = inf gives coef 0 (or nan when max_norm is inf too), norm = nan gives coef nan.
+__global__ __launch_bounds__(256) void grad_clip_finish_kernel(const double* __restrict__ part, int parts, float max_norm, float grad_scale,
+                                                               const float* __restrict__ loss_scale, float* __restrict__ out) {
+  __shared__ double s_wave[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < parts; i += 256) acc += part[i];
+  const double sum = block_sum_f64_fixed(acc, s_wave);
+  if (threadIdx.x != 0) return;
+  const double total = sqrt(sum) * (double)grad_scale / (loss_scale ? (double)*loss_scale : 1.0);
+  const double c = (double)max_norm / (total + 1e-6);
+  out[0] = (float)total;
+  out[1] = (float)(c > 1.0 ? 1.0 : c);
+}
+
+static int grad_sumsq_grid(int64_t n) {      // enh_nonfinite_flag's: one 16-byte load per thread up to 2048 workgroups, a grid-stride loop beyond
+  const int64_t n4 = (n + 3) / 4;
+  const int64_t want = (n4 + 255) / 256;
+  return (int)(want < 2048 ? want : 2048);
+}
+
+extern "C" size_t enh_grad_clip_coef_workspace_bytes(int64_t n) { return n > 0 ? (size_t)grad_sumsq_grid(n) * sizeof(double) : 0; }
+
+extern "C" int enh_grad_clip_coef(const float* g, int64_t n, float max_norm, float grad_scale, const float* loss_scale_dev, float* found_inf, float* out,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  ENH_REQUIRE(g && out && n > 0 && ((uintptr_t)g & 15) == 0 && !(max_norm < 0.f) && max_norm == max_norm, ENH_E_BADARG,
+              "enh_grad_clip_coef: bad argument (g 16-byte aligned, max_norm >= 0)");
+  ENH_REQUIRE(ws && ((uintptr_t)ws & 7) == 0 && ws_bytes >= enh_grad_clip_coef_workspace_bytes(n), ENH_E_WORKSPACE,
+              "enh_grad_clip_coef: workspace too small or misaligned (%zu bytes)", ws_bytes);
+  const int grid = grad_sumsq_grid(n);
+  grad_sumsq_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(g, n, (double*)ws, found_inf);
+  grad_clip_finish_kernel<<<1, 256, 0, (hipStream_t)stream>>>((const double*)ws, grid, max_norm, grad_scale, loss_scale_dev, out);
+  return enh_check_launch("enh_grad_clip_coef");
 }
 
 // Device-side tail of the input pipeline (reference enhancing/dataloader/imagenet.py:26-54: Resize -> RandomCrop / CenterCrop -> RandomHorizontalFlip ->

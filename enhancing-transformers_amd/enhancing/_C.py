@@ -119,13 +119,15 @@ SIGNATURES = {
     "enh_gemm_bf16_split": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "enh_layernorm_forward_x3": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "enh_attention_forward_x3": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
-    "enh_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _i32, _vp]),
+    "enh_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _f32, _i32, _vp]),
+    "enh_grad_clip_coef_workspace_bytes": (_sz, [_i64]),
+    "enh_grad_clip_coef": (_i32, [_vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "enh_loss_scale_update": (_i32, [_vp, _vp, _vp, _f32, _f32, _i32, _vp]),
     "enh_nonfinite_flag": (_i32, [_vp, _i64, _vp, _vp]),
 }
 
 _LIB = None
-ABI_VERSION = 20  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 21  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -537,13 +539,28 @@ def nonfinite_flag(x, flag):
            lambda: _check(lib().enh_nonfinite_flag(_p(x, F32, "x"), x.numel(), _p(flag, F32, "flag"), _stream()), "enh_nonfinite_flag"), unit="byte")
 
 
+def grad_clip_coef(g, max_norm: float, grad_scale: float, out, loss_scale=None, found_inf=None):
+    """out[0] = total_norm = ||g||_2 * grad_scale / (loss_scale or 1), out[1] = coef = min(1, max_norm / (total_norm + 1e-6)) — the coefficient of
+    torch.nn.utils.clip_grad_norm_ over one flat f32 gradient, left on the device (out f32 [2]; enh_adamw_step's clip_coef operand is out[1:]).
+    max_norm = inf: the norm alone (coef = 1).  found_inf (f32 [1]): additionally set to 1.0 on an inf / nan, in the same pass (never cleared)."""
+    nb = lib().enh_grad_clip_coef_workspace_bytes(g.numel())
+    ws = _workspace(nb, g.device)
+    _timed("grad_sumsq_kernel", 4.0 * g.numel(),
+           lambda: _check(lib().enh_grad_clip_coef(_p(g, F32, "g"), g.numel(), float(max_norm), float(grad_scale), _p(loss_scale, F32, "loss_scale"),
+                                                   _p(found_inf, F32, "found_inf"), _p(out, F32, "out"), _p(ws), ws.numel(), _stream()),
+                          "enh_grad_clip_coef"), unit="byte")
+
+
 def adamw_step(p, g, m, v, p_bf16, step: int, lr: float, beta1: float = 0.9, beta2: float = 0.99, eps: float = 1e-8,
-               weight_decay: float = 1e-4, grad_scale: float = 1.0, skip_flag=None, loss_scale=None):
+               weight_decay: float = 1e-4, grad_scale: float = 1.0, skip_flag=None, loss_scale=None, clip_coef=None, clip_value: float = 0.0):
+    """clip_coef (device f32 [1], optional): multiplies the gradient after the loss-scale division (grad_clip_coef's out[1:]); clip_value > 0: the unscaled
+    gradient is clamped to [-clip_value, clip_value] before the moments (0 = off)"""
     # 30 B per parameter: p, g, m, v read (16) + p, m, v written (12) + the bf16 operand shadow written (2)
     _timed("adamw_kernel", (28.0 + (2.0 if p_bf16 is not None else 0.0)) * p.numel(),
            lambda: _check(lib().enh_adamw_step(_p(p, F32, "p"), _p(g, F32, "g"), _p(m, F32, "m"), _p(v, F32, "v"), _p(p_bf16, H16, "p_bf16"),
                                                p.numel(), step, lr, beta1, beta2, eps, weight_decay, grad_scale, _p(skip_flag, F32, "skip_flag"),
-                                               _p(loss_scale, F32, "loss_scale"), _dt(p_bf16), _stream()), "enh_adamw_step"), unit="byte")
+                                               _p(loss_scale, F32, "loss_scale"), _p(clip_coef, F32, "clip_coef"), float(clip_value), _dt(p_bf16),
+                                               _stream()), "enh_adamw_step"), unit="byte")
 
 
 def loss_scale_update(scale, found_inf, tracker, growth: float = 2.0, backoff: float = 0.5, interval: int = 2000):

@@ -501,6 +501,10 @@ class Stage1Engine:
         # the loss scale and GradScaler's growth tracker, on the device (None for bf16 / fp32 engines: no scaling anywhere)
         self.scale_t = torch.full((1,), self._init_scale, dtype=F32, device=self.device) if self.scaled else None
         self._growth_tracker = torch.zeros(1, dtype=torch.int32, device=self.device) if self.scaled else None
+        # (total_norm, clip coefficient) of the last optimizer_step that asked for the gradient norm: written by enh_grad_clip_coef, the coefficient is
+        # read by the AdamW launch — neither ever visits the host inside the step
+        self._clip_out = torch.zeros(2, dtype=F32, device=self.device)
+        self.grad_norm = self._clip_out[:1]
 
     @property
     def loss_scale(self) -> float:
@@ -877,8 +881,13 @@ class Stage1Engine:
             self._anchor_t = torch.zeros(1, device=self.device, requires_grad=True)  # makes autograd call our backward
         return self._anchor_t
 
-    def optimizer_step(self, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 1e-4, grad_scale: float = 1.0) -> None:
-        """torch.optim.AdamW over the single parameter group of vitvqgan.py:153-160 (one fused launch)."""
+    def optimizer_step(self, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 1e-4, grad_scale: float = 1.0,
+                       clip_norm: Optional[float] = None, clip_value: Optional[float] = None) -> None:
+        """torch.optim.AdamW over the single parameter group of vitvqgan.py:153-160 (one fused launch).
+        clip_norm: torch.nn.utils.clip_grad_norm_'s max_norm over this optimizer's parameters (Lightning's gradient_clip_val with the "norm" algorithm);
+        float("inf") measures the norm without clipping (track_grad_norm=2).  Either way the 2-norm of the FINAL gradient — all-reduced, divided by the
+        accumulation window and the world size, unscaled — is left in self.grad_norm (device f32 [1], read it outside the step).
+        clip_value: clamp of every unscaled gradient element to [-clip_value, clip_value] (the "value" algorithm).  None / None: today's two launches."""
         s = self.store
         if self.comm is not None:
             if not s.comm_done:
@@ -887,6 +896,7 @@ class Stage1Engine:
             grad_scale = grad_scale / self.comm.world
         s.step_count += 1
         skip = None
+        loss_scale = self.scale_t if (self.scaled and not s.grads_unscaled) else None
         if self.check_nonfinite:
             # GradScaler.step's found-inf skip + GradScaler.update (reference main.py:25,52 --use_amp), without a host round trip: one pass over the flat
             # gradient sets the flag, the AdamW launch reads it and writes nothing when it is set, and the scale is halved / doubled on the device.
@@ -894,10 +904,20 @@ class Stage1Engine:
             # a dropped step then only shifts the bias correction by one step.
             skip = self.found_inf
             skip.zero_()
+        clip = {}      # the clip operands of the AdamW launch; empty = the call as it was before they existed
+        if clip_norm is not None:
+            # the same single pass over the flat gradient gives the sum of squares AND the flag: the norm costs the fp16 step no extra read
+            _C.grad_clip_coef(s.g, clip_norm, grad_scale, self._clip_out, loss_scale=loss_scale, found_inf=skip)
+            if clip_norm != float("inf"):
+                clip["clip_coef"] = self._clip_out[1:]
+        elif skip is not None:
             _C.nonfinite_flag(s.g, skip)
+        if clip_value:
+            clip["clip_value"] = float(clip_value)
+        if skip is not None:
             self.skipped_steps.add_(skip)
         _C.adamw_step(s.p, s.g, s.m, s.v, s.p16 if self.half else None, s.step_count, lr, betas[0], betas[1], eps, weight_decay,
-                      grad_scale, skip_flag=skip, loss_scale=self.scale_t if (self.scaled and not s.grads_unscaled) else None)
+                      grad_scale, skip_flag=skip, loss_scale=loss_scale, **clip)
         if self.check_nonfinite:
             _C.loss_scale_update(self.scale_t, skip, self._growth_tracker, 2.0, 0.5, self.scale_growth_interval)
         s.refresh_operands()      # operands derived from the masters (the towers' pre-scaled q | k | v weights, the x3 images: _refresh_x3_operands)

@@ -19,8 +19,21 @@ class Trainer:
     def __init__(self, max_epochs: int = 100, precision: int = 32, gpus: int = 1, num_nodes: int = 1, strategy: Optional[str] = None,
                  accumulate_grad_batches: int = 1, callbacks=None, logger=None, max_steps: Optional[int] = None,
                  default_root_dir: str = "experiments", log_every_n_steps: int = 10, limit_val_batches: Optional[int] = None,
-                 val_batches: Optional[int] = None) -> None:
+                 val_batches: Optional[int] = None, gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
+                 track_grad_norm: int = -1) -> None:
         self.max_epochs, self.max_steps = max_epochs, max_steps
+        # Lightning's three gradient-norm arguments: gradient_clip_val (None / 0 = off) with gradient_clip_algorithm "norm" (clip_grad_norm_, per optimizer)
+        # or "value" (clamp), and track_grad_norm (-1 = off, 2 = log the 2-norm; the only norm the device kernel computes).  All on the device
+        # (engine/optim.py): the host reads the norm only when it logs.
+        if gradient_clip_val is not None and not float(gradient_clip_val) >= 0.0:
+            raise ValueError(f"gradient_clip_val must be None or >= 0, got {gradient_clip_val!r}")
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', got {gradient_clip_algorithm!r}")
+        if track_grad_norm not in (-1, 2):
+            raise ValueError(f"track_grad_norm must be -1 (off) or 2 (the 2-norm), got {track_grad_norm!r}")
+        self.gradient_clip_val = float(gradient_clip_val) if gradient_clip_val else None
+        self.gradient_clip_algorithm = gradient_clip_algorithm
+        self.track_grad_norm = track_grad_norm
         # Lightning's `precision` (reference main.py:52): 16 = --use_amp = fp16 autocast + GradScaler -> the fp16 engine mode (fp16 MFMA operands, fp32
         # master weights / accumulation, loss-scaled backward with the inf / nan step skip: engine/stage1.py); "bf16" = Lightning's bf16 mixed precision
         # (bf16 operands, no loss scale); 32 = no AMP = the fp32 "exact" engine mode.  The model's engine precision must AGREE with it: fit() checks and raises.
@@ -92,6 +105,10 @@ class Trainer:
         opt = opts[0]
         for o in opts:
             o.grad_scale = 1.0 / self.accum
+            o.gradient_clip_val, o.gradient_clip_algorithm = self.gradient_clip_val, self.gradient_clip_algorithm
+            o.track_grad_norm = self.track_grad_norm == 2
+        # the norm exists when it is tracked, or as the by-product of clipping by norm
+        log_norm = self.track_grad_norm == 2 or (self.gradient_clip_val is not None and self.gradient_clip_algorithm == "norm")
         sched = _scheds[0]["scheduler"] if _scheds else None
         base_lr = opt.param_groups[0]["lr"]
         if self.world > 1 and len(opts) > 1:
@@ -130,6 +147,11 @@ class Trainer:
                     model.global_step = self.global_step
                     if self.global_step % self.log_every == 0:
                         rec = {k: float(v) for k, v in model.logged.items() if k.startswith("train/")}
+                        if log_norm and self.rank == 0:      # the one place the device value is read
+                            for o, key in zip(opts, ("train/grad_norm", "train/grad_norm_disc")):
+                                gn = getattr(o, "grad_norm", None)
+                                if gn is not None:
+                                    rec[key] = float(gn)
                         rec.update(step=self.global_step, epoch=epoch, images_per_s=seen / (time.time() - t0))
                         self._log(rec)
                         if self.rank == 0:

@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 20  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 21  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -332,10 +332,14 @@ int enh_cast_f32_h16_head_scaled_strided(const float* x, int64_t x_stride, enh_h
  * also refreshes the 16-bit operand shadow p_h16 (`dtype`) used by the GEMMs.  grad_scale multiplies g first (DDP mean / accumulation / 1 / loss scale).
  * skip_flag (optional device float): non-zero = drop this step — nothing is written (p, m, v, p_h16 unchanged): the inf / nan skip of
  * torch.cuda.amp.GradScaler.step under the reference's --use_amp (main.py:25,52); the flag comes from enh_nonfinite_flag.
- * loss_scale_dev (optional device float): g is additionally divided by it (GradScaler's unscale folded into the step). */
+ * loss_scale_dev (optional device float): g is additionally divided by it (GradScaler's unscale folded into the step).
+ * clip_coef_dev (optional device float): multiplied into the gradient scale after the loss-scale division — the coefficient of
+ * torch.nn.utils.clip_grad_norm_, from enh_grad_clip_coef (out + 1).  clip_value (0 = off): the unscaled gradient g * scale is clamped to
+ * [-clip_value, clip_value] before the moments (Lightning's gradient_clip_algorithm="value"; a nan stays a nan).  With NULL and 0 the step is the
+ * step without these operands, bit for bit. */
 int enh_adamw_step(float* p, const float* g, float* m, float* v, enh_h16* p_h16, int64_t n, int step, float lr,
                    float beta1, float beta2, float eps, float weight_decay, float grad_scale, const float* skip_flag, const float* loss_scale_dev,
-                   int dtype, void* stream);
+                   const float* clip_coef_dev, float clip_value, int dtype, void* stream);
 /* GradScaler.update() on the device: found_inf != 0 -> *scale *= backoff_factor, *growth_tracker = 0; otherwise ++*growth_tracker and after
  * growth_interval clean steps in a row *scale *= growth_factor (growth_interval = 0: never grow = a static scale with backoff).  *scale is kept
  * inside [1, 2^24].  torch defaults: growth 2, backoff 0.5, interval 2000, initial scale 65536. */
@@ -344,6 +348,20 @@ int enh_loss_scale_update(float* scale, const float* found_inf, int* growth_trac
 /* flag[0] = 1.0f if any of x[0..n) is inf or nan, otherwise untouched (the caller zeroes it once per step): GradScaler's found-inf check over one flat
  * gradient buffer, one pass at HBM rate.  x 16-byte aligned. */
 int enh_nonfinite_flag(const float* x, int64_t n, float* flag, void* stream);
+/* Gradient-norm clipping over one flat gradient g[0..n) (f32, 16-byte aligned), the arithmetic of torch.nn.utils.clip_grad_norm_ (what Lightning's
+ * Trainer(gradient_clip_val, track_grad_norm=2) does around the reference's optimizers, main.py:51-61):
+ *   out[0] = total_norm = sqrt(sum g_i^2) * grad_scale / (loss_scale_dev ? *loss_scale_dev : 1)
+ *   out[1] = coef       = min(1, max_norm / (total_norm + 1e-6))          (out: device f32[2]; pass out + 1 to enh_adamw_step as clip_coef_dev)
+ * max_norm = +inf: coef = 1 exactly (the norm is measured, nothing is clipped).  found_inf (optional device float): set to 1.0f when g holds an inf or
+ * nan, otherwise untouched — enh_nonfinite_flag's check in the same pass, so a loss-scaled step that wants the norm reads g once, not twice.
+ * One pass over g at HBM rate (16-byte loads, the grid of enh_nonfinite_flag) + a one-workgroup finishing launch, both on `stream`: no host round
+ * trip, safe to capture into a HIP graph.  The four squares of a load are added in f32, everything above that in f64 in a fixed order, no atomics:
+ * relative error of the sum <= 4 * 2^-24 at any n, and the same bits on every run.  ws: enh_grad_clip_coef_workspace_bytes(n) bytes, 8-byte aligned.
+ * A non-finite norm without found_inf (an engine without a loss scale) follows plain arithmetic, like torch: norm = inf -> coef = 0 (the finite
+ * elements then contribute 0 and the inf ones nan), or nan when max_norm is inf as well; norm = nan -> coef = nan. */
+size_t enh_grad_clip_coef_workspace_bytes(int64_t n);
+int enh_grad_clip_coef(const float* g, int64_t n, float max_norm, float grad_scale, const float* loss_scale_dev, float* found_inf, float* out,
+                       void* ws, size_t ws_bytes, void* stream);
 
 /* Device-side tail of the input pipeline (enhancing/dataloader/imagenet.py:26-54: ... RandomCrop / CenterCrop -> RandomHorizontalFlip -> ToTensor):
  * src uint8 [B,Hs,Ws,3] (decoded + resized images, each in the top-left corner of its slot), meta int32 [B,3] = (y0, x0, flip) -> out f32 [B,3,R,R] in [0,1].

@@ -12,7 +12,8 @@ from pathlib import Path
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "enhancing-transformers_amd"))
 
-if __name__ == '__main__':
+
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser()
     parser.add_argument('-c', '--config', type=str, required=True)
     parser.add_argument('-s', '--seed', type=int, default=0)
@@ -30,7 +31,17 @@ if __name__ == '__main__':
     parser.add_argument('--bf16', default=False, action='store_true',
                         help="(extension) mixed precision with bf16 MFMA operands (Lightning precision 'bf16': no loss scale, ~3 %% faster, ~5e-3 parity) "
                              "instead of the fp16 operands of --use_amp")
-    args = parser.parse_args()
+    parser.add_argument('--gradient_clip_val', type=float, default=None,
+                        help="(extension) Lightning's Trainer(gradient_clip_val): clip each optimizer's gradient on the device; unset / 0 = off")
+    parser.add_argument('--gradient_clip_algorithm', type=str, default="norm", choices=("norm", "value"),
+                        help="(extension) 'norm' = clip_grad_norm_ to --gradient_clip_val, 'value' = clamp every element to +-gradient_clip_val")
+    parser.add_argument('--track_grad_norm', type=int, default=-1, choices=(-1, 2),
+                        help="(extension) 2 = log train/grad_norm (and train/grad_norm_disc) to metrics.jsonl without clipping; -1 = off")
+    return parser
+
+
+if __name__ == '__main__':
+    args = build_parser().parse_args()
 
     if args.num_gpus > 1 and "RANK" not in os.environ:
         if args.num_nodes > 1:
@@ -60,5 +71,6 @@ if __name__ == '__main__':
     callbacks, _logger = setup_callbacks(exp_config, config)      # reference main.py:47
     trainer = Trainer(callbacks=callbacks, max_epochs=args.epochs, precision=32 if args.fp32 else ("bf16" if args.bf16 else 16), gpus=args.num_gpus, num_nodes=args.num_nodes,
                       strategy="ddp" if args.num_nodes > 1 or args.num_gpus > 1 else None, accumulate_grad_batches=args.update_every,
-                      max_steps=args.max_steps, default_root_dir=os.path.join(ROOT, "experiments", args.config))
+                      max_steps=args.max_steps, default_root_dir=os.path.join(ROOT, "experiments", args.config),
+                      gradient_clip_val=args.gradient_clip_val, gradient_clip_algorithm=args.gradient_clip_algorithm, track_grad_norm=args.track_grad_norm)
     trainer.fit(model, data)
