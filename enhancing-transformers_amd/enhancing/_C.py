@@ -30,6 +30,7 @@ DETERMINISTIC = os.environ.get("ENH_DETERMINISTIC", "1") != "0"
 
 _c = ctypes
 _vp, _i64, _i32, _f32, _sz = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_float, _c.c_size_t
+_u64, _u32 = _c.c_uint64, _c.c_uint32
 
 # name -> (restype, argtypes); must list every symbol include/enh_hip.h declares (checked by tests)
 SIGNATURES = {
@@ -41,6 +42,10 @@ SIGNATURES = {
     "enh_vq_forward": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
     "enh_vq_backward": (_i32, [_vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _f32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
     "enh_vq_lookup": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "enh_gumbel_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "enh_gumbel_forward": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _i32, _i32, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "enh_gumbel_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _f32, _i32, _vp, _i32, _u64, _u32, _vp, _vp, _vp, _sz, _vp]),
+    "enh_gumbel_noise": (_i32, [_u64, _u32, _i64, _i32, _vp, _vp]),
     "enh_layernorm_forward": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "enh_layernorm_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "enh_layernorm_backward_ws": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
@@ -127,7 +132,7 @@ SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 21  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 22  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -305,6 +310,52 @@ def vq_lookup(codebook, idx, use_norm: bool, want_bf16: bool = True, h16: torch.
     _check(lib().enh_vq_lookup(_p(codebook, F32, "codebook"), _p(idx, I64, "idx"), M, K, d, depth, int(use_norm), _p(out), _p(out16),
                                _dt(out16), _stream()), "enh_vq_lookup")
     return out, out16
+
+
+def gumbel_forward(z: torch.Tensor, codebook: torch.Tensor, tau: float, hard: bool, use_norm: bool, seed: int, call: int):
+    """one level of the fused Gumbel-softmax quantizer: z [M,d] f32, codebook [K,d] f32 (d % 8 == 0, 8 <= d <= 32) ->
+    (z_q [M,d], soft z_q [M,d] (z_q itself unless hard), idx i64 [M], loss [1], stats [5,M] for gumbel_backward)."""
+    _p(z, F32, "z"); _p(codebook, F32, "codebook")
+    M, d = z.shape
+    K = codebook.shape[0]
+    zq = torch.empty_like(z)
+    zq_soft = torch.empty_like(z) if hard else None
+    idx = torch.empty(M, dtype=I64, device=z.device)
+    loss = torch.empty(1, dtype=F32, device=z.device)
+    stats = torch.empty(5, M, dtype=F32, device=z.device)
+    L = lib()
+    ws = _workspace(L.enh_gumbel_workspace_bytes(M, K, d), z.device)
+    # work model: two M x K x 32 products (scores, y @ en) on the exact-f32 MFMA
+    _timed("gumbel_forward (gumbel_prep + gumbel_fwd_kernel + gumbel_loss)", 4.0 * M * K * 32,
+           lambda: _check(L.enh_gumbel_forward(_p(z), _p(codebook), M, K, d, float(tau), int(hard), int(use_norm), int(seed), int(call), _p(zq),
+                                               _p(zq_soft), _p(idx), _p(loss), _p(stats), _p(ws), ws.numel(), _stream()), "enh_gumbel_forward"),
+           unit="flop_f32")
+    return zq, (zq_soft if hard else zq), idx, loss, stats
+
+
+def gumbel_backward(z, codebook, zq_soft, stats, g_zq, g_loss: float, g_loss_dev: Optional[torch.Tensor], tau: float, hard: bool,
+                    idx: Optional[torch.Tensor], use_norm: bool, seed: int, call: int, d_codebook: torch.Tensor):
+    """Returns dz f32 [M,d]; ACCUMULATES into d_codebook [K,d] f32.  hard: the forward's mode, idx [M] i64 its indices (needed when hard)."""
+    _p(z, F32, "z"); _p(codebook, F32, "codebook")
+    M, d = z.shape
+    K = codebook.shape[0]
+    dz = torch.empty_like(z)
+    L = lib()
+    ws = _workspace(L.enh_gumbel_workspace_bytes(M, K, d), z.device)
+    # work model: seven M x K x 32 products (dz: scores, dy, dl @ en; dE: scores, dy, dl^T zn, y^T g_zq) on the exact-f32 MFMA
+    _timed("gumbel_backward (gumbel_prep + gumbel_bwd_dz + gumbel_bwd_de + gumbel_de_finalize)", 14.0 * M * K * 32,
+           lambda: _check(L.enh_gumbel_backward(_p(z), _p(codebook), _p(zq_soft, F32, "zq_soft"), _p(stats, F32, "stats"), _p(g_zq, F32, "g_zq"), float(g_loss),
+                                     _p(g_loss_dev, F32, "g_loss_dev"), M, K, d, float(tau), int(hard), _p(idx, I64, "idx"), int(use_norm), int(seed), int(call),
+                                     _p(dz), _p(d_codebook, F32, "d_codebook"), _p(ws), ws.numel(), _stream()), "enh_gumbel_backward"),
+           unit="flop_f32")
+    return dz
+
+
+def gumbel_noise(seed: int, call: int, M: int, K: int, device) -> torch.Tensor:
+    """the [M,K] noise the fused Gumbel quantizer uses at (seed, call): out[m,k] = g(seed, call, m, k)"""
+    out = torch.empty(M, K, dtype=F32, device=device)
+    _check(lib().enh_gumbel_noise(int(seed), int(call), M, K, _p(out), _stream()), "enh_gumbel_noise")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

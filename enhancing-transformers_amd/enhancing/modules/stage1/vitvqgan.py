@@ -323,7 +323,9 @@ class ViTVQ(nn.Module):
 
 class ViTVQGumbel(ViTVQ):
     """reference vitvqgan.py:191-212: ViTVQ with a GumbelQuantizer and an optional temperature schedule.  The two towers run on the HIP schedule; the
-    quantizer between them is plain torch under autograd (not a hot path of this build — no shipped stage-1 config names this class)."""
+    quantizer between them is plain torch under autograd by default, and the fused gfx950 kernels (csrc/gumbel.hip) with ``fused: true`` among the
+    quantizer's params — the kwarg is passed through to GumbelQuantizer, nothing else changes here.  Either way the step stays the eager sequence:
+    the temperature and the fused path's noise call index are host scalars, so capturing the Gumbel step in a HIP graph is out of scope."""
 
     def __init__(self, image_key: str, image_size: int, patch_size: int, encoder, decoder, quantizer, loss, path: Optional[str] = None,
                  ignore_keys: List[str] = list(), temperature_scheduler=None, scheduler=None) -> None:

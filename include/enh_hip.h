@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 21  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 22  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -113,6 +113,52 @@ int enh_vq_backward(const float* z, const float* codebook, const int64_t* idx, c
 /* decode_codes front half (vitvqgan.py:81-87): out[m] = sum_i n(codebook[idx[m,i]]) ([M,d]) as f32 and as a 16-bit operand (`dtype`) */
 int enh_vq_lookup(const float* codebook, const int64_t* idx, int64_t M, int n_embed, int embed_dim,
                   int depth, int use_norm, float* out, enh_h16* out_h16, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fused Gumbel-softmax quantizer — GumbelQuantizer.quantize, enhancing/modules/stage1/quantizers.py:103-126 (one level; the residual
+ * loop of quantizers.py:38-63 is the caller's)
+ * ------------------------------------------------------------------------------------------------
+ *   zn = n(z), en = n(E)   (n = F.normalize, eps 1e-12, or the identity when use_norm = 0; sums as in the quantizer contract above)
+ *   l_k = (2 zn.en_k - |zn|^2) - |en_k|^2     the dot on the exact-f32 MFMA, column order 0,16,1,17,...,15,31       (quantizers.py:107-109)
+ *   y = softmax((l + g) / tau),  z_q = y @ en                                                                      (quantizers.py:111-114)
+ *   p = softmax(l),  loss = mean over the M tokens of sum_k p_k (log p_k + log K)                                  (quantizers.py:117-118)
+ *   idx = argmax_k (l_k + g_k), lowest k on ties                                                                   (quantizers.py:120)
+ * No [M,K] buffer is written by any entry but the noise dump.  embed_dim: a multiple of 8 in [8, 32] (width 32, zero padding), else ENH_E_SHAPE.
+ * The same bits on every run (no float atomics).
+ *
+ * Noise:  g(seed, call, m, k) = -log(-log(u)),  u = (x >> 9) * 2^-23 + 2^-24  (23 bits: u in [2^-24, 1 - 2^-24], open at both ends),
+ *   x = word (k & 3) of Philox4x32-10 with key (k0, k1) = (seed & 0xffffffff, seed >> 32) and counter
+ *   (c0, c1, c2, c3) = (k >> 2, m & 0xffffffff, m >> 32, call);  the logs are the hardware log2 times ln 2 (the inner one clamped below at 5e-8).
+ *   m = token row, k = code.  Nothing else enters: not M, K, the launch geometry, or which entry asks.  One device function serves all entries. */
+
+/* bytes of scratch of enh_gumbel_forward / enh_gumbel_backward: the prepared codebook, and for the backward the normalised tokens [M,32]
+ * and up to 64 slab partials of the codebook gradient [Kpad,32] */
+size_t enh_gumbel_workspace_bytes(int64_t M, int n_embed, int embed_dim);
+
+/* Forward (quantizers.py:103-126).
+ *   z [M,d] f32, codebook [K,d] f32;  tau > 0;  hard: 0 = z_q is y @ en, 1 = z_q is en[idx] (the value of y_hard - y.detach() + y)
+ *   zq_out    [M,d] f32
+ *   zq_soft   [M,d] f32   hard = 1 only, optional: y @ en, which enh_gumbel_backward needs (hard = 0: zq_out is that already; ignored)
+ *   idx_out   [M] i64,  loss_out [1] f32
+ *   stats_out [5,M] f32   saved for the backward: max and sum of exp of both softmaxes (l, then (l+g)/tau), and the token's loss term */
+int enh_gumbel_forward(const float* z, const float* codebook, int64_t M, int n_embed, int embed_dim, float tau, int hard, int use_norm,
+                       uint64_t seed, uint32_t call, float* zq_out, float* zq_soft, int64_t* idx_out, float* loss_out, float* stats_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of the above (the autograd graph of quantizers.py:103-122).  hard = 1: the gradient through y is that of the soft y, as with hard = 0;
+ * en's own term of z_q = y_st @ en takes the one-hot value, y_hard^T g_zq in place of y^T g_zq, so the forward's idx [M] is needed (hard = 0: unused,
+ * may be NULL).
+ *   zq_soft, stats: the forward's outputs;  seed, call, tau, hard, use_norm: the forward's
+ *   g_zq [M,d] f32 grad wrt z_q;  g_loss * (g_loss_dev ? *g_loss_dev : 1) = grad wrt the loss
+ *   dz [M,d] f32;  d_codebook [K,d] f32 is ACCUMULATED into (caller zeroes it) */
+int enh_gumbel_backward(const float* z, const float* codebook, const float* zq_soft, const float* stats, const float* g_zq, float g_loss,
+                        const float* g_loss_dev, int64_t M, int n_embed, int embed_dim, float tau, int hard, const int64_t* idx,
+                        int use_norm, uint64_t seed, uint32_t call, float* dz, float* d_codebook, void* workspace, size_t workspace_bytes,
+                        void* stream);
+
+/* the noise the two entries above use in place of F.gumbel_softmax's draw (torch/nn/functional.py gumbel_softmax, called at quantizers.py:111):
+ * out [M,K] f32, out[m,k] = g(seed, call, m, k).  For tests and debugging. */
+int enh_gumbel_noise(uint64_t seed, uint32_t call, int64_t M, int n_embed, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm — nn.LayerNorm(dim), eps 1e-5, biased variance (enhancing/modules/stage1/layers.py:85-92,143)
