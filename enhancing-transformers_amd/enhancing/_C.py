@@ -129,10 +129,18 @@ SIGNATURES = {
     "enh_grad_clip_coef": (_i32, [_vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "enh_loss_scale_update": (_i32, [_vp, _vp, _vp, _f32, _f32, _i32, _vp]),
     "enh_nonfinite_flag": (_i32, [_vp, _i64, _vp, _vp]),
+    "enh_skinny_gemm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "enh_skinny_gemm_h16": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
+    "enh_decode_attention_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "enh_decode_attention": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _i32, _vp]),
+    "enh_row_ln_scale": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _i32, _vp]),
+    "enh_gpt_embed": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "enh_skinny_gemm_f32": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "enh_sample_logits": (_i32, [_vp, _i32, _i32, _f32, _i32, _f32, _vp, _u64, _u32, _u32, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _LIB = None
-ABI_VERSION = 22  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 23  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -977,3 +985,89 @@ def lpips_head(feat, lin, B: int, HW: int, C: int, val_ws, out, accumulate: bool
 def lpips_head_backward(feat, lin, gout, B: int, HW: int, C: int, dfeat1):
     _check(lib().enh_lpips_head_backward(_p(feat, H16, "feat"), _p(lin, F32, "lin"), _p(gout, F32, "gout"), B, HW, C, _p(dfeat1, H16, "dfeat1"), _dt(feat, dfeat1), _stream()),
            "enh_lpips_head_backward")
+
+
+# ------------------------------------------------------------------------------------------------
+# stage-2 sampling: decode-shaped kernels (csrc/gpt_decode.hip)
+# ------------------------------------------------------------------------------------------------
+ACT_RELU_SQ = 1      # enh_skinny_gemm_h16's own activation code: square(relu(.))
+
+
+def skinny_gemm(x, w, out, bias=None, relu_sq: bool = False, res=None):
+    """out[M,N] = act(x[M,K] w[N,K]^T + bias) (+ res): x, w 16-bit (one format), M <= 64; out f32 or 16-bit (enh_skinny_gemm_h16)"""
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K or tuple(out.shape) != (M, N) or (res is not None and tuple(res.shape) != (M, N)) or (bias is not None and bias.numel() != N):
+        raise RuntimeError(f"skinny_gemm: x {tuple(x.shape)} w {tuple(w.shape)} out {tuple(out.shape)} do not fit")
+    L = lib()
+    nb = L.enh_skinny_gemm_workspace_bytes(M, N, K)
+    ws = _workspace(nb, x.device) if nb else None
+    o32, o16 = (out, None) if out.dtype == F32 else (None, out)
+    # algorithmic bytes: the weight once, x, the result
+    _timed("gpt_skinny_gemm_kernel", 2.0 * N * K + 2.0 * M * K + float(out.element_size()) * M * N,
+           lambda: _check(L.enh_skinny_gemm_h16(_p(x, H16, "x"), _p(w, H16, "w"), M, N, K, _p(bias, F32, "bias"), ACT_RELU_SQ if relu_sq else 0,
+                                                _p(res, F32, "res"), _p(o32, F32, "out"), _p(o16, H16, "out"), _p(ws), nb, _dt(x, w, o16), _stream()),
+                          "enh_skinny_gemm_h16"), unit="byte")
+
+
+def decode_attention(qkv, k_cache, v_cache, t: int, out):
+    """one token per (batch, head): appends the step's k / v at slot t of k_cache / v_cache [B,H,Tmax,hs] and writes
+    out[B,C] = softmax(q K[0..t]^T / sqrt(hs)) V[0..t]; qkv [B,3C], caches and out share one dtype (bf16 | fp16 | f32)"""
+    B, H, Tmax, hs = k_cache.shape
+    if tuple(v_cache.shape) != (B, H, Tmax, hs) or tuple(qkv.shape) != (B, 3 * H * hs) or tuple(out.shape) != (B, H * hs):
+        raise RuntimeError(f"decode_attention: qkv {tuple(qkv.shape)} caches {tuple(k_cache.shape)} {tuple(v_cache.shape)} out {tuple(out.shape)} do not fit")
+    dt = qkv.dtype
+    if dt not in _DT_OF:
+        raise RuntimeError(f"decode_attention: dtype must be bf16, fp16 or f32, got {dt}")
+    L = lib()
+    nb = L.enh_decode_attention_workspace_bytes(B, H, hs, Tmax)
+    ws = _workspace(nb, qkv.device)
+    _timed("gpt_decode_attn_kernel", 2.0 * qkv.element_size() * B * H * (int(t) + 1) * hs,
+           lambda: _check(L.enh_decode_attention(_p(qkv, dt, "qkv"), _p(k_cache, dt, "k_cache"), _p(v_cache, dt, "v_cache"), B, H, hs, Tmax, int(t),
+                                                 _p(out, dt, "out"), _p(ws), ws.numel(), _DT_OF[dt], _stream()), "enh_decode_attention"), unit="byte")
+
+
+def row_ln_scale(x, w, b, out, colscale=None, eps: float = 1e-5):
+    """out = LayerNorm(x) (* colscale): x [M,D] f32, M <= 64, D % 8 == 0 up to 8192; out f32 or 16-bit"""
+    M, D = x.shape
+    o32, o16 = (out, None) if out.dtype == F32 else (None, out)
+    _check(lib().enh_row_ln_scale(_p(x, F32, "x"), _p(w, F32, "w"), _p(b, F32, "b"), _p(colscale, F32, "colscale"), M, D, eps, _p(o32, F32, "out"),
+                                  _p(o16, H16, "out"), _dt(o16), _stream()), "enh_row_ln_scale")
+
+
+def gpt_embed(table, ids, pos_row, out):
+    """out[b] = table[ids[b]] + pos_row; ids: an int64 device tensor view with one element per row (any stride, e.g. codes[:, t])"""
+    B, C = out.shape
+    if not ids.is_cuda or ids.dtype != I64 or ids.dim() != 1 or ids.numel() != B:
+        raise RuntimeError("gpt_embed: ids must be a 1-D int64 tensor on the device, one per output row")
+    stride = ids.stride(0) if B > 1 else 1
+    _check(lib().enh_gpt_embed(_p(table, F32, "table"), ctypes.c_void_p(ids.data_ptr()), max(int(stride), 1), _p(pos_row, F32, "pos_row"), B, C,
+                               table.shape[0], _p(out, F32, "out"), _stream()), "enh_gpt_embed")
+
+
+def skinny_gemm_f32(x, w, out, bias=None, relu_sq: bool = False, res=None):
+    """the exact mode's skinny_gemm: every tensor f32 (enh_skinny_gemm_f32)"""
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K or tuple(out.shape) != (M, N) or (res is not None and tuple(res.shape) != (M, N)) or (bias is not None and bias.numel() != N):
+        raise RuntimeError(f"skinny_gemm_f32: x {tuple(x.shape)} w {tuple(w.shape)} out {tuple(out.shape)} do not fit")
+    _check(lib().enh_skinny_gemm_f32(_p(x, F32, "x"), _p(w, F32, "w"), M, N, K, _p(bias, F32, "bias"), ACT_RELU_SQ if relu_sq else 0, _p(res, F32, "res"),
+                                     _p(out, F32, "out"), _stream()), "enh_skinny_gemm_f32")
+
+
+def sample_logits(logits, codes_col, temperature: float = 1.0, top_k=None, top_p=None, uniforms=None, seed: int = 0, call: int = 0, step: int = 0,
+                  row0: int = 0, logits_out=None, mask_out=None, probs_out=None):
+    """GPT.sample's filter and draw (enh_sample_logits).  logits [B,V] f32; codes_col: an int64 view with one element per row (e.g. codes[:, t]);
+    logits_out: an f32 view [B,V] whose rows are contiguous (e.g. logits[:, t*V:(t+1)*V]); mask_out uint8 [B,V]; probs_out f32 [B,V]"""
+    B, V = logits.shape
+    if not codes_col.is_cuda or codes_col.dtype != I64 or codes_col.numel() != B:
+        raise RuntimeError("sample_logits: codes_col must be an int64 device view with one element per row")
+    lo_ptr, lo_stride = None, 0
+    if logits_out is not None:
+        if not logits_out.is_cuda or logits_out.dtype != F32 or tuple(logits_out.shape) != (B, V) or logits_out.stride(1) != 1:
+            raise RuntimeError("sample_logits: logits_out must be an f32 device view [B,V] with contiguous rows")
+        lo_ptr, lo_stride = ctypes.c_void_p(logits_out.data_ptr()), (logits_out.stride(0) if B > 1 else V)
+    _check(lib().enh_sample_logits(_p(logits, F32, "logits"), B, V, float(temperature), int(top_k) if top_k is not None else 0,
+                                   float(top_p) if top_p is not None else -1.0, _p(uniforms, F32, "uniforms"), int(seed) & (2 ** 64 - 1), int(call), int(step),
+                                   int(row0), ctypes.c_void_p(codes_col.data_ptr()), max(int(codes_col.stride(0)) if B > 1 else 1, 1), lo_ptr, lo_stride,
+                                   _p(mask_out, torch.uint8, "mask_out"), _p(probs_out, F32, "probs_out"), _stream()), "enh_sample_logits")

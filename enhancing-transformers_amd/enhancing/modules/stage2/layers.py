@@ -1,0 +1,212 @@
+"""Stage-2 GPT prior (reference enhancing/modules/stage2/layers.py:23-303), sampling only.
+
+The modules below are parameter containers with the reference's names, shapes and init, so its checkpoints and yaml load.  `GPT.sample` is the
+reference's cached sampling loop restated per step on the device (csrc/gpt_decode.hip).  With cond_num_tokens == 1 every step is one token per
+batch row; under the cache the block sees T == 1, where `time_shift(x)` is all zeros and the mix `x * time_mix + time_shift(x) * (1 - time_mix)`
+is `ln1(x) * time_mix`.  That is what `GPT.sample` computes, and it is NOT what the teacher-forced `GPT.forward` computes (there the shifted
+term is the previous token): the contract here is `sample` / `sample_step`.
+
+Per step and layer: ln1 * time_mix -> fused q|k|v (one [3C, C] weight) -> attention against the cache, appending k / v -> proj + residual ->
+ln2 -> p0 with relu^2 -> p1 + residual; then the final LayerNorm, the head and the sampler.  Nothing in the loop reads a device value on
+the host: the drawn codes stay in device memory and the next step's embedding kernel reads them there.
+
+Left out: GPT.forward, RQTransformer, stage-2 training, HIP-graph capture of the step."""
+import os
+from typing import Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+MAX_BATCH = 64          # rows of one decode step (enh_skinny_gemm_h16); larger batches run in chunks
+MAX_EMBED = 8192        # enh_row_ln_scale
+MAX_VOCAB = 16384       # enh_sample_logits
+MAX_HEAD = 384          # enh_decode_attention
+MAX_TOKENS = 8192       # enh_decode_attention: slots of the k / v cache
+OPERAND_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
+
+
+class MultiHeadSelfAttention(nn.Module):
+    def __init__(self, ctx_len: int, cond_len: int, embed_dim: int, n_heads: int, attn_bias: bool, use_mask: bool = True):
+        super().__init__()
+        assert embed_dim % n_heads == 0
+        self.key = nn.Linear(embed_dim, embed_dim, bias=attn_bias)
+        self.query = nn.Linear(embed_dim, embed_dim, bias=attn_bias)
+        self.value = nn.Linear(embed_dim, embed_dim, bias=attn_bias)
+        self.proj = nn.Linear(embed_dim, embed_dim, attn_bias)
+        self.n_heads = n_heads
+        self.ctx_len = ctx_len
+        # (the reference's `mask` buffer is non-persistent: no state-dict entry; sampling one token per step needs no mask)
+        self.time_mix = nn.Parameter((torch.arange(embed_dim, dtype=torch.float32) / (embed_dim - 1)).view(1, 1, embed_dim))
+
+
+class FFN(nn.Module):
+    def __init__(self, embed_dim: int, mlp_bias: bool):
+        super().__init__()
+        self.p0 = nn.Linear(embed_dim, 4 * embed_dim, bias=mlp_bias)
+        self.p1 = nn.Linear(4 * embed_dim, embed_dim, bias=mlp_bias)
+
+
+class Block(nn.Module):
+    def __init__(self, ctx_len: int, cond_len: int, embed_dim: int, n_heads: int, mlp_bias: bool, attn_bias: bool):
+        super().__init__()
+        self.ln1 = nn.LayerNorm(embed_dim)
+        self.ln2 = nn.LayerNorm(embed_dim)
+        self.attn = MultiHeadSelfAttention(ctx_len=ctx_len, cond_len=cond_len, embed_dim=embed_dim, n_heads=n_heads, attn_bias=attn_bias)
+        self.mlp = FFN(embed_dim=embed_dim, mlp_bias=mlp_bias)
+
+
+class GPT(nn.Module):
+    def __init__(self, vocab_cond_size: int, vocab_img_size: int, embed_dim: int, cond_num_tokens: int, img_num_tokens: int, n_heads: int,
+                 n_layers: int, mlp_bias: bool = True, attn_bias: bool = True) -> None:
+        super().__init__()
+        if cond_num_tokens != 1:
+            raise ValueError(f"GPT: cond_num_tokens must be 1 (class conditioning: every sampling step is one token), got {cond_num_tokens}")
+        if embed_dim % n_heads:
+            raise ValueError(f"GPT: embed_dim {embed_dim} is not a multiple of n_heads {n_heads}")
+        hs = embed_dim // n_heads
+        if hs % 64 or hs > MAX_HEAD:
+            raise ValueError(f"GPT: the head size embed_dim / n_heads must be a multiple of 64 up to {MAX_HEAD}, got {hs}")
+        if vocab_img_size > MAX_VOCAB:
+            raise ValueError(f"GPT: vocab_img_size must be at most {MAX_VOCAB}, got {vocab_img_size}")
+        if embed_dim > MAX_EMBED:
+            raise ValueError(f"GPT: embed_dim must be at most {MAX_EMBED}, got {embed_dim}")
+        if vocab_img_size % 8:
+            raise ValueError(f"GPT: vocab_img_size must be a multiple of 8 (the head's GEMM), got {vocab_img_size}")
+        if img_num_tokens > MAX_TOKENS:
+            raise ValueError(f"GPT: img_num_tokens must be at most {MAX_TOKENS} (the cache of the decode attention), got {img_num_tokens}")
+        self.img_num_tokens = img_num_tokens
+        self.vocab_cond_size = vocab_cond_size
+        self.vocab_img_size = vocab_img_size
+        self.embed_dim = embed_dim
+        self.n_heads = n_heads
+        self.tok_emb_cond = nn.Embedding(vocab_cond_size, embed_dim)
+        self.pos_emb_cond = nn.Parameter(torch.zeros(1, cond_num_tokens, embed_dim))
+        self.tok_emb_code = nn.Embedding(vocab_img_size, embed_dim)
+        self.pos_emb_code = nn.Parameter(torch.zeros(1, img_num_tokens, embed_dim))
+        self.blocks = nn.Sequential(*[Block(ctx_len=cond_num_tokens + img_num_tokens, cond_len=cond_num_tokens, embed_dim=embed_dim,
+                                            n_heads=n_heads, mlp_bias=mlp_bias, attn_bias=attn_bias) for _ in range(n_layers)])
+        self.layer_norm = nn.LayerNorm(embed_dim)
+        self.head = nn.Linear(embed_dim, vocab_img_size, bias=False)
+        self.apply(self._init_weights)
+        self._operands = {}       # operand format -> (versions of the masters, per-layer operand copies)
+
+    def _init_weights(self, module: nn.Module) -> None:
+        if isinstance(module, (nn.Linear, nn.Embedding)):
+            module.weight.data.normal_(mean=0.0, std=0.02)
+            if isinstance(module, nn.Linear) and module.bias is not None:
+                module.bias.data.zero_()
+        elif isinstance(module, nn.LayerNorm):
+            module.bias.data.zero_()
+            module.weight.data.fill_(1.0)
+
+    def forward(self, codes, conds):
+        raise NotImplementedError("GPT.forward (teacher-forced logits over the whole sequence) is not built: this module only samples; note that the "
+                                  "reference's cached sample() and its forward() do not compute the same logits (time_shift)")
+
+    # ---- operand copies -------------------------------------------------------------------------
+    def _operand_copies(self, dt: torch.dtype):
+        """the GEMM weights in the operand format `dt` (torch.float32: the exact mode's packed f32 q|k|v), built once from the fp32 masters and
+        rebuilt when a master was replaced or written in place (load_state_dict, an optimizer step): the masters' version counters are the key"""
+        masters = [p for _, p in sorted(self.named_parameters())]
+        key = tuple((p.data_ptr(), p._version) for p in masters)
+        hit = self._operands.get(dt)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        cast = (lambda w: w.detach().to(dt).contiguous())
+        layers = []
+        for blk in self.blocks:
+            a, m = blk.attn, blk.mlp
+            bias = None
+            if a.query.bias is not None:
+                bias = torch.cat([a.query.bias, a.key.bias, a.value.bias]).detach().float().contiguous()
+            layers.append(dict(wqkv=cast(torch.cat([a.query.weight, a.key.weight, a.value.weight], 0)), bqkv=bias, wproj=cast(a.proj.weight),
+                               w0=cast(m.p0.weight), w1=cast(m.p1.weight), time_mix=a.time_mix.detach().reshape(-1).contiguous()))
+        ops = dict(layers=layers, head=cast(self.head.weight))
+        self._operands[dt] = (key, ops)
+        return ops
+
+    # ---- sampling -------------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
+               use_fp16: bool = True, *, seed: Optional[int] = None, forced_codes: Optional[torch.Tensor] = None, return_logits: bool = True,
+               call: int = 0, row_offset: int = 0) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+        """reference layers.py:213-266: returns (logits [B, T*V] after the temperature and the top-k mask, codes [B, T]).
+
+        use_fp16=True runs the 16-bit operand format of ENH_PRECISION (default fp16) with f32 accumulation; False the exact mode (f32 operands on the vector ALU, f32 cache and
+        row kernels).  The draw is an inverse-CDF walk in index order with one uniform per (seed, call, step, row_offset + row): the distribution of
+        the reference's torch.multinomial, not its bits; a seed gives the same codes on every run (seed=None draws one from torch's generator).
+        forced_codes [B, T] feeds the given codes to the next step instead of the drawn ones (codes are still drawn and returned).
+        Batches above 64 rows run in chunks of 64 rows.
+        Side effect: a module whose parameters are not on the device of `conds` is MOVED there (`self.to(conds.device)`) on the first call, as the
+        stage-1 engine moves its model; the reference leaves that to the caller."""
+        if not conds.is_cuda:
+            raise RuntimeError("GPT.sample runs on a ROCm device only: conds must be a device tensor (there is no CPU path)")
+        dev = conds.device
+        if self.head.weight.device != dev:
+            self.to(dev)
+        conds = conds.reshape(conds.shape[0], -1)
+        if conds.shape[1] != 1:
+            raise ValueError(f"GPT.sample: one condition token per row (cond_num_tokens == 1), got {conds.shape[1]}")
+        conds = conds[:, 0].to(torch.int64).contiguous()
+        B, T, V = conds.shape[0], self.img_num_tokens, self.vocab_img_size
+        if top_k is not None and not 1 <= int(top_k) <= V:
+            raise ValueError(f"GPT.sample: top_k must be in [1, {V}], got {top_k}")
+        if forced_codes is not None:
+            forced_codes = forced_codes.to(device=dev, dtype=torch.int64).reshape(B, T).contiguous()
+            if int(forced_codes.min()) < 0 or int(forced_codes.max()) >= V:
+                raise ValueError(f"GPT.sample: forced_codes outside [0, {V})")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if use_fp16:
+            prec = os.environ.get("ENH_PRECISION", "fp16")
+            if prec not in OPERAND_DTYPE:
+                raise ValueError(f"GPT.sample(use_fp16=True): ENH_PRECISION must be 'fp16' or 'bf16' for the 16-bit mode, got {prec!r}")
+            dt = OPERAND_DTYPE[prec]
+        else:
+            dt = torch.float32
+        codes = torch.empty(B, T, dtype=torch.int64, device=dev)
+        logits = torch.empty(B, T * V, dtype=torch.float32, device=dev) if return_logits else None
+        for s in range(0, B, MAX_BATCH):
+            e = min(s + MAX_BATCH, B)
+            self._sample_rows(conds[s:e], codes[s:e], None if logits is None else logits[s:e], None if forced_codes is None else forced_codes[s:e],
+                              dt, top_k, top_p, float(softmax_temperature), seed, call, row_offset + s)
+        return logits, codes
+
+    def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0):
+        from ... import _C
+        T, V = self.img_num_tokens, self.vocab_img_size
+        st = self._decode_state(conds.shape[0], dt, conds.device)
+        feed = codes if forced is None else forced
+        for t in range(T):
+            self._decode_step(st, t, conds if t == 0 else feed[:, t - 1])
+            _C.sample_logits(st["logits"], codes[:, t], temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, call=call, step=t, row0=row0,
+                             logits_out=None if logits is None else logits[:, t * V:(t + 1) * V])
+
+    def _decode_state(self, b: int, dt: torch.dtype, dev, cache_len: Optional[int] = None) -> dict:
+        """the buffers of one chunk of b <= 64 rows: residual stream, activations, the step's logits and every layer's k / v cache [b, H, T, hs]"""
+        f32, C, H = torch.float32, self.embed_dim, self.n_heads
+        T = cache_len or self.img_num_tokens
+        e = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=dev)
+        return dict(dt=dt, b=b, x=e(b, C, dtype=f32), x2=e(b, C, dtype=f32), a=e(b, C), qkv=e(b, 3 * C), att=e(b, C), hid=e(b, 4 * C),
+                    logits=e(b, self.vocab_img_size, dtype=f32), caches=[(e(b, H, T, C // H), e(b, H, T, C // H)) for _ in self.blocks],
+                    ops=self._operand_copies(dt))
+
+    def _decode_step(self, st: dict, t: int, ids: torch.Tensor) -> None:
+        """one token per row: ids (int64, on the device: the condition at t == 0, else the previous step's codes) -> st["logits"] [b, V] f32"""
+        from ... import _C
+        x, x2, a, qkv, att, hid = st["x"], st["x2"], st["a"], st["qkv"], st["att"], st["hid"]
+        linear = _C.skinny_gemm_f32 if st["dt"] == torch.float32 else _C.skinny_gemm
+        if t == 0:
+            _C.gpt_embed(self.tok_emb_cond.weight.detach(), ids, self.pos_emb_cond.detach()[0, 0], x)
+        else:
+            _C.gpt_embed(self.tok_emb_code.weight.detach(), ids, self.pos_emb_code.detach()[0, t - 1], x)
+        for blk, W, (kc, vc) in zip(self.blocks, st["ops"]["layers"], st["caches"]):
+            _C.row_ln_scale(x, blk.ln1.weight, blk.ln1.bias, a, colscale=W["time_mix"], eps=blk.ln1.eps)
+            linear(a, W["wqkv"], qkv, bias=W["bqkv"])
+            _C.decode_attention(qkv, kc, vc, t, att)
+            linear(att, W["wproj"], x2, bias=blk.attn.proj.bias, res=x)
+            _C.row_ln_scale(x2, blk.ln2.weight, blk.ln2.bias, a, eps=blk.ln2.eps)
+            linear(a, W["w0"], hid, bias=blk.mlp.p0.bias, relu_sq=True)
+            linear(hid, W["w1"], x, bias=blk.mlp.p1.bias, res=x2)
+        _C.row_ln_scale(x, self.layer_norm.weight, self.layer_norm.bias, a, eps=self.layer_norm.eps)
+        linear(a, st["ops"]["head"], st["logits"])

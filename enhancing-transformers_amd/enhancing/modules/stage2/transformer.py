@@ -1,0 +1,64 @@
+"""CondTransformer (reference enhancing/modules/stage2/transformer.py:23-95): a condition model, a frozen stage-1 tokenizer and the GPT prior; `sample`
+draws codes on the device and decodes them with the tokenizer.  Training (`training_step`, `configure_optimizers`) is not built."""
+from typing import List, Optional
+
+import torch
+import torch.nn as nn
+
+from ...utils.general import initialize_from_config
+from .layers import GPT  # noqa: F401  (the reference's `from .layers import *`)
+
+
+class CondTransformer(nn.Module):
+    def __init__(self, cond_key: str, cond, stage1, transformer, path: Optional[str] = None, ignore_keys: List[str] = list(),
+                 code_shape: Optional[List[int]] = None, scheduler=None) -> None:
+        super().__init__()
+        self.cond_key = cond_key
+        self.code_shape = code_shape
+        self.scheduler = scheduler
+        self.cond_model = initialize_from_config(cond)
+        self.stage1_model = initialize_from_config(stage1)
+        self.transformer = initialize_from_config(transformer)
+        # the tokenizer is frozen by never being stepped: its engine keeps the operand copies of the parameters that require a gradient (engine/stage1.py
+        # ParamStore), so the reference's requires_grad = False loop would take the decoder's weights out of that store
+        self.stage1_model.eval()
+        self.cond_model.eval()
+        for p in self.cond_model.parameters():
+            p.requires_grad = False
+        if path is not None:
+            self.init_from_ckpt(path, ignore_keys)
+
+    def init_from_ckpt(self, path: str, ignore_keys: List[str] = list()):
+        """reference transformer.py:67-76"""
+        sd = torch.load(path, map_location="cpu")["state_dict"]
+        for k in list(sd.keys()):
+            for ik in ignore_keys:
+                if k.startswith(ik):
+                    print("Deleting key {} from state_dict.".format(k))
+                    del sd[k]
+        self.load_state_dict(sd, strict=False)
+        print(f"Restored from {path}")
+
+    def forward(self, codes, conds):
+        raise NotImplementedError("CondTransformer.forward (teacher-forced logits) belongs to stage-2 training, which is not built: only sample() is")
+
+    @torch.no_grad()
+    def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
+               use_fp16: bool = True, **kw) -> torch.Tensor:
+        """reference transformer.py:78-95.  **kw goes to GPT.sample (seed, forced_codes, ...).  The drawn codes are kept in `last_codes`."""
+        conds = conds.view(conds.shape[0], -1)
+        kw.setdefault("return_logits", False)
+        _, codes = self.transformer.sample(conds=conds, top_k=top_k, top_p=top_p, softmax_temperature=softmax_temperature, use_fp16=use_fp16, **kw)
+        if self.code_shape is not None:
+            codes = codes.view(codes.shape[0], *self.code_shape)
+        self.last_codes = codes
+        return self.stage1_model.decode_codes(codes).clamp(0, 1)
+
+    def training_step(self, batch, batch_idx: int, optimizer_idx: int = 0):
+        raise NotImplementedError("stage-2 training is not built: CondTransformer only samples")
+
+    def validation_step(self, batch, batch_idx: int):
+        raise NotImplementedError("stage-2 training is not built: CondTransformer only samples")
+
+    def configure_optimizers(self):
+        raise NotImplementedError("stage-2 training is not built: CondTransformer only samples")

@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 22  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 23  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -562,6 +562,49 @@ int enh_maxpool2_nhwc_h16_backward(const enh_h16* x, const enh_h16* gy, const en
  * Backward: gradient w.r.t. the reconstruction features only, dfeat1 [B,h,w,C] bf16, given gout[B] */
 int enh_lpips_head(const enh_h16* feat, const float* lin, int B, int64_t HW, int C, float* val_ws, float* out, int accumulate, int dtype, void* stream);
 int enh_lpips_head_backward(const enh_h16* feat, const float* lin, const float* gout, int B, int64_t HW, int C, enh_h16* dfeat1, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 sampling: the decode-shaped kernels behind GPT.sample / sample_step with one condition token
+ * (enhancing/modules/stage2/layers.py:57-97,213-303).  Every step is one token per batch row: M = batch <= 64 rows.
+ * No float atomics; the same bits on every run.
+ * ------------------------------------------------------------------------------------------------ */
+/* y[M,N] = act(x[M,K] W[N,K]^T + bias[N]) (+ res[M,N]): W in nn.Linear layout, streamed exactly once; 1 <= M <= 64 (else ENH_E_SHAPE),
+ * K % 8 == 0, N % 8 == 0; act 0 = none, 1 = square(relu(.)) (FFN.forward, layers.py:108); bias / res optional f32; the result goes to out_f32
+ * and / or out_h16.  Rows of the padded MFMA tile beyond M or N are never read from memory.  Work is split over N (16 rows of W per
+ * workgroup) and, where that leaves the chip idle, over K: slabs in `workspace`, added in ascending order by a second pass. */
+size_t enh_skinny_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int enh_skinny_gemm_h16(const enh_h16* x, const enh_h16* W, int64_t M, int64_t N, int64_t K, const float* bias, int act, const float* res,
+                        float* out_f32, enh_h16* out_h16, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* One new token per (batch, head).  qkv [B, 3C] = the step's q | k | v (C = H hs), k_cache / v_cache [B, H, Tmax, hs], all in the format of
+ * dtype: ENH_DT_BF16 / ENH_DT_F16, or ENH_DT_F32 (the exact mode).  Writes k and v into slot t and
+ * out[B, C] = softmax(q K[0..t]^T / sqrt(hs)) V[0..t] (layers.py:64-89, the (B nh, T, hs) views).  Slots > t are neither read nor written.
+ * hs: a multiple of 64 up to 384; Tmax <= 8192; 0 <= t < Tmax.  The cache length is cut into pieces of <= 256 slots across workgroups; their
+ * partial results meet in `workspace` and are merged in ascending order. */
+size_t enh_decode_attention_workspace_bytes(int B, int H, int hs, int Tmax);
+int enh_decode_attention(const void* qkv, void* k_cache, void* v_cache, int B, int H, int hs, int Tmax, int t, void* out, void* workspace,
+                         size_t workspace_bytes, int dtype, void* stream);
+/* LayerNorm of M <= 64 rows (biased variance, f32 statistics), D % 8 == 0, D <= 8192, times colscale[D] when given (time_mix, layers.py:60 at
+ * T == 1); out_f32 and / or out_h16 */
+int enh_row_ln_scale(const float* x, const float* w, const float* b, const float* colscale, int M, int D, float eps, float* out_f32,
+                     enh_h16* out_h16, int dtype, void* stream);
+/* out[b] = table[ids[b * id_stride]] + pos_row, b < B; table [V, C] f32, pos_row [C] f32, C % 4 == 0 (layers.py:280-281,290-291) */
+int enh_gpt_embed(const float* table, const int64_t* ids, int64_t id_stride, const float* pos_row, int B, int C, int V, float* out, void* stream);
+/* The exact mode's form of enh_skinny_gemm_h16: f32 operands and result on the vector ALU, every dot product summed as 64 lane partials of K / 64
+ * terms and a 6-level tree (enh_gemm_f32 adds the K terms in ascending order, which at K = 3072 is four times the fp32 reference's own error).
+ * A parity instrument, not a fast path: W is re-read once per eight rows of x. */
+int enh_skinny_gemm_f32(const float* x, const float* W, int64_t M, int64_t N, int64_t K, const float* bias, int act, const float* res, float* out,
+                        void* stream);
+/* GPT.sample lines 233-258 for B rows of V <= 16384 f32 logits, one workgroup per row: x = logits / temperature; top_k > 0: every x below the
+ * k-th largest becomes -inf (ties with it stay); p = softmax(x); top_p >= 0: an entry is dropped when the probabilities strictly larger than
+ * it sum to >= top_p (the largest always stays; entries of EQUAL probability stay or go together, where the reference's sort breaks such a
+ * tie by position), then p is renormalised; the code is the first index whose running sum of p exceeds u * sum(p).  u = uniforms[row] when
+ * given, else 23 bits of Philox4x32-10 (u = (x >> 9) 2^-23 + 2^-24, never 0 or 1) at key = seed, counter = (row0 + row, step, call): a pure function of those, the distribution of
+ * torch.multinomial, not its bits.  top_k <= 0 / top_p < 0: off.
+ * codes[row * code_stride] = the code; optional outputs: logits_out[row * logits_out_stride + v] = x after top-k (what the reference
+ * returns), mask_out [B, V] (1 = kept), probs_out [B, V] (the renormalised p). */
+int enh_sample_logits(const float* logits, int B, int V, float temperature, int top_k, float top_p, const float* uniforms, uint64_t seed,
+                      uint32_t call, uint32_t step, int64_t row0, int64_t* codes, int64_t code_stride, float* logits_out,
+                      int64_t logits_out_stride, uint8_t* mask_out, float* probs_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,169 @@
+"""Times stage-2 sampling at the shipped size (configs/imagenet_gpt_vitvq_base.yaml: C = 6144, 24 layers, 16 heads of 384, V = 8192; random weights)
+and writes profiles/gpt_sample.txt:  python tools/gpt_sample_bench.py [--out FILE] [--layers N]
+
+Per point (batch 4 | 16, cache length 1 | 512 | 1024): ms per sampling step of the device path (GPT._decode_step + the sampler) and of a plain-torch
+fp16 restatement of the same step (torch.matmul / F.layer_norm / softmax on a preallocated cache), alternating inside this process; and the bytes the
+step must move (every GEMM weight once + the cache up to t + the activations) over the time, as a share of the 6.29 TB/s that a plain copy reaches on
+MI355X.  The same share for the skinny GEMM and the decode attention alone, and the time of a whole 1024-step sample at batch 4.
+Timing: HIP events around a window of back-to-back calls (10 steps; 100 kernel launches over rotating operand buffers larger than the last-level
+cache), median, minimum and maximum of 7 windows that alternate between the two paths, after a warm-up."""
+import argparse
+import math
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "enhancing-transformers_amd"))
+from enhancing import _C  # noqa: E402
+from enhancing.modules.stage2.layers import GPT  # noqa: E402
+
+COPY_TBS = 6.29
+
+
+def timed(fn, inner):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for i in range(inner):
+        fn(i)
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / inner
+
+
+def ab(fa, fb, inner, reps=7):
+    """(min, median, max) ms per call of fa and of fb: `reps` alternating windows of `inner` back-to-back calls each, after a warm-up of both.
+    fa / fb take the call's index inside its window (the kernel-alone runs rotate their weight buffers with it)."""
+    fa(0); fb(0)
+    torch.cuda.synchronize()
+    ta, tb = [], []
+    for _ in range(reps):
+        ta.append(timed(fa, inner))
+        tb.append(timed(fb, inner))
+    st = lambda v: (min(v), statistics.median(v), max(v))
+    return st(ta), st(tb)
+
+
+class TorchStep:
+    """the yardstick: the same step in plain fp16 torch on the operand copies of the model"""
+
+    def __init__(self, m, b, T):
+        self.m, self.b = m, b
+        C, H = m.embed_dim, m.n_heads
+        self.ops = m._operand_copies(torch.float16)
+        h = lambda p: None if p is None else p.detach().half()
+        self.ln = [(h(k.ln1.weight), h(k.ln1.bias), h(k.ln2.weight), h(k.ln2.bias), h(k.attn.proj.bias), h(k.mlp.p0.bias), h(k.mlp.p1.bias)) for k in m.blocks]
+        self.lnf = (h(m.layer_norm.weight), h(m.layer_norm.bias))
+        self.tm = [W["time_mix"].half() for W in self.ops["layers"]]
+        self.bqkv = [W["bqkv"].half() for W in self.ops["layers"]]
+        self.emb, self.pos = h(m.tok_emb_code.weight), h(m.pos_emb_code)[0]
+        self.kc = [torch.zeros(b * H, T, C // H, dtype=torch.float16, device="cuda") for _ in m.blocks]
+        self.vc = [torch.zeros(b * H, T, C // H, dtype=torch.float16, device="cuda") for _ in m.blocks]
+
+    def __call__(self, t, ids):
+        m, b = self.m, self.b
+        C, H = m.embed_dim, m.n_heads
+        hs = C // H
+        x = self.emb[ids] + self.pos[t - 1]
+        for W, (w1, b1, w2, b2, bp, b0, bq), tm, bqkv, kc, vc in zip(self.ops["layers"], self.ln, self.tm, self.bqkv, self.kc, self.vc):
+            a = F.layer_norm(x, (C,), w1, b1) * tm
+            qkv = torch.addmm(bqkv, a, W["wqkv"].t())
+            q, k, v = (z.reshape(b * H, 1, hs) for z in qkv.split(C, dim=1))
+            kc[:, t:t + 1], vc[:, t:t + 1] = k, v
+            att = torch.softmax(torch.bmm(q, kc[:, :t + 1].transpose(1, 2)) * (1.0 / math.sqrt(hs)), dim=-1)
+            x = x + torch.addmm(bp, torch.bmm(att, vc[:, :t + 1]).reshape(b, C), W["wproj"].t())
+            hdn = torch.square(torch.relu(torch.addmm(b0, F.layer_norm(x, (C,), w2, b2), W["w0"].t())))
+            x = x + torch.addmm(bq, hdn, W["w1"].t())
+        logits = torch.matmul(F.layer_norm(x, (C,), *self.lnf), self.ops["head"].t()).float()
+        return torch.multinomial(torch.softmax(logits, -1), 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gpt_sample.txt"))
+    ap.add_argument("--layers", type=int, default=24)
+    ap.add_argument("--whole", type=int, default=1, help="also time a whole 1024-step sample at batch 4")
+    args = ap.parse_args()
+    C, H, V, T, L = 6144, 16, 8192, 1024, args.layers
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        m = GPT(vocab_cond_size=1000, vocab_img_size=V, embed_dim=C, cond_num_tokens=1, img_num_tokens=T, n_heads=H, n_layers=L)
+        with torch.no_grad():
+            m.pos_emb_code.normal_(0, 0.02)
+    dt = torch.float16
+    wbytes = (12 * C * C * L + V * C) * 2
+    lines = [f"stage-2 sampling step on {torch.cuda.get_device_name(0)}: C={C} layers={L} heads={H} V={V}, fp16 operands; weights {wbytes / 1e9:.2f} GB per step",
+             "times: median [min .. max] of 7 alternating windows; a step window is 10 steps (the 21.8 GB of weights pass once per step), a kernel window",
+             "is 100 launches over rotating operand buffers of >= 1 GB in all, so no launch finds its weights or cache in the 256 MB last-level cache;",
+             "kernel times are event times over back-to-back launches: they include the launch boundary (~1-2 us each)",
+             f"{'batch':>5} {'cache':>5} {'device ms [min .. max]':>28} {'torch ms [min .. max]':>28} {'torch/dev':>9} {'GB moved':>9} {'TB/s':>6} {'of 6.29':>8}"]
+    f3 = lambda v: f"{v[1]:.3f} [{v[0]:.3f} .. {v[2]:.3f}]"
+    f1 = lambda v: f"{v[1] * 1e3:.1f} [{v[0] * 1e3:.1f} .. {v[2] * 1e3:.1f}]"
+    worst = 0.0
+    for b in (4, 16):
+        st = m._decode_state(b, dt, "cuda")
+        codes = torch.randint(0, V, (b, T), device="cuda")
+        ts = TorchStep(m, b, T)
+        for n in (1, 512, 1024):
+            t = n - 1
+            tt = max(t, 1)      # the yardstick has no condition branch: its first step is timed as a one-slot code step
+
+            def dev(i):
+                m._decode_step(st, t, codes[:, t - 1] if t else codes[:, 0] % 1000)
+                _C.sample_logits(st["logits"], codes[:, t], top_k=None, top_p=None, seed=1, step=t)
+
+            def ref(i):
+                ts(tt if n > 1 else 0, codes[:, tt - 1])
+            d, r = ab(dev, ref, inner=10)
+            moved = wbytes + 2 * L * b * n * C * 2 + L * b * C * (4 * 6 + 2 * 10)
+            tbs = moved / (d[1] * 1e-3) / 1e12
+            worst = max(worst, d[1] / r[1])
+            lines.append(f"{b:>5} {n:>5} {f3(d):>28} {f3(r):>28} {r[1] / d[1]:>9.2f} {moved / 1e9:>9.2f} {tbs:>6.2f} {100 * tbs / COPY_TBS:>7.1f}%")
+        del st, ts
+        torch.cuda.empty_cache()
+    lines.append(f"device / torch (medians), worst of the six points: {worst:.3f} (must be <= 1)")
+    lines.append("kernels alone (fp16), us: median [min .. max]:")
+    for b in (4, 16):
+        for name, N, K in (("qkv", 3 * C, C), ("proj", C, C), ("p0", 4 * C, C), ("p1", C, 4 * C), ("head", V, C)):
+            nbuf = max(2, -(-(1 << 30) // (2 * N * K)))
+            x = torch.randn(b, K, device="cuda").half()
+            ws = [torch.randn(N, K, device="cuda").half() for _ in range(nbuf)]
+            out = torch.empty(b, N, device="cuda")
+            d, r = ab(lambda i: _C.skinny_gemm(x, ws[i % nbuf], out), lambda i: torch.matmul(x, ws[i % nbuf].t()), inner=100)
+            by = 2 * N * K + 2 * b * K + 4 * b * N
+            lines.append(f"  skinny_gemm {name:>4} M={b:<2} N={N:<5} K={K:<5}: {f1(d):>24} us  {by / d[1] / 1e9:5.2f} TB/s ({100 * by / d[1] / 1e9 / COPY_TBS:4.1f}% of copy)   "
+                         f"torch.matmul {f1(r):>24} us")
+            del ws
+        torch.cuda.empty_cache()
+        for n in (1, 512, 1024):
+            by = 2 * b * n * C * 2 + b * 4 * C * 2
+            nbuf = max(2, min(16, -(-(1 << 30) // (2 * b * T * C * 2))))
+            qkv = torch.randn(b, 3 * C, device="cuda").half()
+            kvs = [(torch.randn(b, H, T, C // H, device="cuda").half(), torch.randn(b, H, T, C // H, device="cuda").half()) for _ in range(nbuf)]
+            out = torch.empty(b, C, device="cuda").half()
+            d, _ = ab(lambda i: _C.decode_attention(qkv, kvs[i % nbuf][0], kvs[i % nbuf][1], n - 1, out), lambda i: None, inner=100)
+            lines.append(f"  decode_attention B={b:<2} len={n:<4}: {f1(d):>24} us  {by / d[1] / 1e9:5.2f} TB/s ({100 * by / d[1] / 1e9 / COPY_TBS:4.1f}% of copy)")
+            del kvs
+        torch.cuda.empty_cache()
+    if args.whole:
+        conds = torch.randint(0, 1000, (4, 1), device="cuda")
+        m.sample(conds, top_k=100, seed=1, return_logits=False)
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        m.sample(conds, top_k=100, seed=1, return_logits=False)
+        e.record()
+        torch.cuda.synchronize()
+        lines.append(f"whole sample, batch 4, {T} steps, top_k 100: {s.elapsed_time(e) / 1e3:.2f} s ({s.elapsed_time(e) / T:.3f} ms per step)")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()
