@@ -33,6 +33,8 @@ int enh_check_launch(const char* what);
 void enh_note_kernel(const char* name, int dtype);
 // the same for a kernel template <int D, typename OT> (attention_dh.hip): named "name<D, OT>"
 void enh_note_kernel_dh(const char* name, int d, int dtype);
+// the same for a symbol that is taken as it stands (no template, or its arguments spelled out in the literal)
+void enh_note_kernel_plain(const char* name);
 int enh_zero_f32_launch(float* p, int64_t n, hipStream_t s);   // p[0..n) = 0 as a kernel launch (graph-safe; see common.cpp)
 #define ENH_MAX_DEVICES 64
 int enh_current_device();   // hipGetDevice of the calling thread, clamped to [0, ENH_MAX_DEVICES)

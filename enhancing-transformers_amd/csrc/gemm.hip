@@ -199,10 +199,12 @@ static int gemm_make_persistent(GemmArgs& g, GemmLaunch& L, const char* what) {
 static thread_local struct { const char* name; int dtype; GemmLaunch gemm; int d; } g_last = {};
 void enh_note_kernel(const char* name, int dtype) { g_last.name = name; g_last.dtype = dtype; g_last.d = 0; }
 void enh_note_kernel_dh(const char* name, int d, int dtype) { g_last.name = name; g_last.dtype = dtype; g_last.d = d; }
+void enh_note_kernel_plain(const char* name) { g_last.name = name; g_last.dtype = 0; g_last.d = -1; }      // the symbol as it stands (no template, or its arguments spelled out)
 extern "C" const char* enh_last_kernel(void) {
   static thread_local char buf[96];
   buf[0] = 0;
-  if (g_last.name && g_last.d) snprintf(buf, sizeof(buf), "%s<%d, %s>", g_last.name, g_last.d, g_last.dtype == ENH_DT_F16 ? "F16" : "BF16");
+  if (g_last.name && g_last.d < 0) snprintf(buf, sizeof(buf), "%s", g_last.name);
+  else if (g_last.name && g_last.d) snprintf(buf, sizeof(buf), "%s<%d, %s>", g_last.name, g_last.d, g_last.dtype == ENH_DT_F16 ? "F16" : "BF16");
   else if (g_last.name) snprintf(buf, sizeof(buf), "%s<%s>", g_last.name, g_last.dtype == ENH_DT_F16 ? "F16" : "BF16");
   else if (g_last.gemm.grid) ENH_DT_DISPATCH(g_last.dtype, (gemm_launch_name<OT>(g_last.gemm, buf, sizeof(buf))));
   return buf;

@@ -136,11 +136,18 @@ SIGNATURES = {
     "enh_row_ln_scale": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _i32, _vp]),
     "enh_gpt_embed": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp]),
     "enh_skinny_gemm_f32": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "enh_causal_attention_forward": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp]),
+    "enh_causal_attention_forward_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "enh_ln_timeshift": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _i32, _vp]),
+    "enh_gpt_embed_seq": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "enh_relu_sq_h16": (_i32, [_vp, _vp, _i64, _i32, _vp]),
+    "enh_cross_entropy_rows": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "enh_mean_f32": (_i32, [_vp, _i64, _vp, _vp]),
     "enh_sample_logits": (_i32, [_vp, _i32, _i32, _f32, _i32, _f32, _vp, _u64, _u32, _u32, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _LIB = None
-ABI_VERSION = 23  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 24  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -1071,3 +1078,62 @@ def sample_logits(logits, codes_col, temperature: float = 1.0, top_k=None, top_p
                                    float(top_p) if top_p is not None else -1.0, _p(uniforms, F32, "uniforms"), int(seed) & (2 ** 64 - 1), int(call), int(step),
                                    int(row0), ctypes.c_void_p(codes_col.data_ptr()), max(int(codes_col.stride(0)) if B > 1 else 1, 1), lo_ptr, lo_stride,
                                    _p(mask_out, torch.uint8, "mask_out"), _p(probs_out, F32, "probs_out"), _stream()), "enh_sample_logits")
+
+
+# ------------------------------------------------------------------------------------------------
+# stage-2 teacher-forced forward: sequence-shaped kernels (csrc/gpt_prefill.hip)
+# ------------------------------------------------------------------------------------------------
+def causal_attention(qkv, B: int, N: int, H: int, D: int, out, lse=None, scale: Optional[float] = None):
+    """out [B,N,H*D] = causal softmax attention of the packed qkv [B,N,3*H*D]; 16-bit tensors run the MFMA kernel, f32 tensors the exact mode's
+    instrument; lse [B,H,N] f32 optional; scale defaults to D ** -0.5"""
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    if qkv.numel() != B * N * 3 * H * D or out.numel() != B * N * H * D or (lse is not None and lse.numel() != B * H * N):
+        raise RuntimeError(f"causal_attention: qkv {tuple(qkv.shape)} out {tuple(out.shape)} do not fit B={B} N={N} H={H} D={D}")
+    L = lib()
+    if qkv.dtype == F32:
+        _check(L.enh_causal_attention_forward_f32(_p(qkv, F32, "qkv"), B, N, H, D, scale, _p(out, F32, "out"), _p(lse, F32, "lse"), _stream()),
+               "enh_causal_attention_forward_f32")
+        return
+    # executed MFMA work: the score product over D and P V over D, on the lower triangle
+    _timed(None, 2.0 * B * H * N * (N + 1) * D,
+           lambda: _check(L.enh_causal_attention_forward(_p(qkv, H16, "qkv"), B, N, H, D, scale, _p(out, H16, "out"), _p(lse, F32, "lse"), _dt(qkv, out),
+                                                         _stream()), "enh_causal_attention_forward"))
+
+
+def ln_timeshift(x, w, b, out, S: int, colscale=None, eps: float = 1e-5, out_f32=None):
+    """out = LayerNorm(x) [* colscale + LayerNorm(previous row of the same sequence) * (1 - colscale)]: x [M,D] f32, M whole sequences of S rows;
+    out f32 or 16-bit; out_f32: an f32 copy beside a 16-bit out"""
+    M, D = x.shape
+    o32, o16 = (out, None) if out.dtype == F32 else (out_f32, out)
+    _check(lib().enh_ln_timeshift(_p(x, F32, "x"), _p(w, F32, "w"), _p(b, F32, "b"), _p(colscale, F32, "colscale"), M, int(S), D, eps, _p(o32, F32, "out"),
+                                  _p(o16, H16, "out"), _dt(o16), _stream()), "enh_ln_timeshift")
+
+
+def gpt_embed_seq(conds, codes, tok_cond, pos_cond, tok_code, pos_code, out):
+    """out [B,S,C] f32: the condition row and the first S - 1 codes of every row of codes [B,T] (int64, contiguous rows), S <= T + 1"""
+    B, S, C = out.shape
+    if conds.dtype != I64 or conds.numel() != B or codes.dtype != I64 or codes.dim() != 2 or codes.shape[0] != B or codes.shape[1] < S - 1 or codes.stride(1) != 1:
+        raise RuntimeError("gpt_embed_seq: conds [B] and codes [B,T >= S-1] must be int64 device tensors with contiguous rows")
+    _check(lib().enh_gpt_embed_seq(_p(conds, I64, "conds"), ctypes.c_void_p(codes.data_ptr()), codes.stride(0) if B > 1 else codes.shape[1],
+                                   _p(tok_cond, F32, "tok_cond"), _p(pos_cond, F32, "pos_cond"), _p(tok_code, F32, "tok_code"), _p(pos_code, F32, "pos_code"),
+                                   B, S, C, tok_cond.shape[0], tok_code.shape[0], _p(out, F32, "out"), _stream()), "enh_gpt_embed_seq")
+
+
+def relu_sq(y, x=None):
+    """y = square(relu(x)) (x f32, y 16-bit or f32), or in place on y when x is None"""
+    if y.dtype not in _DT_OF or (x is not None and x.numel() != y.numel()):
+        raise RuntimeError("relu_sq: y must be bf16, fp16 or f32 and x as long as y")
+    _check(lib().enh_relu_sq_h16(_p(x, F32, "x"), _p(y, y.dtype, "y"), y.numel(), _DT_OF[y.dtype], _stream()), "enh_relu_sq_h16")
+
+
+def cross_entropy_rows(logits, target, nll, mean=None):
+    """nll[m] = logsumexp(logits[m]) - logits[m, target[m]]: logits [M,V] f32, target [M] int64, nll [M] f32; mean [1] f32 optional"""
+    M, V = logits.shape
+    if target.numel() != M or nll.numel() != M:
+        raise RuntimeError("cross_entropy_rows: one target and one result per row")
+    _check(lib().enh_cross_entropy_rows(_p(logits, F32, "logits"), _p(target, I64, "target"), M, V, _p(nll, F32, "nll"), _p(mean, F32, "mean"), _stream()),
+           "enh_cross_entropy_rows")
+
+
+def mean_f32(v, mean):
+    _check(lib().enh_mean_f32(_p(v, F32, "v"), v.numel(), _p(mean, F32, "mean"), _stream()), "enh_mean_f32")

@@ -1,16 +1,20 @@
-"""Stage-2 GPT prior (reference enhancing/modules/stage2/layers.py:23-303), sampling only.
+"""Stage-2 GPT prior (reference enhancing/modules/stage2/layers.py:23-303): sampling and the teacher-forced forward, no training.
 
 The modules below are parameter containers with the reference's names, shapes and init, so its checkpoints and yaml load.  `GPT.sample` is the
 reference's cached sampling loop restated per step on the device (csrc/gpt_decode.hip).  With cond_num_tokens == 1 every step is one token per
 batch row; under the cache the block sees T == 1, where `time_shift(x)` is all zeros and the mix `x * time_mix + time_shift(x) * (1 - time_mix)`
 is `ln1(x) * time_mix`.  That is what `GPT.sample` computes, and it is NOT what the teacher-forced `GPT.forward` computes (there the shifted
-term is the previous token): the contract here is `sample` / `sample_step`.
+term is the previous token's ln1 row): two contracts, two goldens (tests/golden/gpt_<case>.npz, gpt_fwd_<case>.npz).
 
 Per step and layer: ln1 * time_mix -> fused q|k|v (one [3C, C] weight) -> attention against the cache, appending k / v -> proj + residual ->
 ln2 -> p0 with relu^2 -> p1 + residual; then the final LayerNorm, the head and the sampler.  Nothing in the loop reads a device value on
 the host: the drawn codes stay in device memory and the next step's embedding kernel reads them there.
 
-Left out: GPT.forward, RQTransformer, stage-2 training, HIP-graph capture of the step."""
+`GPT.forward` runs the whole sequence at once (csrc/gpt_prefill.hip between enh_gemm_h16 products): embedding of [B, S, C] in one launch, per layer
+ln1 + time shift -> q|k|v -> causal flash attention -> proj + residual -> ln2 -> p0 -> relu^2 -> p1 + residual, the final LayerNorm and the head;
+optionally the per-position cross-entropy and its mean on the device.  Inference only: no autograd graph.
+
+Left out: RQTransformer, stage-2 backward and training, more than one condition token, HIP-graph capture, a relu^2 GEMM epilogue."""
 import os
 from typing import Optional, Tuple
 
@@ -22,6 +26,7 @@ MAX_EMBED = 8192        # enh_row_ln_scale
 MAX_VOCAB = 16384       # enh_sample_logits
 MAX_HEAD = 384          # enh_decode_attention
 MAX_TOKENS = 8192       # enh_decode_attention: slots of the k / v cache
+FORWARD_HIDDEN_CAP = 2 << 30   # bytes of forward()'s [chunk T, 4C] hidden activation (f32 + operand copy): shipped size, 6 sequences per chunk
 OPERAND_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
 
 
@@ -89,6 +94,8 @@ class GPT(nn.Module):
         self.head = nn.Linear(embed_dim, vocab_img_size, bias=False)
         self.apply(self._init_weights)
         self._operands = {}       # operand format -> (versions of the masters, per-layer operand copies)
+        self._fwd_states = {}     # (chunk, dtype, device) -> the buffers of forward()
+        self.forward_hidden_cap = FORWARD_HIDDEN_CAP
 
     def _init_weights(self, module: nn.Module) -> None:
         if isinstance(module, (nn.Linear, nn.Embedding)):
@@ -99,9 +106,109 @@ class GPT(nn.Module):
             module.bias.data.zero_()
             module.weight.data.fill_(1.0)
 
-    def forward(self, codes, conds):
-        raise NotImplementedError("GPT.forward (teacher-forced logits over the whole sequence) is not built: this module only samples; note that the "
-                                  "reference's cached sample() and its forward() do not compute the same logits (time_shift)")
+    # ---- teacher-forced forward -------------------------------------------------------------------
+    @torch.no_grad()
+    def forward(self, codes: torch.Tensor, conds: torch.Tensor, *, use_fp16: bool = True, return_loss: bool = False):
+        """reference layers.py:193-211: logits [B, T, V] (f32) of every code given the condition and the codes before it; with return_loss=True
+        (logits, nll [B, T], mean): the per-position cross-entropy against `codes` and its mean (the reference's val/total_loss), both on the device.
+
+        Inference only: the call runs under torch.no_grad and the result carries no autograd graph (stage-2 training is not built).
+        S = T rows are built, the condition and the first T - 1 codes: the causal mask keeps the last code's row from every logit that is kept.
+        use_fp16=True runs the 16-bit operand format of ENH_PRECISION (default fp16) through enh_gemm_h16 and the MFMA causal attention; biases,
+        residuals and LayerNorms stay on the f32 residual stream.  False is the exact mode: f32 operands, tree-ordered sums (enh_skinny_gemm_f32
+        in 64-row pieces), the f32 attention instrument.  Device tensors only.  Batches run in chunks of whole sequences sized so that the hidden
+        activation of the MLP ([chunk T, 4C], f32 and its operand copy) stays under `forward_hidden_cap` bytes.
+        Side effect, as in sample(): a module whose parameters are not on the device of `codes` is moved there."""
+        if not (torch.is_tensor(codes) and torch.is_tensor(conds) and codes.is_cuda and conds.is_cuda):
+            raise NotImplementedError("GPT.forward runs on a ROCm device only: codes and conds must be device tensors (there is no CPU path for the "
+                                      "teacher-forced forward; note that the cached sample() does not compute the same logits: time_shift)")
+        from ... import _C
+        dev = codes.device
+        if self.head.weight.device != dev:
+            self.to(dev)
+        B, T, V = codes.shape[0], self.img_num_tokens, self.vocab_img_size
+        codes = codes.reshape(B, -1).to(torch.int64).contiguous()
+        if codes.shape[1] != T:
+            raise ValueError(f"GPT.forward: codes must hold img_num_tokens = {T} codes per row, got {codes.shape[1]}")
+        conds = conds.reshape(B, -1)
+        if conds.shape[1] != 1:
+            raise ValueError(f"GPT.forward: one condition token per row (cond_num_tokens == 1), got {conds.shape[1]}")
+        conds = conds[:, 0].to(torch.int64).contiguous()
+        if int(codes.min()) < 0 or int(codes.max()) >= V:
+            raise ValueError(f"GPT.forward: codes outside [0, {V})")
+        if int(conds.min()) < 0 or int(conds.max()) >= self.vocab_cond_size:
+            raise ValueError(f"GPT.forward: conds outside [0, {self.vocab_cond_size})")
+        if use_fp16:
+            prec = os.environ.get("ENH_PRECISION", "fp16")
+            if prec not in OPERAND_DTYPE:
+                raise ValueError(f"GPT.forward(use_fp16=True): ENH_PRECISION must be 'fp16' or 'bf16' for the 16-bit mode, got {prec!r}")
+            dt = OPERAND_DTYPE[prec]
+        else:
+            dt = torch.float32
+        chunk = max(1, min(B, int(self.forward_hidden_cap) // (T * 4 * self.embed_dim * (4 + (2 if use_fp16 else 0)))))
+        logits = torch.empty(B, T, V, dtype=torch.float32, device=dev)
+        nll = torch.empty(B, T, dtype=torch.float32, device=dev) if return_loss else None
+        st = self._forward_state(chunk, dt, dev)
+        for s in range(0, B, chunk):
+            e = min(s + chunk, B)
+            self._forward_rows(st, codes[s:e], conds[s:e], logits[s:e], dt)
+            if return_loss:
+                _C.cross_entropy_rows(logits[s:e].view(-1, V), codes[s:e].reshape(-1), nll[s:e].view(-1))
+        if not return_loss:
+            return logits
+        mean = torch.empty(1, dtype=torch.float32, device=dev)
+        _C.mean_f32(nll.view(-1), mean)
+        return logits, nll, mean[0]
+
+    def _forward_state(self, b: int, dt: torch.dtype, dev) -> dict:
+        """the buffers of a chunk of b sequences, kept per (b, dtype) from call to call; a shorter last chunk uses their leading rows"""
+        key = (b, dt, str(dev))
+        st = self._fwd_states.get(key)
+        if st is None:
+            f32, C, M = torch.float32, self.embed_dim, b * self.img_num_tokens
+            e = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=dev)
+            st = dict(x=e(M, C, dtype=f32), x2=e(M, C, dtype=f32), a=e(M, C), qkv=e(M, 3 * C), att=e(M, C), hid32=e(M, 4 * C, dtype=f32),
+                      hid=e(M, 4 * C) if dt != f32 else None)
+            self._fwd_states = {key: st}      # one chunk size at a time: the buffers of a shipped-size chunk are gigabytes
+        return st
+
+    def _forward_rows(self, st, codes, conds, logits, dt) -> None:
+        """one chunk of b whole sequences in the leading b T rows of the buffers `st`: logits [b, T, V] f32"""
+        from ... import _C
+        b, T, C, H, V = codes.shape[0], self.img_num_tokens, self.embed_dim, self.n_heads, self.vocab_img_size
+        M, hs = b * T, C // H
+        ops = self._operand_copies(dt)
+        x, x2, a, qkv, att, hid32, hid = (None if st[k] is None else st[k][:M] for k in ("x", "x2", "a", "qkv", "att", "hid32", "hid"))
+        if dt == torch.float32:
+            def linear(inp, w, out, bias=None, res=None, relu_sq=False):      # tree-ordered sums: enh_gemm_f32 adds K terms in ascending order (DESIGN §3.5)
+                for m0 in range(0, M, MAX_BATCH):
+                    m1 = min(m0 + MAX_BATCH, M)
+                    _C.skinny_gemm_f32(inp[m0:m1], w, out[m0:m1], bias=bias, relu_sq=relu_sq, res=None if res is None else res[m0:m1])
+        else:
+            def linear(inp, w, out, bias=None, res=None, relu_sq=False):
+                N, K = w.shape
+                if out.dtype == torch.float32:
+                    _C.gemm(inp, w, M, N, K, bias=bias, res=res, res_rows=M if res is not None else 0, out_f32=out)
+                else:
+                    _C.gemm(inp, w, M, N, K, bias=bias, out_bf16=out)
+        _C.gpt_embed_seq(conds, codes, self.tok_emb_cond.weight.detach(), self.pos_emb_cond.detach()[0, 0], self.tok_emb_code.weight.detach(),
+                         self.pos_emb_code.detach()[0], x.view(b, T, C))
+        for blk, W in zip(self.blocks, ops["layers"]):
+            _C.ln_timeshift(x, blk.ln1.weight, blk.ln1.bias, a, T, colscale=W["time_mix"], eps=blk.ln1.eps)
+            linear(a, W["wqkv"], qkv, bias=W["bqkv"])
+            _C.causal_attention(qkv, b, T, H, hs, att)
+            linear(att, W["wproj"], x2, bias=blk.attn.proj.bias, res=x)
+            _C.ln_timeshift(x2, blk.ln2.weight, blk.ln2.bias, a, T, eps=blk.ln2.eps)
+            if dt == torch.float32:
+                linear(a, W["w0"], hid32, bias=blk.mlp.p0.bias, relu_sq=True)
+                linear(hid32, W["w1"], x, bias=blk.mlp.p1.bias, res=x2)
+            else:
+                # relu^2 on the f32 product, one rounding to the operand format (in place on a 16-bit product it would be two)
+                linear(a, W["w0"], hid32, bias=blk.mlp.p0.bias)
+                _C.relu_sq(hid, hid32)
+                linear(hid, W["w1"], x, bias=blk.mlp.p1.bias, res=x2)
+        _C.ln_timeshift(x, self.layer_norm.weight, self.layer_norm.bias, a, T, eps=self.layer_norm.eps)
+        linear(a, ops["head"], logits.view(M, V))
 
     # ---- operand copies -------------------------------------------------------------------------
     def _operand_copies(self, dt: torch.dtype):

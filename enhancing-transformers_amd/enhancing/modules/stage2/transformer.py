@@ -1,6 +1,7 @@
 """CondTransformer (reference enhancing/modules/stage2/transformer.py:23-95): a condition model, a frozen stage-1 tokenizer and the GPT prior; `sample`
-draws codes on the device and decodes them with the tokenizer.  Training (`training_step`, `configure_optimizers`) is not built."""
-from typing import List, Optional
+draws codes on the device and decodes them with the tokenizer; `forward` / `validation_step` give the teacher-forced logits and the reference's
+val/total_loss.  Training (`training_step`, `configure_optimizers`) is not built."""
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -16,6 +17,7 @@ class CondTransformer(nn.Module):
         self.cond_key = cond_key
         self.code_shape = code_shape
         self.scheduler = scheduler
+        self.logged = {}
         self.cond_model = initialize_from_config(cond)
         self.stage1_model = initialize_from_config(stage1)
         self.transformer = initialize_from_config(transformer)
@@ -39,8 +41,12 @@ class CondTransformer(nn.Module):
         self.load_state_dict(sd, strict=False)
         print(f"Restored from {path}")
 
-    def forward(self, codes, conds):
-        raise NotImplementedError("CondTransformer.forward (teacher-forced logits) belongs to stage-2 training, which is not built: only sample() is")
+    @torch.no_grad()
+    def forward(self, codes: torch.Tensor, conds: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """reference transformer.py:56-65: (teacher-forced logits [B, T, V], the codes as [B', T']).  Inference only (GPT.forward): no autograd graph."""
+        conds = conds.view(conds.shape[0], -1)
+        logits = self.transformer(codes, conds)
+        return logits, codes.view(-1, codes.shape[-1])
 
     @torch.no_grad()
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
@@ -54,11 +60,39 @@ class CondTransformer(nn.Module):
         self.last_codes = codes
         return self.stage1_model.decode_codes(codes).clamp(0, 1)
 
-    def training_step(self, batch, batch_idx: int, optimizer_idx: int = 0):
-        raise NotImplementedError("stage-2 training is not built: CondTransformer only samples")
+    def get_input(self, batch, key: str) -> torch.Tensor:
+        """reference transformer.py:97-105"""
+        x = batch[key]
+        if len(x.shape) == 3:
+            x = x[..., None]
+        if x.dtype == torch.double:
+            x = x.float()
+        return x.contiguous()
 
-    def validation_step(self, batch, batch_idx: int):
-        raise NotImplementedError("stage-2 training is not built: CondTransformer only samples")
+    def log(self, name: str, value, **_) -> None:
+        """Lightning's ``self.log`` as the stage-1 module keeps it: the last value per name, in `logged`"""
+        self.logged[name] = value
+
+    @torch.no_grad()
+    def shared_step(self, batch, batch_idx: int) -> torch.Tensor:
+        """reference transformer.py:107-118: tokenize the images, encode the condition, run the teacher-forced forward and take the mean
+        cross-entropy of every code given the condition and the codes before it, on the device (enh_cross_entropy_rows)"""
+        images = self.get_input(batch, self.stage1_model.image_key)
+        conds = self.get_input(batch, self.cond_key)
+        codes = self.stage1_model.encode_codes(images).detach()
+        conds = self.cond_model.encode_codes(conds).detach()
+        conds = conds.to(codes.device).view(conds.shape[0], -1)
+        _, _, loss = self.transformer(codes, conds, return_loss=True)
+        return loss
+
+    def validation_step(self, batch, batch_idx: int) -> torch.Tensor:
+        """reference transformer.py:126-130: the loss, also logged as val/total_loss"""
+        loss = self.shared_step(batch, batch_idx)
+        self.log("val/total_loss", loss, on_step=True, on_epoch=True, prog_bar=True, logger=True)
+        return loss
+
+    def training_step(self, batch, batch_idx: int, optimizer_idx: int = 0):
+        raise NotImplementedError("stage-2 training is not built (no backward pass of the GPT): CondTransformer samples and validates")
 
     def configure_optimizers(self):
-        raise NotImplementedError("stage-2 training is not built: CondTransformer only samples")
+        raise NotImplementedError("stage-2 training is not built (no backward pass of the GPT): CondTransformer samples and validates")

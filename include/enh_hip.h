@@ -53,12 +53,12 @@ typedef enh_h16 enh_bf16;  /* raw bfloat16 bits (bf16-only entries) */
 
 const char* enh_last_error(void);
 /* The symbol — as a profiler prints it: template arguments, no parameter list, e.g. "gemm_w256r_kernel<F16, false, 2, true>" — of the main kernel that
- * the calling thread's most recent enh_gemm_h16 / enh_gemm_h16_ws / enh_gemm_h16_dtanh_colsum / enh_gemm_bf16_split / enh_attention_forward(_dh) call
+ * the calling thread's most recent enh_gemm_h16 / enh_gemm_h16_ws / enh_gemm_h16_dtanh_colsum / enh_gemm_bf16_split / enh_attention_forward(_dh) / stage-2 forward (gpt_prefill) call
  * enqueued: the GEMM or attention kernel, not the helpers that ride along (split-K second pass, column sums).  "" before the first such call.  The
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 23  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 24  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -605,6 +605,34 @@ int enh_skinny_gemm_f32(const float* x, const float* W, int64_t M, int64_t N, in
 int enh_sample_logits(const float* logits, int B, int V, float temperature, int top_k, float top_p, const float* uniforms, uint64_t seed,
                       uint32_t call, uint32_t step, int64_t row0, int64_t* codes, int64_t code_stride, float* logits_out,
                       int64_t logits_out_stride, uint8_t* mask_out, float* probs_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 GPT, teacher-forced forward (csrc/gpt_prefill.hip; reference enhancing/modules/stage2/layers.py:57-97,132-136,193-211 with
+ * cond_num_tokens == 1).  M = B S token rows at once: the wide products are enh_gemm_h16's (exact mode: enh_skinny_gemm_f32 in 64-row pieces),
+ * these are the kernels between them.  No float atomics: the same bits on every run.
+ * ------------------------------------------------------------------------------------------------ */
+/* Causal softmax attention, out[b, n, h] = softmax_{j <= n}(q_n . k_j * scale) V: qkv packed [B, N, 3 H D] (enh_attention_forward_dh's layout),
+ * out [B, N, H D], lse [B, H, N] f32 or NULL.  D a multiple of 64 up to 384 (else ENH_E_SHAPE), any N >= 1.  Key tiles above the diagonal are
+ * neither loaded nor computed; above D = 128 two workgroups share a query block, each owning half of V's width. */
+int enh_causal_attention_forward(const enh_h16* qkv, int B, int N, int H, int D, float scale, enh_h16* out, float* lse, int dtype, void* stream);
+/* the exact mode's form (f32 tensors, vector ALU, N <= 8192): a parity instrument */
+int enh_causal_attention_forward_f32(const float* qkv, int B, int N, int H, int D, float scale, float* out, float* lse, void* stream);
+/* LayerNorm (biased variance, f32 statistics) of M rows of width D (D % 8 == 0, D <= 8192), M a multiple of the sequence length S.  With
+ * colscale = time_mix [D]: y[b, s] = ln(x[b, s]) tm + ln(x[b, s - 1]) (1 - tm), and y[b, 0] = ln(x[b, 0]) tm (layers.py:60,77: the shifted term of a
+ * batch element's first row is zero).  colscale = NULL: the plain LayerNorm (ln2, the final norm).  out_f32 and / or out_h16. */
+int enh_ln_timeshift(const float* x, const float* w, const float* b, const float* colscale, int64_t M, int S, int D, float eps, float* out_f32,
+                     enh_h16* out_h16, int dtype, void* stream);
+/* out [B, S, C] f32: row (b, 0) = tok_cond[conds[b]] + pos_cond, row (b, s) = tok_code[codes[b * code_stride + s - 1]] + pos_code[s - 1]
+ * (layers.py:195-203 without the last code, whose row the causal mask keeps from every logit).  C % 4 == 0; ids outside a table are clamped. */
+int enh_gpt_embed_seq(const int64_t* conds, const int64_t* codes, int64_t code_stride, const float* tok_cond, const float* pos_cond,
+                      const float* tok_code, const float* pos_code, int B, int S, int C, int Vc, int V, float* out, void* stream);
+/* y = square(relu(.)) over n % 8 == 0 elements (FFN, layers.py:134).  x != NULL: reads f32 x and writes y in `dtype` (one rounding: what
+ * GPT.forward uses); x == NULL: in place on y.  dtype ENH_DT_BF16 | ENH_DT_F16 | ENH_DT_F32 (the exact mode: y is f32). */
+int enh_relu_sq_h16(const float* x, void* y, int64_t n, int dtype, void* stream);
+/* nll[m] = logsumexp(logits[m]) - logits[m][target[m]] for M rows of V <= 16384 f32 logits, one workgroup per row; mean != NULL: a second,
+ * fixed-order pass writes mean[0] = sum(nll) / M.  enh_mean_f32 is that pass alone (the mean over several calls' rows). */
+int enh_cross_entropy_rows(const float* logits, const int64_t* target, int64_t M, int V, float* nll, float* mean, void* stream);
+int enh_mean_f32(const float* v, int64_t M, float* mean, void* stream);
 
 #ifdef __cplusplus
 }
