@@ -98,6 +98,12 @@ __device__ inline float unpack_hi(uint32_t u) {
   if constexpr (OT::id == 0) return __builtin_bit_cast(float, u & 0xffff0000u);
   else return (float)__builtin_bit_cast(f16x2_t, u)[1];
 }
+// the eight 16-bit elements of one 16-byte load, widened to f32
+template <typename OT>
+__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { f[2 * k] = unpack_lo<OT>(v[k]); f[2 * k + 1] = unpack_hi<OT>(v[k]); }
+}
 template <typename OT>
 __device__ inline float unpack1(uint16_t h) {
   if constexpr (OT::id == 0) return __builtin_bit_cast(float, (uint32_t)h << 16);
@@ -164,6 +170,62 @@ __device__ inline float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+__device__ inline float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// Reductions over the NW = 4 or 16 waves of a workgroup, in a fixed order; every thread gets the result.  s_w: NW words, reusable after the call.
+// The order is part of the callers' bit contract: 4 waves ((s0 + s1) + s2) + s3 and max(max(s0, s1), max(s2, s3)), 16 waves ascending.
+template <int NW, typename T>
+__device__ __forceinline__ void block_publish(T wave_value, T* s_w) {
+  static_assert(NW == 4 || NW == 16, "workgroups of 256 or 1024 threads");
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = wave_value;
+  __syncthreads();
+}
+template <int NW>
+__device__ __forceinline__ float block_sum(float v, float* s_w) {
+  block_publish<NW>(wave_sum(v), s_w);
+  if constexpr (NW == 4) return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) s += s_w[i];
+  return s;
+}
+template <int NW>
+__device__ __forceinline__ float block_max(float v, float* s_w) {
+  block_publish<NW>(wave_max(v), s_w);
+  if constexpr (NW == 4) return fmaxf(fmaxf(s_w[0], s_w[1]), fmaxf(s_w[2], s_w[3]));
+  float s = s_w[0];
+#pragma unroll
+  for (int i = 1; i < NW; ++i) s = fmaxf(s, s_w[i]);
+  return s;
+}
+template <int NW>
+__device__ __forceinline__ int block_count(int v, int* s_w) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  block_publish<NW>(v, s_w);
+  int s = 0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) s += s_w[i];
+  return s;
+}
+
+// Philox4x32-10: key (k0, k1), counter c -> four random words.  The callers choose what the counter words mean and how a word becomes a float
+// (gumbel.hip gb_noise4, gpt_decode.hip gd_uniform).
+__device__ __forceinline__ u32x4 philox4x32_10(uint32_t k0, uint32_t k1, u32x4 c) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c.x), l0 = 0xD2511F53u * c.x;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c.z), l1 = 0xCD9E8D57u * c.z;
+    c = u32x4{h1 ^ c.y ^ k0, l1, h0 ^ c.w ^ k1, l0};
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return c;
 }
 
 // Fixed-order reduction of `rows` partial rows: returns, for thread (col = threadIdx.x & 15, grp = threadIdx.x >> 4) of a 256-thread workgroup handling

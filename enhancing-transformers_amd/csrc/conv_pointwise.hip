@@ -12,12 +12,6 @@
 // a dense 1 x 1, stride 1 one with C == 8 (forward / weight gradient) or N == 8 (input gradient).
 #include "gemm_tiles.h"
 
-template <typename OT>
-__device__ __forceinline__ void pw_unpack8(const u32x4 v, float (&f)[8]) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { f[2 * k] = unpack_lo<OT>(v[k]); f[2 * k + 1] = unpack_hi<OT>(v[k]); }
-}
-
 // ---- forward: x [M][8], w [N][8] (packed operand of the implicit-GEMM kernels), out [M][N]; mode 2 (plain) or 3 (bias + leaky-ReLU * p1) -------------
 template <typename OT>
 __global__ __launch_bounds__(256) void conv_pw_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, const float* __restrict__ bias,
@@ -27,7 +21,7 @@ __global__ __launch_bounds__(256) void conv_pw_fwd_kernel(const uint16_t* __rest
   float wr[8][8], b[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    pw_unpack8<OT>(*reinterpret_cast<const u32x4*>(w + (int64_t)(ng * 8 + j) * 8), wr[j]);
+    unpack8<OT>(*reinterpret_cast<const u32x4*>(w + (int64_t)(ng * 8 + j) * 8), wr[j]);
     b[j] = (mode == 3 && bias) ? bias[ng * 8 + j] : 0.f;
   }
   const int64_t p0_ = (int64_t)blockIdx.x * pix_per_wg;
@@ -44,7 +38,7 @@ __global__ __launch_bounds__(256) void conv_pw_fwd_kernel(const uint16_t* __rest
       const int64_t p = p0_ + it + u * ppb + pl;
       if (p >= M) continue;
       float f[8], v[8];
-      pw_unpack8<OT>(xin[u], f);
+      unpack8<OT>(xin[u], f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float a = 0.f;
@@ -67,7 +61,7 @@ __global__ __launch_bounds__(256) void conv_pw_dgrad_kernel(const uint16_t* __re
   const int kg = t % groups, pl = t / groups, ppb = 256 / groups;
   float wr[8][8];                                       // wr[j][k] = wt[j][kg*8 + k]
 #pragma unroll
-  for (int j = 0; j < 8; ++j) pw_unpack8<OT>(*reinterpret_cast<const u32x4*>(wt + (int64_t)j * K + kg * 8), wr[j]);
+  for (int j = 0; j < 8; ++j) unpack8<OT>(*reinterpret_cast<const u32x4*>(wt + (int64_t)j * K + kg * 8), wr[j]);
   const int64_t p0_ = (int64_t)blockIdx.x * pix_per_wg;
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
   for (int it = 0; it < pix_per_wg; it += 4 * ppb) {          // four pixels per thread in flight; no early exit: the reductions need every lane of the wave
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(256) void conv_pw_dgrad_kernel(const uint16_t* __re
     for (int u = 0; u < 4; ++u) {
       const int64_t p = p0_ + it + u * ppb + pl;
       float f[8], v[8];
-      pw_unpack8<OT>(sin[u], f);
+      unpack8<OT>(sin[u], f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float a = 0.f;
@@ -136,8 +130,8 @@ __global__ __launch_bounds__(256) void conv_pw_wgrad_kernel(const uint16_t* __re
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       float f[8], d[8];
-      pw_unpack8<OT>(xin[u], f);
-      pw_unpack8<OT>(din[u], d);
+      unpack8<OT>(xin[u], f);
+      unpack8<OT>(din[u], d);
 #pragma unroll
       for (int j = 0; j < 8; ++j)
 #pragma unroll

@@ -205,11 +205,6 @@ extern "C" int enh_upfirdn2d(const float* in, const float* kernel, float* out, i
 // the same kernel with other arguments), which is what lets the R1 penalty differentiate through the backward pass.
 // =================================================================================================
 template <typename OT>
-__device__ __forceinline__ void unpack8(const u32x4 v, float (&f)[8]) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { f[2 * k] = unpack_lo<OT>(v[k]); f[2 * k + 1] = unpack_hi<OT>(v[k]); }
-}
-template <typename OT>
 __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
   return (u32x4){pack2<OT>(f[0], f[1]), pack2<OT>(f[2], f[3]), pack2<OT>(f[4], f[5]), pack2<OT>(f[6], f[7])};
 }
@@ -456,16 +451,7 @@ extern "C" int enh_nhwc8_to_img(const enh_h16* src, int B, int C, int H, int W, 
 // the channel padding of the final convolution's input: sample b belongs to slot b % n (n = B / group); for every position p = (h,w,c) the standard
 // deviation over the `group` samples of the slot, sd_p = sqrt(var_p + 1e-8) (biased variance), is averaged over p into ONE scalar per slot:
 //   out[b,h,w,0..C-1] = x[b,h,w,:] ; out[b,h,w,C] = mean_p sd_p of b's slot ; out[b,h,w,C+1..Cp-1] = 0
-// One workgroup per slot (the tensor is B x 4 x 4 x 512: a few hundred KiB); fixed-order reductions, no atomics.
-__device__ __forceinline__ float block_sum_256(float v, float* s_red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) s_red[wave] = v;
-  __syncthreads();
-  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
-
+// One workgroup per slot (the tensor is B x 4 x 4 x 512: a few hundred KiB); fixed-order reductions (common.h block_sum), no atomics.
 template <typename OT>
 __global__ __launch_bounds__(256) void stddev_fwd_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ out, int group, int n, int HW, int C, int Cp) {
   __shared__ float s_red[4];
@@ -493,7 +479,7 @@ __global__ __launch_bounds__(256) void stddev_fwd_kernel(const uint16_t* __restr
 #pragma unroll
     for (int k = 0; k < 8; ++k) part += sqrtf(q[k] / (float)group + 1e-8f);
   }
-  const float sd = block_sum_256(part, s_red) / (float)P;
+  const float sd = block_sum<4>(part, s_red) / (float)P;
   // write the group's samples: copy, the statistic, zero padding
   const int cq = Cp / 8;                       // 16-byte chunks per output pixel
   for (int gi = 0; gi < group; ++gi) {
@@ -526,7 +512,7 @@ __global__ __launch_bounds__(256) void stddev_bwd_kernel(const uint16_t* __restr
     const int64_t b = (int64_t)(i / HW) * n + slot;
     part += unpack1<OT>(g[(b * HW + i % HW) * Cp + C]);
   }
-  const float gsd = block_sum_256(part, s_red) / (float)P;
+  const float gsd = block_sum<4>(part, s_red) / (float)P;
   const int c8 = C / 8;
   for (int64_t p8 = threadIdx.x; p8 < P / 8; p8 += 256) {
     const int64_t pix = p8 / c8;

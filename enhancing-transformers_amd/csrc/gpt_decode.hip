@@ -11,10 +11,9 @@
 //                         softmax(q K[0..t]^T / sqrt(hs)) V[0..t].  Slot t is taken from the step's qkv row, never read back from the cache; slots > t
 //                         are never touched.  The cache length is cut into pieces of at most 256 slots (grid.y); partial (max, sum, out) triples are
 //                         merged in ascending piece order by a second kernel.
-//   enh_row_ln_scale      LayerNorm of <= 64 rows of any width D % 8 == 0 up to 8192 with f32 statistics, times an optional per-column vector.
-//   enh_gpt_embed         x[b] = table[id[b]] + pos[row], ids read from device memory.
 //   enh_sample_logits     temperature, top-k, softmax, top-p and an inverse-CDF draw of one row per workgroup (GPT.sample lines 233-258).
 //   enh_skinny_gemm_f32   the exact mode's form of the product: f32 operands, vector ALU, tree-ordered sums.
+// The step's LayerNorm and embedding are row kernels and stand beside the teacher-forced forward's: gpt_rows.hip (enh_row_ln_scale, enh_gpt_embed).
 // Every result is the same bits on every run: all sums run in a fixed order.
 #include "common.h"
 #include <type_traits>
@@ -23,7 +22,6 @@
 #define GD_MAX_SPLITS 32
 #define GD_ATT_PIECE 256      // cache slots per workgroup of the decode attention (its scores live in LDS)
 #define GD_ATT_MAX_T 8192
-#define GD_LN_MAX_D 8192
 #define GD_SAMPLE_MAX_V 16384
 #define GD_SAMPLE_PER 16      // logits per thread of the sampler (1024 threads)
 
@@ -153,12 +151,17 @@ extern "C" int enh_skinny_gemm_h16(const enh_h16* x, const enh_h16* W, int64_t M
   }
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((N + 15) / 16), (unsigned)splits);
-  if (M <= 16)
-    ENH_DT_DISPATCH(dtype, (gpt_skinny_gemm_kernel<OT, 1><<<grid, 256, 0, s>>>(x, W, (int)M, (int)N, (int)K, cps, bias, act, res, out_f32, out_h16, part)));
-  else if (M <= 32)
-    ENH_DT_DISPATCH(dtype, (gpt_skinny_gemm_kernel<OT, 2><<<grid, 256, 0, s>>>(x, W, (int)M, (int)N, (int)K, cps, bias, act, res, out_f32, out_h16, part)));
-  else
-    ENH_DT_DISPATCH(dtype, (gpt_skinny_gemm_kernel<OT, 4><<<grid, 256, 0, s>>>(x, W, (int)M, (int)N, (int)K, cps, bias, act, res, out_f32, out_h16, part)));
+  // the label is the product kernel's, also when the slab pass follows
+#define GD_GEMM_LAUNCH(MT)                                                                                                                        \
+  do {                                                                                                                                            \
+    enh_note_kernel_plain(dtype == ENH_DT_F16 ? "gpt_skinny_gemm_kernel<F16, " #MT ">" : "gpt_skinny_gemm_kernel<BF16, " #MT ">");                \
+    ENH_DT_DISPATCH(dtype, (gpt_skinny_gemm_kernel<OT, MT><<<grid, 256, 0, s>>>(x, W, (int)M, (int)N, (int)K, cps, bias, act, res, out_f32,       \
+                                                                                out_h16, part)));                                                 \
+  } while (0)
+  if (M <= 16) GD_GEMM_LAUNCH(1);
+  else if (M <= 32) GD_GEMM_LAUNCH(2);
+  else GD_GEMM_LAUNCH(4);
+#undef GD_GEMM_LAUNCH
   if (splits > 1)
     ENH_DT_DISPATCH(dtype, (gpt_skinny_reduce_kernel<OT><<<(unsigned)((M * N + 255) / 256), 256, 0, s>>>(part, splits, (int)M, (int)N, bias, act, res,
                                                                                                         out_f32, out_h16)));
@@ -174,9 +177,7 @@ __device__ __forceinline__ void gd_load8(const void* p, float (&f)[8]) {
     const f32x4 a = reinterpret_cast<const f32x4*>(p)[0], b = reinterpret_cast<const f32x4*>(p)[1];
     f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
   } else {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(p);
-    f[0] = unpack_lo<OT>(v.x); f[1] = unpack_hi<OT>(v.x); f[2] = unpack_lo<OT>(v.y); f[3] = unpack_hi<OT>(v.y);
-    f[4] = unpack_lo<OT>(v.z); f[5] = unpack_hi<OT>(v.z); f[6] = unpack_lo<OT>(v.w); f[7] = unpack_hi<OT>(v.w);
+    unpack8<OT>(*reinterpret_cast<const u32x4*>(p), f);
   }
 }
 
@@ -347,9 +348,11 @@ extern "C" int enh_decode_attention(const void* qkv, void* k_cache, void* v_cach
   const dim3 grid((unsigned)(B * H), (unsigned)nsplit);
   const float scale = 1.0f / sqrtf((float)hs);
   if (dtype == ENH_DT_F32) {
+    enh_note_kernel_plain("gpt_decode_attn_kernel<BF16, true>");
     gpt_decode_attn_kernel<BF16, true><<<grid, 256, 0, s>>>(qkv, k_cache, v_cache, H, hs, Tmax, t, nsplit, split_len, scale, out, part);
     if (nsplit > 1) gpt_decode_attn_merge_kernel<BF16, true><<<(unsigned)(B * H), 128, 0, s>>>(part, H, hs, nsplit, out);
   } else {
+    enh_note_kernel_plain(dtype == ENH_DT_F16 ? "gpt_decode_attn_kernel<F16, false>" : "gpt_decode_attn_kernel<BF16, false>");
     ENH_DT_DISPATCH(dtype, (gpt_decode_attn_kernel<OT, false><<<grid, 256, 0, s>>>(qkv, k_cache, v_cache, H, hs, Tmax, t, nsplit, split_len, scale, out, part)));
     if (nsplit > 1) ENH_DT_DISPATCH(dtype, (gpt_decode_attn_merge_kernel<OT, false><<<(unsigned)(B * H), 128, 0, s>>>(part, H, hs, nsplit, out)));
   }
@@ -357,92 +360,8 @@ extern "C" int enh_decode_attention(const void* qkv, void* k_cache, void* v_cach
 }
 
 // ---------------------------------------------------------------------------------------------
-// row LayerNorm (* per-column scale)
+// exact-mode product
 // ---------------------------------------------------------------------------------------------
-// sum over the 256 threads of a workgroup, fixed order; every thread gets the result.  s_red: 4 floats, reusable after the call.
-__device__ __forceinline__ float gd_block_sum256(float v, float* s_red) {
-  const float w = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = w;
-  __syncthreads();
-  return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-}
-
-template <typename OT>
-__global__ __launch_bounds__(256) void gpt_row_ln_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                         const float* __restrict__ colscale, int D, float eps, float* __restrict__ out_f32,
-                                                         uint16_t* __restrict__ out_h16) {
-  __shared__ float s_red[4];
-  const int t = threadIdx.x;
-  const float* xr = x + (size_t)blockIdx.x * D;
-  const int nv = D >> 2;      // float4 pieces of the row (<= 2048)
-  f32x4 v[8];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int c = t + 256 * i;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    v[i] = c < nv ? *reinterpret_cast<const f32x4*>(xr + 4 * c) : zero;
-    s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-  }
-  const float mean = gd_block_sum256(s, s_red) / (float)D;
-  float s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    if (t + 256 * i < nv) {
-      const f32x4 d = v[i] - mean;
-      s2 += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-    }
-  }
-  const float rstd = 1.0f / sqrtf(gd_block_sum256(s2, s_red) / (float)D + eps);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int c = t + 256 * i;
-    if (c >= nv) continue;
-    const f32x4 g = *reinterpret_cast<const f32x4*>(w + 4 * c), bb = *reinterpret_cast<const f32x4*>(bias + 4 * c);
-    f32x4 y = (v[i] - mean) * rstd * g + bb;
-    if (colscale) y = y * *reinterpret_cast<const f32x4*>(colscale + 4 * c);
-    const size_t o = (size_t)blockIdx.x * D + 4 * c;
-    if (out_f32) *reinterpret_cast<f32x4*>(out_f32 + o) = y;
-    if (out_h16) {
-      const u32x2 pk = {pack2<OT>(y.x, y.y), pack2<OT>(y.z, y.w)};
-      *reinterpret_cast<u32x2*>(out_h16 + o) = pk;
-    }
-  }
-}
-
-extern "C" int enh_row_ln_scale(const float* x, const float* w, const float* b, const float* colscale, int M, int D, float eps, float* out_f32,
-                                enh_h16* out_h16, int dtype, void* stream) {
-  ENH_REQUIRE(x && w && b && (out_f32 || out_h16), ENH_E_BADARG, "enh_row_ln_scale: null pointer");
-  ENH_REQUIRE_DT(dtype, "enh_row_ln_scale");
-  ENH_REQUIRE(M >= 1 && M <= GD_MAX_M, ENH_E_SHAPE, "enh_row_ln_scale: M must be in [1, %d], got %d", GD_MAX_M, M);
-  ENH_REQUIRE(D >= 8 && D <= GD_LN_MAX_D && D % 8 == 0, ENH_E_SHAPE, "enh_row_ln_scale: D must be a multiple of 8 in [8, %d], got %d", GD_LN_MAX_D, D);
-  ENH_DT_DISPATCH(dtype, (gpt_row_ln_kernel<OT><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>(x, w, b, colscale, D, eps, out_f32, out_h16)));
-  return enh_check_launch("enh_row_ln_scale");
-}
-
-// ---------------------------------------------------------------------------------------------
-// embedding, exact-mode product
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gpt_embed_kernel(const float* __restrict__ table, const int64_t* __restrict__ ids, int64_t id_stride,
-                                                        const float* __restrict__ pos_row, int C, int V, float* __restrict__ out) {
-  int64_t id = ids[(int64_t)blockIdx.x * id_stride];
-  id = id < 0 ? 0 : (id >= V ? V - 1 : id);      // an id outside the table cannot come from the sampler; a caller's is clamped, never followed
-  const float* row = table + (size_t)id * C;
-  for (int c = threadIdx.x * 4; c < C; c += 1024) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(row + c), p = *reinterpret_cast<const f32x4*>(pos_row + c);
-    *reinterpret_cast<f32x4*>(out + (size_t)blockIdx.x * C + c) = a + p;
-  }
-}
-
-extern "C" int enh_gpt_embed(const float* table, const int64_t* ids, int64_t id_stride, const float* pos_row, int B, int C, int V, float* out, void* stream) {
-  ENH_REQUIRE(table && ids && pos_row && out, ENH_E_BADARG, "enh_gpt_embed: null pointer");
-  ENH_REQUIRE(B >= 1 && V >= 1 && id_stride >= 1, ENH_E_BADARG, "enh_gpt_embed: B=%d V=%d id_stride=%lld", B, V, (long long)id_stride);
-  ENH_REQUIRE(C >= 4 && C % 4 == 0, ENH_E_SHAPE, "enh_gpt_embed: C must be a positive multiple of 4, got %d", C);
-  gpt_embed_kernel<<<(unsigned)B, 256, 0, (hipStream_t)stream>>>(table, ids, id_stride, pos_row, C, V, out);
-  return enh_check_launch("enh_gpt_embed");
-}
-
 // exact mode: the same product with f32 operands on the vector ALU.  One wave per row of W, the lanes share K (a lane adds K / 64 products,
 // then a 6-level tree over the lanes), eight rows of x at a time.  A parity instrument: W is re-read through L2 once per eight rows.
 __global__ __launch_bounds__(256) void gpt_skinny_gemm_f32_kernel(const float* __restrict__ x, const float* __restrict__ W, int M, int N, int K,
@@ -479,6 +398,7 @@ extern "C" int enh_skinny_gemm_f32(const float* x, const float* W, int64_t M, in
   ENH_REQUIRE(N >= 1 && K >= 8 && K % 8 == 0 && N < (1LL << 30) && K < (1LL << 30), ENH_E_SHAPE,
               "enh_skinny_gemm_f32: K must be a positive multiple of 8, got N=%lld K=%lld", (long long)N, (long long)K);
   ENH_REQUIRE(act == 0 || act == 1, ENH_E_BADARG, "enh_skinny_gemm_f32: act must be 0 (none) or 1 (relu^2), got %d", act);
+  enh_note_kernel_plain("gpt_skinny_gemm_f32_kernel");
   gpt_skinny_gemm_f32_kernel<<<(unsigned)((N + 3) / 4), 256, 0, (hipStream_t)stream>>>(x, W, (int)M, (int)N, (int)K, bias, act, res, out);
   return enh_check_launch("enh_skinny_gemm_f32");
 }
@@ -488,55 +408,14 @@ extern "C" int enh_skinny_gemm_f32(const float* x, const float* W, int64_t M, in
 // in index order.  The k-th largest logit and the top-p cut are found by a bitwise threshold search on the order-preserving integer image
 // of a float (32 counting / summing passes over registers), not by a sort.
 // ---------------------------------------------------------------------------------------------
-// Philox4x32-10 (the rounds of gumbel.hip's gb_noise4, kept as a second copy): word 0 of key = seed, counter = (row low, row high, step, call)
+// word 0 of Philox4x32-10 (common.h) with key = seed and counter = (row low, row high, step, call)
 __device__ __forceinline__ float gd_uniform(uint64_t seed, uint32_t call, uint32_t step, uint64_t row) {
-  uint32_t c0 = (uint32_t)row, c1 = (uint32_t)(row >> 32), c2 = step, c3 = call;
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
+  const uint32_t c0 = philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), u32x4{(uint32_t)row, (uint32_t)(row >> 32), step, call}).x;
   return (float)(c0 >> 9) * 1.1920928955078125e-07f + 5.9604644775390625e-08f;   // 23 bits: (c0 >> 9) 2^-23 + 2^-24 in [2^-24, 1 - 2^-24], every step exact
 }
 __device__ __forceinline__ uint32_t gd_key(float x) {   // a < b  <=>  key(a) < key(b)
   const uint32_t u = __builtin_bit_cast(uint32_t, x);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-// fixed-order reductions over the 1024 threads; s_w: 16 words
-__device__ __forceinline__ float gd_block_sum1024(float v, float* s_w) {
-  const float w = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = w;
-  __syncthreads();
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) s += s_w[i];
-  return s;
-}
-__device__ __forceinline__ float gd_block_max1024(float v, float* s_w) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = s_w[0];
-#pragma unroll
-  for (int i = 1; i < 16; ++i) s = fmaxf(s, s_w[i]);
-  return s;
-}
-__device__ __forceinline__ int gd_block_count1024(int v, int* s_w) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int s = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) s += s_w[i];
-  return s;
 }
 
 __global__ __launch_bounds__(1024) void gpt_sample_kernel(const float* __restrict__ logits, int V, float temperature, int top_k, float top_p,
@@ -564,7 +443,7 @@ __global__ __launch_bounds__(1024) void gpt_sample_kernel(const float* __restric
       int cnt = 0;
 #pragma unroll
       for (int i = 0; i < GD_SAMPLE_PER; ++i) cnt += (i0 + i < V && gd_key(x[i]) >= cand) ? 1 : 0;
-      if (gd_block_count1024(cnt, s_i) >= top_k) T = cand;
+      if (block_count<16>(cnt, s_i) >= top_k) T = cand;
     }
 #pragma unroll
     for (int i = 0; i < GD_SAMPLE_PER; ++i)
@@ -579,7 +458,7 @@ __global__ __launch_bounds__(1024) void gpt_sample_kernel(const float* __restric
   float mx = NEG;
 #pragma unroll
   for (int i = 0; i < GD_SAMPLE_PER; ++i) mx = fmaxf(mx, x[i]);
-  mx = gd_block_max1024(mx, s_f);
+  mx = block_max<16>(mx, s_f);
   float p[GD_SAMPLE_PER];
   float ps = 0.f;
 #pragma unroll
@@ -587,7 +466,7 @@ __global__ __launch_bounds__(1024) void gpt_sample_kernel(const float* __restric
     p[i] = i0 + i < V ? expf(x[i] - mx) : 0.f;
     ps += p[i];
   }
-  const float tot = gd_block_sum1024(ps, s_f);
+  const float tot = block_sum<16>(ps, s_f);
 #pragma unroll
   for (int i = 0; i < GD_SAMPLE_PER; ++i) p[i] = p[i] / tot;
   // ---- top-p: in descending order entry j >= 1 goes when the probability in front of it is >= top_p, i.e. an entry stays iff the sum of the
@@ -598,18 +477,18 @@ __global__ __launch_bounds__(1024) void gpt_sample_kernel(const float* __restric
     float pm = 0.f;
 #pragma unroll
     for (int i = 0; i < GD_SAMPLE_PER; ++i) pm = fmaxf(pm, p[i]);
-    pm = gd_block_max1024(pm, s_f);
+    pm = block_max<16>(pm, s_f);
     float f = 0.f;
 #pragma unroll
     for (int i = 0; i < GD_SAMPLE_PER; ++i) f += p[i] > 0.f ? p[i] : 0.f;
-    if (!(gd_block_sum1024(f, s_f) < top_p)) {
+    if (!(block_sum<16>(f, s_f) < top_p)) {
       uint32_t Tn = 0;      // the largest T with F(T) >= top_p
       for (int bit = 30; bit >= 0; --bit) {
         const uint32_t cand = Tn | (1u << bit);
         float fs = 0.f;
 #pragma unroll
         for (int i = 0; i < GD_SAMPLE_PER; ++i) fs += __builtin_bit_cast(uint32_t, p[i]) > cand ? p[i] : 0.f;
-        if (!(gd_block_sum1024(fs, s_f) < top_p)) Tn = cand;
+        if (!(block_sum<16>(fs, s_f) < top_p)) Tn = cand;
       }
       cut = Tn + 1;
     }
@@ -625,7 +504,7 @@ __global__ __launch_bounds__(1024) void gpt_sample_kernel(const float* __restric
     ks += p[i];
   }
   if (top_p >= 0.f) {
-    const float kt = gd_block_sum1024(ks, s_f);
+    const float kt = block_sum<16>(ks, s_f);
     ks = 0.f;
 #pragma unroll
     for (int i = 0; i < GD_SAMPLE_PER; ++i) { p[i] = p[i] / kt; ks += p[i]; }
@@ -685,6 +564,7 @@ extern "C" int enh_sample_logits(const float* logits, int B, int V, float temper
               B, (long long)code_stride, (long long)logits_out_stride);
   ENH_REQUIRE(V >= 1 && V <= GD_SAMPLE_MAX_V, ENH_E_SHAPE, "enh_sample_logits: V must be in [1, %d], got %d", GD_SAMPLE_MAX_V, V);
   ENH_REQUIRE(temperature > 0.f, ENH_E_BADARG, "enh_sample_logits: temperature must be positive, got %g", (double)temperature);
+  enh_note_kernel_plain("gpt_sample_kernel");
   gpt_sample_kernel<<<(unsigned)B, 1024, 0, (hipStream_t)stream>>>(logits, V, temperature, top_k, top_p, uniforms, seed, call, step, row0, codes,
                                                                    code_stride, logits_out, logits_out_stride, mask_out, probs_out);
   return enh_check_launch("enh_sample_logits");

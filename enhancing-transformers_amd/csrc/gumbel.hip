@@ -38,16 +38,8 @@ __device__ __forceinline__ float gb_gumbel(uint32_t x) {
   return -0.69314718056f * __builtin_amdgcn_logf(e);
 }
 __device__ __forceinline__ void gb_noise4(uint64_t seed, uint32_t call, uint64_t m, uint32_t k4, float (&g)[4]) {
-  uint32_t c0 = k4, c1 = (uint32_t)m, c2 = (uint32_t)(m >> 32), c3 = call;
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  g[0] = gb_gumbel(c0); g[1] = gb_gumbel(c1); g[2] = gb_gumbel(c2); g[3] = gb_gumbel(c3);
+  const u32x4 x = philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), u32x4{k4, (uint32_t)m, (uint32_t)(m >> 32), call});
+  g[0] = gb_gumbel(x.x); g[1] = gb_gumbel(x.y); g[2] = gb_gumbel(x.z); g[3] = gb_gumbel(x.w);
 }
 
 __global__ void gumbel_noise_kernel(uint64_t seed, uint32_t call, int64_t M, int K, float* __restrict__ out) {

@@ -995,7 +995,7 @@ def lpips_head_backward(feat, lin, gout, B: int, HW: int, C: int, dfeat1):
 
 
 # ------------------------------------------------------------------------------------------------
-# stage-2 sampling: decode-shaped kernels (csrc/gpt_decode.hip)
+# stage-2 sampling: decode-shaped kernels (csrc/gpt_decode.hip; LayerNorm and embedding: csrc/gpt_rows.hip)
 # ------------------------------------------------------------------------------------------------
 ACT_RELU_SQ = 1      # enh_skinny_gemm_h16's own activation code: square(relu(.))
 
@@ -1011,7 +1011,7 @@ def skinny_gemm(x, w, out, bias=None, relu_sq: bool = False, res=None):
     ws = _workspace(nb, x.device) if nb else None
     o32, o16 = (out, None) if out.dtype == F32 else (None, out)
     # algorithmic bytes: the weight once, x, the result
-    _timed("gpt_skinny_gemm_kernel", 2.0 * N * K + 2.0 * M * K + float(out.element_size()) * M * N,
+    _timed(None, 2.0 * N * K + 2.0 * M * K + float(out.element_size()) * M * N,
            lambda: _check(L.enh_skinny_gemm_h16(_p(x, H16, "x"), _p(w, H16, "w"), M, N, K, _p(bias, F32, "bias"), ACT_RELU_SQ if relu_sq else 0,
                                                 _p(res, F32, "res"), _p(o32, F32, "out"), _p(o16, H16, "out"), _p(ws), nb, _dt(x, w, o16), _stream()),
                           "enh_skinny_gemm_h16"), unit="byte")
@@ -1029,7 +1029,7 @@ def decode_attention(qkv, k_cache, v_cache, t: int, out):
     L = lib()
     nb = L.enh_decode_attention_workspace_bytes(B, H, hs, Tmax)
     ws = _workspace(nb, qkv.device)
-    _timed("gpt_decode_attn_kernel", 2.0 * qkv.element_size() * B * H * (int(t) + 1) * hs,
+    _timed(None, 2.0 * qkv.element_size() * B * H * (int(t) + 1) * hs,
            lambda: _check(L.enh_decode_attention(_p(qkv, dt, "qkv"), _p(k_cache, dt, "k_cache"), _p(v_cache, dt, "v_cache"), B, H, hs, Tmax, int(t),
                                                  _p(out, dt, "out"), _p(ws), ws.numel(), _DT_OF[dt], _stream()), "enh_decode_attention"), unit="byte")
 
@@ -1081,7 +1081,7 @@ def sample_logits(logits, codes_col, temperature: float = 1.0, top_k=None, top_p
 
 
 # ------------------------------------------------------------------------------------------------
-# stage-2 teacher-forced forward: sequence-shaped kernels (csrc/gpt_prefill.hip)
+# stage-2 teacher-forced forward: sequence-shaped kernels (csrc/gpt_prefill.hip: the attention; the row kernels: csrc/gpt_rows.hip)
 # ------------------------------------------------------------------------------------------------
 def causal_attention(qkv, B: int, N: int, H: int, D: int, out, lse=None, scale: Optional[float] = None):
     """out [B,N,H*D] = causal softmax attention of the packed qkv [B,N,3*H*D]; 16-bit tensors run the MFMA kernel, f32 tensors the exact mode's

@@ -1,7 +1,7 @@
 """Stage-2 GPT prior (reference enhancing/modules/stage2/layers.py:23-303): sampling and the teacher-forced forward, no training.
 
 The modules below are parameter containers with the reference's names, shapes and init, so its checkpoints and yaml load.  `GPT.sample` is the
-reference's cached sampling loop restated per step on the device (csrc/gpt_decode.hip).  With cond_num_tokens == 1 every step is one token per
+reference's cached sampling loop restated per step on the device (csrc/gpt_decode.hip, gpt_rows.hip).  With cond_num_tokens == 1 every step is one token per
 batch row; under the cache the block sees T == 1, where `time_shift(x)` is all zeros and the mix `x * time_mix + time_shift(x) * (1 - time_mix)`
 is `ln1(x) * time_mix`.  That is what `GPT.sample` computes, and it is NOT what the teacher-forced `GPT.forward` computes (there the shifted
 term is the previous token's ln1 row): two contracts, two goldens (tests/golden/gpt_<case>.npz, gpt_fwd_<case>.npz).
@@ -10,7 +10,7 @@ Per step and layer: ln1 * time_mix -> fused q|k|v (one [3C, C] weight) -> attent
 ln2 -> p0 with relu^2 -> p1 + residual; then the final LayerNorm, the head and the sampler.  Nothing in the loop reads a device value on
 the host: the drawn codes stay in device memory and the next step's embedding kernel reads them there.
 
-`GPT.forward` runs the whole sequence at once (csrc/gpt_prefill.hip between enh_gemm_h16 products): embedding of [B, S, C] in one launch, per layer
+`GPT.forward` runs the whole sequence at once (csrc/gpt_rows.hip and gpt_prefill.hip between enh_gemm_h16 products): embedding of [B, S, C] in one launch, per layer
 ln1 + time shift -> q|k|v -> causal flash attention -> proj + residual -> ln2 -> p0 -> relu^2 -> p1 + residual, the final LayerNorm and the head;
 optionally the per-position cross-entropy and its mean on the device.  Inference only: no autograd graph.
 
@@ -106,6 +106,26 @@ class GPT(nn.Module):
             module.bias.data.zero_()
             module.weight.data.fill_(1.0)
 
+    # ---- what forward() and sample() both begin with ----------------------------------------------
+    def _on_device_conds(self, conds: torch.Tensor, B: int, who: str) -> torch.Tensor:
+        """moves a module whose parameters are elsewhere to the device of `conds`; returns the [B] int64 column of the one condition token per row"""
+        if self.head.weight.device != conds.device:
+            self.to(conds.device)
+        conds = conds.reshape(B, -1)
+        if conds.shape[1] != 1:
+            raise ValueError(f"{who}: one condition token per row (cond_num_tokens == 1), got {conds.shape[1]}")
+        return conds[:, 0].to(torch.int64).contiguous()
+
+    @staticmethod
+    def _operand_dtype(use_fp16: bool, who: str) -> torch.dtype:
+        """use_fp16 -> the 16-bit operand format of ENH_PRECISION (default fp16), else f32: the exact mode"""
+        if not use_fp16:
+            return torch.float32
+        prec = os.environ.get("ENH_PRECISION", "fp16")
+        if prec not in OPERAND_DTYPE:
+            raise ValueError(f"{who}(use_fp16=True): ENH_PRECISION must be 'fp16' or 'bf16' for the 16-bit mode, got {prec!r}")
+        return OPERAND_DTYPE[prec]
+
     # ---- teacher-forced forward -------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, codes: torch.Tensor, conds: torch.Tensor, *, use_fp16: bool = True, return_loss: bool = False):
@@ -124,27 +144,16 @@ class GPT(nn.Module):
                                       "teacher-forced forward; note that the cached sample() does not compute the same logits: time_shift)")
         from ... import _C
         dev = codes.device
-        if self.head.weight.device != dev:
-            self.to(dev)
         B, T, V = codes.shape[0], self.img_num_tokens, self.vocab_img_size
         codes = codes.reshape(B, -1).to(torch.int64).contiguous()
         if codes.shape[1] != T:
             raise ValueError(f"GPT.forward: codes must hold img_num_tokens = {T} codes per row, got {codes.shape[1]}")
-        conds = conds.reshape(B, -1)
-        if conds.shape[1] != 1:
-            raise ValueError(f"GPT.forward: one condition token per row (cond_num_tokens == 1), got {conds.shape[1]}")
-        conds = conds[:, 0].to(torch.int64).contiguous()
+        conds = self._on_device_conds(conds, B, "GPT.forward")
         if int(codes.min()) < 0 or int(codes.max()) >= V:
             raise ValueError(f"GPT.forward: codes outside [0, {V})")
         if int(conds.min()) < 0 or int(conds.max()) >= self.vocab_cond_size:
             raise ValueError(f"GPT.forward: conds outside [0, {self.vocab_cond_size})")
-        if use_fp16:
-            prec = os.environ.get("ENH_PRECISION", "fp16")
-            if prec not in OPERAND_DTYPE:
-                raise ValueError(f"GPT.forward(use_fp16=True): ENH_PRECISION must be 'fp16' or 'bf16' for the 16-bit mode, got {prec!r}")
-            dt = OPERAND_DTYPE[prec]
-        else:
-            dt = torch.float32
+        dt = self._operand_dtype(use_fp16, "GPT.forward")
         chunk = max(1, min(B, int(self.forward_hidden_cap) // (T * 4 * self.embed_dim * (4 + (2 if use_fp16 else 0)))))
         logits = torch.empty(B, T, V, dtype=torch.float32, device=dev)
         nll = torch.empty(B, T, dtype=torch.float32, device=dev) if return_loss else None
@@ -249,12 +258,7 @@ class GPT(nn.Module):
         if not conds.is_cuda:
             raise RuntimeError("GPT.sample runs on a ROCm device only: conds must be a device tensor (there is no CPU path)")
         dev = conds.device
-        if self.head.weight.device != dev:
-            self.to(dev)
-        conds = conds.reshape(conds.shape[0], -1)
-        if conds.shape[1] != 1:
-            raise ValueError(f"GPT.sample: one condition token per row (cond_num_tokens == 1), got {conds.shape[1]}")
-        conds = conds[:, 0].to(torch.int64).contiguous()
+        conds = self._on_device_conds(conds, conds.shape[0], "GPT.sample")
         B, T, V = conds.shape[0], self.img_num_tokens, self.vocab_img_size
         if top_k is not None and not 1 <= int(top_k) <= V:
             raise ValueError(f"GPT.sample: top_k must be in [1, {V}], got {top_k}")
@@ -264,13 +268,7 @@ class GPT(nn.Module):
                 raise ValueError(f"GPT.sample: forced_codes outside [0, {V})")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        if use_fp16:
-            prec = os.environ.get("ENH_PRECISION", "fp16")
-            if prec not in OPERAND_DTYPE:
-                raise ValueError(f"GPT.sample(use_fp16=True): ENH_PRECISION must be 'fp16' or 'bf16' for the 16-bit mode, got {prec!r}")
-            dt = OPERAND_DTYPE[prec]
-        else:
-            dt = torch.float32
+        dt = self._operand_dtype(use_fp16, "GPT.sample")
         codes = torch.empty(B, T, dtype=torch.int64, device=dev)
         logits = torch.empty(B, T * V, dtype=torch.float32, device=dev) if return_logits else None
         for s in range(0, B, MAX_BATCH):

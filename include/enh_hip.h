@@ -53,7 +53,7 @@ typedef enh_h16 enh_bf16;  /* raw bfloat16 bits (bf16-only entries) */
 
 const char* enh_last_error(void);
 /* The symbol — as a profiler prints it: template arguments, no parameter list, e.g. "gemm_w256r_kernel<F16, false, 2, true>" — of the main kernel that
- * the calling thread's most recent enh_gemm_h16 / enh_gemm_h16_ws / enh_gemm_h16_dtanh_colsum / enh_gemm_bf16_split / enh_attention_forward(_dh) / stage-2 forward (gpt_prefill) call
+ * the calling thread's most recent enh_gemm_h16 / enh_gemm_h16_ws / enh_gemm_h16_dtanh_colsum / enh_gemm_bf16_split / enh_attention_forward(_dh) / stage-2 (gpt_decode, gpt_rows, gpt_prefill) call
  * enqueued: the GEMM or attention kernel, not the helpers that ride along (split-K second pass, column sums).  "" before the first such call.  The
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
@@ -583,8 +583,9 @@ int enh_skinny_gemm_h16(const enh_h16* x, const enh_h16* W, int64_t M, int64_t N
 size_t enh_decode_attention_workspace_bytes(int B, int H, int hs, int Tmax);
 int enh_decode_attention(const void* qkv, void* k_cache, void* v_cache, int B, int H, int hs, int Tmax, int t, void* out, void* workspace,
                          size_t workspace_bytes, int dtype, void* stream);
-/* LayerNorm of M <= 64 rows (biased variance, f32 statistics), D % 8 == 0, D <= 8192, times colscale[D] when given (time_mix, layers.py:60 at
- * T == 1); out_f32 and / or out_h16 */
+/* What enh_ln_timeshift (below) computes at S = 1, for a decode step's M <= 64 rows, in a kernel of its own whose statistics may differ from that
+ * one's by an ulp: LayerNorm (biased variance, f32 statistics), D % 8 == 0, D <= 8192, times colscale[D] when given (time_mix, layers.py:60 at
+ * T == 1: no shifted term); out_f32 and / or out_h16.  csrc/gpt_rows.hip, as enh_gpt_embed. */
 int enh_row_ln_scale(const float* x, const float* w, const float* b, const float* colscale, int M, int D, float eps, float* out_f32,
                      enh_h16* out_h16, int dtype, void* stream);
 /* out[b] = table[ids[b * id_stride]] + pos_row, b < B; table [V, C] f32, pos_row [C] f32, C % 4 == 0 (layers.py:280-281,290-291) */
@@ -607,7 +608,7 @@ int enh_sample_logits(const float* logits, int B, int V, float temperature, int 
                       int64_t logits_out_stride, uint8_t* mask_out, float* probs_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Stage-2 GPT, teacher-forced forward (csrc/gpt_prefill.hip; reference enhancing/modules/stage2/layers.py:57-97,132-136,193-211 with
+ * Stage-2 GPT, teacher-forced forward (csrc/gpt_prefill.hip: the attention, csrc/gpt_rows.hip: the row kernels; reference enhancing/modules/stage2/layers.py:57-97,132-136,193-211 with
  * cond_num_tokens == 1).  M = B S token rows at once: the wide products are enh_gemm_h16's (exact mode: enh_skinny_gemm_f32 in 64-row pieces),
  * these are the kernels between them.  No float atomics: the same bits on every run.
  * ------------------------------------------------------------------------------------------------ */

@@ -80,10 +80,14 @@ PREFILL_LABELS = ["gpt_prefill_causal_kernel<64, F16>", "gpt_prefill_causal_kern
                   "gpt_prefill_ln_kernel<F16>", "gpt_prefill_ln_kernel<BF16>", "gpt_prefill_relu_sq_kernel<F16, true, false>",
                   "gpt_prefill_relu_sq_kernel<BF16, false, false>", "gpt_prefill_relu_sq_kernel<BF16, true, true>", "gpt_prefill_ce_kernel",
                   "gpt_prefill_mean_kernel", "gpt_prefill_embed_kernel", "gpt_prefill_causal_f32_kernel"]
+# what the decode entry points report (tests/test_gpt_kernels_gpu.py reads them back after each call)
+DECODE_LABELS = [f"gpt_skinny_gemm_kernel<{ot}, {mt}>" for ot in ("F16", "BF16") for mt in (1, 2, 4)] + [
+    "gpt_skinny_gemm_f32_kernel", "gpt_decode_attn_kernel<F16, false>", "gpt_decode_attn_kernel<BF16, false>", "gpt_decode_attn_kernel<BF16, true>",
+    "gpt_row_ln_kernel<F16>", "gpt_row_ln_kernel<BF16>", "gpt_embed_kernel", "gpt_sample_kernel"]
 
 
 def test_prefill_labels_are_kernel_symbols_without_scratch():
-    """every label the stage-2 forward's launches report (enh_last_kernel) is exactly one kernel symbol of the shipped library, and none of the
+    """every label the launches of the stage-2 forward and of sampling report (enh_last_kernel) is exactly one kernel symbol of the shipped library, and none of the
     new kernels uses scratch (the D = 384 causal kernel holds 96 accumulator and 96 Q-fragment registers per lane)"""
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -92,7 +96,7 @@ def test_prefill_labels_are_kernel_symbols_without_scratch():
     if not os.path.exists(isa_lint.DEFAULT_SO) or not os.path.exists(isa_lint.LLVM + "/llvm-objdump"):
         pytest.skip("needs the built library and the ROCm llvm tools")
     stats = isa_lint.kernel_stats()
-    for label in PREFILL_LABELS:
+    for label in PREFILL_LABELS + DECODE_LABELS:
         hits = [n for n in stats if n.startswith(label + "(") or n.startswith("void " + label + "(")]
         assert len(hits) == 1, (label, hits)
     mine = [n for n in stats if "gpt_prefill_" in n]

@@ -1,4 +1,4 @@
-"""The decode-shaped kernels of stage-2 sampling (csrc/gpt_decode.hip), each against an fp64 statement of what it computes, with bounds worked out
+"""The decode-shaped kernels of stage-2 sampling (csrc/gpt_decode.hip and the row kernels of csrc/gpt_rows.hip), each against an fp64 statement of what it computes, with bounds worked out
 from the number formats (tests/util.py elem_bound and the reasoning written at each check); nothing here is a measured tolerance."""
 import math
 
@@ -217,6 +217,91 @@ def test_gpt_embed_reads_ids_from_device_memory_and_exact_product():
         pre, pmag = x.double() @ w.double().t() + bias.double(), x.double().abs() @ w.double().abs().t() + bias.double().abs()
         b_pre = (2 * (K // 64 + 6) + 8) * E24 * pmag            # the square: as in test_skinny_gemm_against_fp64
         assert_elementwise(out2, torch.relu(pre) ** 2, elem_bound(pre, (2 * torch.relu(pre) + b_pre) * pmag, K // 64 + 6), f"skinny_gemm_f32 relu^2 {M}x{N}x{K}")
+
+
+# ---------------------------------------------------------------------------------------------
+# every decode entry point names the kernel it launched (enh_last_kernel), at its smallest legal shape
+# ---------------------------------------------------------------------------------------------
+def _last():
+    from enhancing import _C
+    return _C.lib().enh_last_kernel().decode()
+
+
+def _stale():
+    """a call with another label in front of the checked one, so that a label left over from an earlier call cannot pass"""
+    from enhancing import _C
+    _C.mean_f32(torch.ones(8, device="cuda"), torch.empty(1, device="cuda"))
+    assert _last() == "gpt_prefill_mean_kernel"
+
+
+@pytest.mark.parametrize("fmt", ["fp16", "bf16"])
+@pytest.mark.parametrize("M, N, K, mt", [(1, 8, 8, 1), (17, 8, 8, 2), (33, 8, 8, 4), (3, 16, 6144, 1)])
+def test_skinny_gemm_names_its_kernel(M, N, K, mt, fmt):
+    """the three row-tile forms in both operand types; (3, 16, 6144) runs K slabs, and the label is still the product kernel's"""
+    from enhancing import _C
+    dt = H16[fmt]
+    g = _gen(M + N + K)
+    x = torch.randn(M, K, generator=g).to(dt).cuda()
+    w = (torch.randn(N, K, generator=g) / math.sqrt(K)).to(dt).cuda()
+    assert (_C.lib().enh_skinny_gemm_workspace_bytes(M, N, K) > 0) == (K == 6144)
+    out = torch.full((M, N), float("nan"), device="cuda")
+    _stale()
+    _C.skinny_gemm(x, w, out)
+    assert _last() == f"gpt_skinny_gemm_kernel<{'F16' if fmt == 'fp16' else 'BF16'}, {mt}>"
+    ref, mag = x.double() @ w.double().t(), x.double().abs() @ w.double().abs().t()
+    assert_elementwise(out, ref, elem_bound(ref, mag, K), f"skinny_gemm M={M} N={N} K={K} {fmt}")
+
+
+@pytest.mark.parametrize("fmt, label", [("fp16", "gpt_decode_attn_kernel<F16, false>"), ("bf16", "gpt_decode_attn_kernel<BF16, false>"),
+                                        ("f32", "gpt_decode_attn_kernel<BF16, true>")])
+def test_decode_attention_names_its_kernel(fmt, label):
+    from enhancing import _C
+    dt = H16.get(fmt, torch.float32)
+    g = _gen(3)
+    qkv = torch.randn(1, 192, generator=g).to(dt).cuda()
+    kc, vc = (torch.full((1, 1, 4, 64), float("nan"), dtype=dt, device="cuda") for _ in range(2))
+    out = torch.full((1, 64), float("nan"), dtype=dt, device="cuda")
+    _stale()
+    _C.decode_attention(qkv, kc, vc, 0, out)
+    assert _last() == label
+    # one key: its probability is exactly 1 and the output is v itself
+    assert torch.equal(out.double(), qkv[:, 128:].double()) and torch.equal(kc[0, 0, 0], qkv[0, 64:128]) and torch.equal(vc[0, 0, 0], qkv[0, 128:])
+
+
+def test_row_kernels_sampler_and_exact_product_name_their_kernels():
+    from enhancing import _C
+    g = _gen(9)
+    x, w, b = (0.5 + 2.0 * torch.randn(1, 8, generator=g)).cuda(), (1.0 + 0.1 * torch.randn(8, generator=g)).cuda(), (0.1 * torch.randn(8, generator=g)).cuda()
+    for odt, label in ((torch.float16, "gpt_row_ln_kernel<F16>"), (torch.bfloat16, "gpt_row_ln_kernel<BF16>")):
+        out = torch.full((1, 8), float("nan"), dtype=odt, device="cuda")
+        _stale()
+        _C.row_ln_scale(x, w, b, out)
+        assert _last() == label
+        # the bound of test_row_ln_scale_against_fp64
+        x64 = x.double()
+        rstd = 1.0 / torch.sqrt(x64.var(-1, unbiased=False, keepdim=True) + 1e-5)
+        xhat = (x64 - x64.mean(-1, keepdim=True)) * rstd
+        ref = xhat * w.double() + b.double()
+        bound = 64 * E24 * (xhat.abs() + x64.abs().mean(-1, keepdim=True) * rstd) * w.double().abs() + 8 * E24 * b.double().abs()
+        assert_elementwise(out, ref, bound + U16[odt] * ref.abs() + SUB16.get(odt, 0.0), f"row_ln_scale -> {odt}")
+    g = _gen(4)
+    table, pos, ids = torch.randn(5, 4, generator=g).cuda(), torch.randn(4, generator=g).cuda(), torch.tensor([3]).cuda()
+    out = torch.full((1, 4), float("nan"), device="cuda")
+    _stale()
+    _C.gpt_embed(table, ids, pos, out)
+    assert _last() == "gpt_embed_kernel" and torch.equal(out, table[ids] + pos)
+    logits = torch.tensor([[0.5, -1.0, 2.0, 0.0, 1.5, -0.5, 1.0, -2.0]]).cuda()
+    code = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+    _stale()
+    _C.sample_logits(logits, code, top_k=1, uniforms=torch.tensor([0.5]).cuda())      # top_k = 1 keeps the largest logit alone
+    assert _last() == "gpt_sample_kernel" and code.item() == 2
+    xs, ws = torch.randn(1, 8, generator=g).cuda(), torch.randn(1, 8, generator=g).cuda()
+    out = torch.full((1, 1), float("nan"), device="cuda")
+    _stale()
+    _C.skinny_gemm_f32(xs, ws, out)
+    assert _last() == "gpt_skinny_gemm_f32_kernel"
+    ref, mag = xs.double() @ ws.double().t(), xs.double().abs() @ ws.double().abs().t()
+    assert_elementwise(out, ref, elem_bound(ref, mag, 8 // 64 + 6), "skinny_gemm_f32 1x1x8")
 
 
 # ---------------------------------------------------------------------------------------------
