@@ -143,11 +143,18 @@ SIGNATURES = {
     "enh_relu_sq_h16": (_i32, [_vp, _vp, _i64, _i32, _vp]),
     "enh_cross_entropy_rows": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "enh_mean_f32": (_i32, [_vp, _i64, _vp, _vp]),
+    "enh_causal_attention_backward_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "enh_causal_attention_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _i32, _vp]),
+    "enh_cross_entropy_backward": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _i32, _vp]),
+    "enh_relu_sq_backward": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "enh_ln_timeshift_backward_workspace_bytes": (_sz, [_i64, _i32]),
+    "enh_ln_timeshift_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _i32, _vp]),
+    "enh_gpt_embed_seq_backward": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "enh_sample_logits": (_i32, [_vp, _i32, _i32, _f32, _i32, _f32, _vp, _u64, _u32, _u32, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _LIB = None
-ABI_VERSION = 24  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 25  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -1137,3 +1144,66 @@ def cross_entropy_rows(logits, target, nll, mean=None):
 
 def mean_f32(v, mean):
     _check(lib().enh_mean_f32(_p(v, F32, "v"), v.numel(), _p(mean, F32, "mean"), _stream()), "enh_mean_f32")
+
+
+# ------------------------------------------------------------------------------------------------
+# stage-2 backward (csrc/gpt_attn_bwd.hip: the attention; the row kernels: csrc/gpt_rows.hip)
+# ------------------------------------------------------------------------------------------------
+def causal_attention_backward(qkv, out, dout, lse, B: int, N: int, H: int, D: int, dqkv, scale: Optional[float] = None):
+    """dqkv [B,N,3*H*D] of causal_attention from qkv, the out and lse [B,H,N] it stored, and dout [B,N,H*D]; 16-bit tensors of one format"""
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    if qkv.numel() != B * N * 3 * H * D or dqkv.numel() != qkv.numel() or out.numel() != B * N * H * D or dout.numel() != out.numel() or lse.numel() != B * H * N:
+        raise RuntimeError(f"causal_attention_backward: qkv {tuple(qkv.shape)} out {tuple(out.shape)} dout {tuple(dout.shape)} lse {tuple(lse.shape)} "
+                           f"do not fit B={B} N={N} H={H} D={D}")
+    L = lib()
+    nb = L.enh_causal_attention_backward_workspace_bytes(B, N, H)
+    ws = _workspace(nb, qkv.device)
+    # MFMA work of an unsplit kernel on the lower triangle: S and dP twice (both kernels), dQ, dK, dV
+    _timed(None, 7.0 * B * H * N * (N + 1) * D,
+           lambda: _check(L.enh_causal_attention_backward(_p(qkv, H16, "qkv"), _p(out, H16, "out"), _p(dout, H16, "dout"), _p(lse, F32, "lse"), B, N, H, D, scale,
+                                                          _p(dqkv, H16, "dqkv"), _p(ws), ws.numel(), _dt(qkv, out, dout, dqkv), _stream()),
+                          "enh_causal_attention_backward"))
+
+
+def cross_entropy_backward(logits, target, nll, dlogits, gscale: float):
+    """nll[m] as cross_entropy_rows (the same bits) and dlogits [M,V] 16-bit = (softmax(logits[m]) - onehot(target[m])) * gscale; V % 8 == 0"""
+    M, V = logits.shape
+    if target.numel() != M or nll.numel() != M or tuple(dlogits.shape) != (M, V):
+        raise RuntimeError("cross_entropy_backward: one target and one result per row, dlogits as the logits")
+    _timed(None, 6.0 * M * V, lambda: _check(lib().enh_cross_entropy_backward(_p(logits, F32, "logits"), _p(target, I64, "target"), M, V, float(gscale),
+                                                                               _p(nll, F32, "nll"), _p(dlogits, H16, "dlogits"), _dt(dlogits), _stream()),
+                                             "enh_cross_entropy_backward"), unit="byte")
+
+
+def relu_sq_backward(dy, y, dx):
+    """dx (16-bit) = dy (f32) * 2 relu(h), relu(h) = sqrt(y) from the stored 16-bit y = relu(h)^2; n % 8 == 0"""
+    if dy.numel() != y.numel() or dx.numel() != y.numel():
+        raise RuntimeError("relu_sq_backward: dy, y and dx must be equally long")
+    _timed(None, 8.0 * y.numel(), lambda: _check(lib().enh_relu_sq_backward(_p(dy, F32, "dy"), _p(y, H16, "y"), _p(dx, H16, "dx"), y.numel(), _dt(y, dx), _stream()),
+                                                 "enh_relu_sq_backward"), unit="byte")
+
+
+def ln_timeshift_backward(dy, x, w, S: int, dx, dw, db, b=None, colscale=None, dcolscale=None, dres=None, dx16=None, eps: float = 1e-5, accumulate: bool = False):
+    """backward of ln_timeshift: dy, x [M,D] f32 -> dx f32 (+ dres), dx16 an optional 16-bit copy; dw, db, dcolscale [D] set or (accumulate) added to"""
+    M, D = x.shape
+    L = lib()
+    nb = L.enh_ln_timeshift_backward_workspace_bytes(M, D)
+    ws = _workspace(nb, x.device)
+    _timed(None, 4.0 * M * D * (3 + (1 if dres is not None else 0)),
+           lambda: _check(L.enh_ln_timeshift_backward(_p(dy, F32, "dy"), _p(x, F32, "x"), _p(w, F32, "w"), _p(b, F32, "b"), _p(colscale, F32, "colscale"),
+                                                      _p(dres, F32, "dres"), M, int(S), D, eps, _p(dx, F32, "dx"), _p(dx16, H16, "dx16"), _p(dw, F32, "dw"),
+                                                      _p(db, F32, "db"), _p(dcolscale, F32, "dcolscale"), int(accumulate), _p(ws), ws.numel(), _dt(dx16),
+                                                      _stream()), "enh_ln_timeshift_backward"), unit="byte")
+
+
+def gpt_embed_seq_backward(g, conds, codes, dtok_cond, dpos_cond, dtok_code, dpos_code, accumulate: bool = False):
+    """gradients of gpt_embed_seq's four tables from g [B,S,C] f32: dtok_cond [Vc,C], dpos_cond [C], dtok_code [V,C], dpos_code [P >= S-1, C]"""
+    B, S, C = g.shape
+    if conds.dtype != I64 or conds.numel() != B or codes.dtype != I64 or codes.dim() != 2 or codes.shape[0] != B or codes.shape[1] < S - 1 or codes.stride(1) != 1:
+        raise RuntimeError("gpt_embed_seq_backward: conds [B] and codes [B,T >= S-1] must be int64 device tensors with contiguous rows")
+    _timed(None, 4.0 * (B * S * C + dtok_cond.numel() + dtok_code.numel() + dpos_code.numel() + C),
+           lambda: _check(lib().enh_gpt_embed_seq_backward(_p(g, F32, "g"), _p(conds, I64, "conds"), ctypes.c_void_p(codes.data_ptr()),
+                                                           codes.stride(0) if B > 1 else codes.shape[1], B, S, C, dtok_cond.shape[0], dtok_code.shape[0],
+                                                           dpos_code.shape[0], _p(dtok_cond, F32, "dtok_cond"), _p(dpos_cond, F32, "dpos_cond"),
+                                                           _p(dtok_code, F32, "dtok_code"), _p(dpos_code, F32, "dpos_code"), int(accumulate), _stream()),
+                          "enh_gpt_embed_seq_backward"), unit="byte")

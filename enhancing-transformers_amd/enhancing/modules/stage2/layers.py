@@ -1,4 +1,5 @@
-"""Stage-2 GPT prior (reference enhancing/modules/stage2/layers.py:23-303): sampling and the teacher-forced forward, no training.
+"""Stage-2 GPT prior (reference enhancing/modules/stage2/layers.py:23-303): sampling, the teacher-forced forward, and the loss with its gradients
+(no optimizer step yet).
 
 The modules below are parameter containers with the reference's names, shapes and init, so its checkpoints and yaml load.  `GPT.sample` is the
 reference's cached sampling loop restated per step on the device (csrc/gpt_decode.hip, gpt_rows.hip).  With cond_num_tokens == 1 every step is one token per
@@ -14,7 +15,13 @@ the host: the drawn codes stay in device memory and the next step's embedding ke
 ln1 + time shift -> q|k|v -> causal flash attention -> proj + residual -> ln2 -> p0 -> relu^2 -> p1 + residual, the final LayerNorm and the head;
 optionally the per-position cross-entropy and its mean on the device.  Inference only: no autograd graph.
 
-Left out: RQTransformer, stage-2 backward and training, more than one condition token, HIP-graph capture, a relu^2 GEMM epilogue."""
+`GPT.forward_backward` is that forward with its activations kept per layer, followed by a hand-written backward on the device: the
+loss gradient fused with the cross-entropy, every product an enh_gemm_h16 call (weight gradients accumulated in f32 into one flat gradient buffer
+that every `p.grad` is a view into), the f32 gradient of the residual stream carried through the LayerNorm / time-shift, relu^2 and embedding
+backward kernels of csrc/gpt_rows.hip and the causal flash-attention backward of csrc/gpt_attn_bwd.hip.  16-bit operand formats only.
+
+Left out: RQTransformer, the optimizer step and training_step, overflow detection and loss-scale updates, an exact-f32 backward, more than one
+condition token, HIP-graph capture, relu^2 / LayerNorm fused into GEMM epilogues."""
 import os
 from typing import Optional, Tuple
 
@@ -27,6 +34,7 @@ MAX_VOCAB = 16384       # enh_sample_logits
 MAX_HEAD = 384          # enh_decode_attention
 MAX_TOKENS = 8192       # enh_decode_attention: slots of the k / v cache
 FORWARD_HIDDEN_CAP = 2 << 30   # bytes of forward()'s [chunk T, 4C] hidden activation (f32 + operand copy): shipped size, 6 sequences per chunk
+BACKWARD_SAVED_CAP = 16 << 30  # bytes of forward_backward()'s saved activations: shipped size 24 x 172,096 B per token, 4 sequences of 1024 per chunk
 OPERAND_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
 
 
@@ -96,6 +104,10 @@ class GPT(nn.Module):
         self._operands = {}       # operand format -> (versions of the masters, per-layer operand copies)
         self._fwd_states = {}     # (chunk, dtype, device) -> the buffers of forward()
         self.forward_hidden_cap = FORWARD_HIDDEN_CAP
+        self.backward_saved_cap = BACKWARD_SAVED_CAP      # bytes of forward_backward()'s saved activations of all layers in one chunk
+        self._bwd_states = {}     # (chunk, dtype, device) -> the buffers of forward_backward()
+        self._grad_key = None     # the parameters whose .grad are views into flat_grad
+        self.flat_grad = None
 
     def _init_weights(self, module: nn.Module) -> None:
         if isinstance(module, (nn.Linear, nn.Embedding)):
@@ -145,14 +157,7 @@ class GPT(nn.Module):
         from ... import _C
         dev = codes.device
         B, T, V = codes.shape[0], self.img_num_tokens, self.vocab_img_size
-        codes = codes.reshape(B, -1).to(torch.int64).contiguous()
-        if codes.shape[1] != T:
-            raise ValueError(f"GPT.forward: codes must hold img_num_tokens = {T} codes per row, got {codes.shape[1]}")
-        conds = self._on_device_conds(conds, B, "GPT.forward")
-        if int(codes.min()) < 0 or int(codes.max()) >= V:
-            raise ValueError(f"GPT.forward: codes outside [0, {V})")
-        if int(conds.min()) < 0 or int(conds.max()) >= self.vocab_cond_size:
-            raise ValueError(f"GPT.forward: conds outside [0, {self.vocab_cond_size})")
+        codes, conds = self._check_inputs(codes, conds, "GPT.forward")
         dt = self._operand_dtype(use_fp16, "GPT.forward")
         chunk = max(1, min(B, int(self.forward_hidden_cap) // (T * 4 * self.embed_dim * (4 + (2 if use_fp16 else 0)))))
         logits = torch.empty(B, T, V, dtype=torch.float32, device=dev)
@@ -169,6 +174,159 @@ class GPT(nn.Module):
         _C.mean_f32(nll.view(-1), mean)
         return logits, nll, mean[0]
 
+    # ---- teacher-forced loss and its gradients -----------------------------------------------------
+    def _check_inputs(self, codes, conds, who: str):
+        """what forward() and forward_backward() accept: (codes [B, T] int64, conds [B] int64) on the device, ranges checked"""
+        B, T, V = codes.shape[0], self.img_num_tokens, self.vocab_img_size
+        codes = codes.reshape(B, -1).to(torch.int64).contiguous()
+        if codes.shape[1] != T:
+            raise ValueError(f"{who}: codes must hold img_num_tokens = {T} codes per row, got {codes.shape[1]}")
+        conds = self._on_device_conds(conds, B, who)
+        if int(codes.min()) < 0 or int(codes.max()) >= V:
+            raise ValueError(f"{who}: codes outside [0, {V})")
+        if int(conds.min()) < 0 or int(conds.max()) >= self.vocab_cond_size:
+            raise ValueError(f"{who}: conds outside [0, {self.vocab_cond_size})")
+        return codes, conds
+
+    def saved_bytes_per_token(self) -> int:
+        """bytes forward_backward keeps per token row for ALL layers: per layer the f32 inputs of ln1 and ln2 (4C + 4C), the
+        16-bit operands a, qkv, att, a2 and hid (2C + 6C + 2C + 2C + 8C) and the attention's lse (4 H)"""
+        return len(self.blocks) * (28 * self.embed_dim + 4 * self.n_heads)
+
+    def _flat_grads(self, dev) -> torch.Tensor:
+        """one flat f32 buffer that every parameter's .grad is a view into (engine/stage1.py ParamStore's layout: registration order, every
+        parameter padded to 64 elements), allocated on first use and kept while the parameters stay where they are"""
+        params = list(self.named_parameters())
+        key = (str(dev),) + tuple(p.data_ptr() for _, p in params)
+        if self._grad_key != key or any(p.grad is None for _, p in params):
+            total, offs = 0, []
+            for _, p in params:
+                offs.append(total)
+                total += (p.numel() + 63) // 64 * 64
+            self.flat_grad = torch.zeros(total, dtype=torch.float32, device=dev)
+            for (_, p), o in zip(params, offs):
+                p.grad = self.flat_grad[o:o + p.numel()].view(p.shape)
+            self._grad_key = key
+        return self.flat_grad
+
+    def _backward_state(self, b: int, dt: torch.dtype, dev) -> dict:
+        """the buffers of a chunk of b sequences: row counts rounded up to 8 (the contraction length of a weight-gradient product), everything
+        zero at first so that the tail rows of an operand are finite; the tail rows of the gradient operands are zeroed again for a shorter chunk"""
+        key = (b, dt, str(dev))
+        st = self._bwd_states.get(key)
+        if st is None:
+            f32, C, H, V, T = torch.float32, self.embed_dim, self.n_heads, self.vocab_img_size, self.img_num_tokens
+            Mp = (b * T + 7) // 8 * 8
+            z = lambda *shape, dtype=dt: torch.zeros(*shape, dtype=dtype, device=dev)
+            saved = [dict(x=z(Mp, C, dtype=f32), a=z(Mp, C), qkv=z(Mp, 3 * C), att=z(Mp, C), lse=z(b * H * T, dtype=f32), x2=z(Mp, C, dtype=f32),
+                          a2=z(Mp, C), hid=z(Mp, 4 * C)) for _ in self.blocks]
+            st = dict(saved=saved, x=z(Mp, C, dtype=f32), a=z(Mp, C), hid32=z(Mp, 4 * C, dtype=f32), logits=z(Mp, V, dtype=f32), dlogits=z(Mp, V),
+                      g=z(Mp, C, dtype=f32), g2=z(Mp, C, dtype=f32), d32=z(Mp, C, dtype=f32), g16=z(Mp, C), dh16=z(Mp, 4 * C), dqkv=z(Mp, 3 * C),
+                      datt=z(Mp, C), dbqkv=z(3 * C, dtype=f32))
+            self._bwd_states = {key: st}      # one chunk size at a time, as _forward_state
+        return st
+
+    @torch.no_grad()
+    def forward_backward(self, codes: torch.Tensor, conds: torch.Tensor, *, use_fp16: bool = True, loss_scale: float = 1.0) -> torch.Tensor:
+        """the teacher-forced loss and its gradients in one call: returns the unscaled mean cross-entropy over all B T positions (0-dim f32 on the
+        device: what forward(..., return_loss=True)[2] returns, and with the same chunking the same bits) and leaves in `p.grad` of EVERY
+        parameter loss_scale x the gradient of that mean (f32, views into the flat buffer `flat_grad`: what GradScaler.scale(loss).backward()
+        leaves).  The call SETS the gradients; rows of the token tables whose id does not occur are exactly zero.
+
+        use_fp16=True runs the 16-bit operand format of ENH_PRECISION: every product is an enh_gemm_h16 call (weight gradients accumulate in f32),
+        the residual stream's gradient stays f32, the kernels between the products are csrc/gpt_rows.hip's and csrc/gpt_attn_bwd.hip's.  The
+        exact-f32 backward is not built: use_fp16=False raises.  Device tensors only.  Batches run in chunks of whole sequences sized so that the
+        activations saved for the backward stay under `backward_saved_cap` bytes (saved_bytes_per_token() per token row); weight gradients
+        accumulate across the chunks in a fixed order, so two runs give the same bits.  Any B T works: a chunk's row buffers are rounded up to 8 rows
+        and the tail rows of every gradient operand are zero.  No optimizer step, no overflow check: later work."""
+        if not use_fp16:
+            raise NotImplementedError("GPT.forward_backward(use_fp16=False): the exact-f32 backward is not built; use the 16-bit operand format")
+        if not (torch.is_tensor(codes) and torch.is_tensor(conds) and codes.is_cuda and conds.is_cuda):
+            raise NotImplementedError("GPT.forward_backward runs on a ROCm device only: codes and conds must be device tensors (there is no CPU path)")
+        from ... import _C
+        dev = codes.device
+        B, T, V = codes.shape[0], self.img_num_tokens, self.vocab_img_size
+        codes, conds = self._check_inputs(codes, conds, "GPT.forward_backward")
+        dt = self._operand_dtype(True, "GPT.forward_backward")
+        chunk = max(1, min(B, int(self.backward_saved_cap) // (T * self.saved_bytes_per_token())))
+        self._flat_grads(dev)
+        st = self._backward_state(chunk, dt, dev)
+        nll = torch.empty(B, T, dtype=torch.float32, device=dev)
+        gscale = float(loss_scale) / float(B * T)
+        for s in range(0, B, chunk):
+            e = min(s + chunk, B)
+            self._backward_rows(st, codes[s:e], conds[s:e], nll[s:e], dt, gscale, accumulate=s > 0)
+        mean = torch.empty(1, dtype=torch.float32, device=dev)
+        _C.mean_f32(nll.view(-1), mean)
+        return mean[0]
+
+    def _backward_rows(self, st, codes, conds, nll, dt, gscale: float, accumulate: bool) -> None:
+        """one chunk: the saving forward, then the backward of DESIGN.md §3.7, setting (accumulate=False) or adding to every parameter's gradient"""
+        from ... import _C
+        b, T, C, H, V = codes.shape[0], self.img_num_tokens, self.embed_dim, self.n_heads, self.vocab_img_size
+        M, hs = b * T, C // H
+        Mp = (M + 7) // 8 * 8
+        ops = self._operand_copies(dt)
+        saved = st["saved"]
+        logits, dlogits, g, g2, d32, g16, dh16, dqkv, datt, hid32 = (st[k][:M] for k in ("logits", "dlogits", "g", "g2", "d32", "g16", "dh16", "dqkv",
+                                                                                         "datt", "hid32"))
+        if Mp > M:      # rows M .. Mp - 1 of the gradient operands may hold a longer chunk's rows
+            for k in ("dlogits", "g16", "dh16", "dqkv"):
+                st[k][M:Mp].zero_()
+        self._forward_rows(st, codes, conds, logits.view(b, T, V), dt, saved=saved)
+
+        def wgrad(dy, inp, grad, n_out: int, k_in: int, lda=None):      # grad [n_out, k_in] (+)= dy^T inp over the chunk's Mp rows
+            _C.gemm(dy, inp, n_out, k_in, Mp, trans_a=True, trans_b=True, accumulate=accumulate, out_f32=grad, lda=lda, ldb=k_in)
+
+        def dgrad(dy, w, out):      # out [M, K] = dy [M, N] w [N, K]
+            N, K = w.shape
+            if out.dtype == torch.float32:
+                _C.gemm(dy, w, M, K, N, trans_b=True, out_f32=out)
+            else:
+                _C.gemm(dy, w, M, K, N, trans_b=True, out_bf16=out)
+
+        _C.cross_entropy_backward(logits, codes.reshape(-1), nll.view(-1), dlogits, gscale)
+        wgrad(st["dlogits"], st["a"], self.head.weight.grad, V, C)
+        dgrad(dlogits, ops["head"], d32)
+        ln = self.layer_norm
+        _C.ln_timeshift_backward(d32, st["x"][:M], ln.weight, T, g, ln.weight.grad, ln.bias.grad, dx16=g16, eps=ln.eps, accumulate=accumulate)
+        for i in range(len(self.blocks) - 1, -1, -1):
+            blk, W, sv = self.blocks[i], ops["layers"][i], saved[i]
+            at, ml = blk.attn, blk.mlp
+            # p1, relu^2, p0
+            wgrad(st["g16"], sv["hid"], ml.p1.weight.grad, C, 4 * C)
+            if ml.p1.bias is not None:
+                _C.colsum(g16, M, C, ml.p1.bias.grad, accumulate)
+            dgrad(g16, W["w1"], hid32)
+            _C.relu_sq_backward(hid32, sv["hid"][:M], dh16)
+            wgrad(st["dh16"], sv["a2"], ml.p0.weight.grad, 4 * C, C)
+            if ml.p0.bias is not None:
+                _C.colsum(dh16, M, 4 * C, ml.p0.bias.grad, accumulate)
+            dgrad(dh16, W["w0"], d32)
+            _C.ln_timeshift_backward(d32, sv["x2"][:M], blk.ln2.weight, T, g2, blk.ln2.weight.grad, blk.ln2.bias.grad, dres=g, dx16=g16, eps=blk.ln2.eps,
+                                     accumulate=accumulate)
+            # proj, attention, q | k | v
+            wgrad(st["g16"], sv["att"], at.proj.weight.grad, C, C)
+            if at.proj.bias is not None:
+                _C.colsum(g16, M, C, at.proj.bias.grad, accumulate)
+            dgrad(g16, W["wproj"], datt)
+            _C.causal_attention_backward(sv["qkv"][:M], sv["att"][:M], datt, sv["lse"][:b * H * T], b, T, H, hs, dqkv)
+            flat = st["dqkv"].view(-1)      # the gradient of the fused [3C, C] operand, split back: column block j of dqkv is lin's output gradient
+            for j, lin in enumerate((at.query, at.key, at.value)):
+                wgrad(flat[j * C:], sv["a"], lin.weight.grad, C, C, lda=3 * C)
+            if at.query.bias is not None:
+                _C.colsum(dqkv, M, 3 * C, st["dbqkv"], False)
+                for j, lin in enumerate((at.query, at.key, at.value)):
+                    if accumulate:
+                        lin.bias.grad.add_(st["dbqkv"][j * C:(j + 1) * C])
+                    else:
+                        lin.bias.grad.copy_(st["dbqkv"][j * C:(j + 1) * C])
+            dgrad(dqkv, W["wqkv"], d32)
+            _C.ln_timeshift_backward(d32, sv["x"][:M], blk.ln1.weight, T, g, blk.ln1.weight.grad, blk.ln1.bias.grad, b=blk.ln1.bias, colscale=W["time_mix"],
+                                     dcolscale=at.time_mix.grad.view(-1), dres=g2, dx16=g16, eps=blk.ln1.eps, accumulate=accumulate)
+        _C.gpt_embed_seq_backward(g.view(b, T, C), conds, codes, self.tok_emb_cond.weight.grad, self.pos_emb_cond.grad.view(-1), self.tok_emb_code.weight.grad,
+                                  self.pos_emb_code.grad.view(-1, C), accumulate)
+
     def _forward_state(self, b: int, dt: torch.dtype, dev) -> dict:
         """the buffers of a chunk of b sequences, kept per (b, dtype) from call to call; a shorter last chunk uses their leading rows"""
         key = (b, dt, str(dev))
@@ -181,13 +339,15 @@ class GPT(nn.Module):
             self._fwd_states = {key: st}      # one chunk size at a time: the buffers of a shipped-size chunk are gigabytes
         return st
 
-    def _forward_rows(self, st, codes, conds, logits, dt) -> None:
-        """one chunk of b whole sequences in the leading b T rows of the buffers `st`: logits [b, T, V] f32"""
+    def _forward_rows(self, st, codes, conds, logits, dt, saved=None) -> None:
+        """one chunk of b whole sequences in the leading b T rows of the buffers `st`: logits [b, T, V] f32.  saved (forward_backward): one dict of
+        buffers per layer; the layer's input x, a (ln1), qkv, att, lse, x2, a2 (ln2) and hid then stay there instead of in the shared buffers of
+        `st`, and the last layer's output goes to st["x"].  The launches and their arguments are the same: so are the bits."""
         from ... import _C
         b, T, C, H, V = codes.shape[0], self.img_num_tokens, self.embed_dim, self.n_heads, self.vocab_img_size
         M, hs = b * T, C // H
         ops = self._operand_copies(dt)
-        x, x2, a, qkv, att, hid32, hid = (None if st[k] is None else st[k][:M] for k in ("x", "x2", "a", "qkv", "att", "hid32", "hid"))
+        x, x2, a, qkv, att, hid32, hid = (None if st.get(k) is None else st[k][:M] for k in ("x", "x2", "a", "qkv", "att", "hid32", "hid"))
         if dt == torch.float32:
             def linear(inp, w, out, bias=None, res=None, relu_sq=False):      # tree-ordered sums: enh_gemm_f32 adds K terms in ascending order (DESIGN §3.5)
                 for m0 in range(0, M, MAX_BATCH):
@@ -200,22 +360,31 @@ class GPT(nn.Module):
                     _C.gemm(inp, w, M, N, K, bias=bias, res=res, res_rows=M if res is not None else 0, out_f32=out)
                 else:
                     _C.gemm(inp, w, M, N, K, bias=bias, out_bf16=out)
+        x_out, a2, lse = x, a, None
+        if saved is not None:
+            x = saved[0]["x"][:M]
         _C.gpt_embed_seq(conds, codes, self.tok_emb_cond.weight.detach(), self.pos_emb_cond.detach()[0, 0], self.tok_emb_code.weight.detach(),
                          self.pos_emb_code.detach()[0], x.view(b, T, C))
-        for blk, W in zip(self.blocks, ops["layers"]):
+        for i, (blk, W) in enumerate(zip(self.blocks, ops["layers"])):
+            if saved is not None:
+                a, qkv, att, x2, a2, hid = (saved[i][k][:M] for k in ("a", "qkv", "att", "x2", "a2", "hid"))
+                lse = saved[i]["lse"][:b * H * T]
+                x_out = saved[i + 1]["x"][:M] if i + 1 < len(saved) else st["x"][:M]
             _C.ln_timeshift(x, blk.ln1.weight, blk.ln1.bias, a, T, colscale=W["time_mix"], eps=blk.ln1.eps)
             linear(a, W["wqkv"], qkv, bias=W["bqkv"])
-            _C.causal_attention(qkv, b, T, H, hs, att)
+            _C.causal_attention(qkv, b, T, H, hs, att, lse=lse)
             linear(att, W["wproj"], x2, bias=blk.attn.proj.bias, res=x)
-            _C.ln_timeshift(x2, blk.ln2.weight, blk.ln2.bias, a, T, eps=blk.ln2.eps)
+            _C.ln_timeshift(x2, blk.ln2.weight, blk.ln2.bias, a2, T, eps=blk.ln2.eps)
             if dt == torch.float32:
-                linear(a, W["w0"], hid32, bias=blk.mlp.p0.bias, relu_sq=True)
-                linear(hid32, W["w1"], x, bias=blk.mlp.p1.bias, res=x2)
+                linear(a2, W["w0"], hid32, bias=blk.mlp.p0.bias, relu_sq=True)
+                linear(hid32, W["w1"], x_out, bias=blk.mlp.p1.bias, res=x2)
             else:
                 # relu^2 on the f32 product, one rounding to the operand format (in place on a 16-bit product it would be two)
-                linear(a, W["w0"], hid32, bias=blk.mlp.p0.bias)
+                linear(a2, W["w0"], hid32, bias=blk.mlp.p0.bias)
                 _C.relu_sq(hid, hid32)
-                linear(hid, W["w1"], x, bias=blk.mlp.p1.bias, res=x2)
+                linear(hid, W["w1"], x_out, bias=blk.mlp.p1.bias, res=x2)
+            x = x_out
+        a = st["a"][:M]
         _C.ln_timeshift(x, self.layer_norm.weight, self.layer_norm.bias, a, T, eps=self.layer_norm.eps)
         linear(a, ops["head"], logits.view(M, V))
 

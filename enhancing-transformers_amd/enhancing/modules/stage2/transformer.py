@@ -1,6 +1,7 @@
 """CondTransformer (reference enhancing/modules/stage2/transformer.py:23-95): a condition model, a frozen stage-1 tokenizer and the GPT prior; `sample`
 draws codes on the device and decodes them with the tokenizer; `forward` / `validation_step` give the teacher-forced logits and the reference's
-val/total_loss.  Training (`training_step`, `configure_optimizers`) is not built."""
+val/total_loss; `loss_and_grads` returns the training loss and leaves the gradient of every GPT parameter on the device (GPT.forward_backward).
+The optimizer step (`training_step`, `configure_optimizers`) is not built."""
 from typing import List, Optional, Tuple
 
 import torch
@@ -74,15 +75,29 @@ class CondTransformer(nn.Module):
         self.logged[name] = value
 
     @torch.no_grad()
-    def shared_step(self, batch, batch_idx: int) -> torch.Tensor:
-        """reference transformer.py:107-118: tokenize the images, encode the condition, run the teacher-forced forward and take the mean
-        cross-entropy of every code given the condition and the codes before it, on the device (enh_cross_entropy_rows)"""
+    def _tokenize(self, batch) -> Tuple[torch.Tensor, torch.Tensor]:
+        """reference transformer.py:107-113: (codes of the batch's images from the frozen tokenizer, the encoded condition [B, 1]) on the device"""
         images = self.get_input(batch, self.stage1_model.image_key)
         conds = self.get_input(batch, self.cond_key)
         codes = self.stage1_model.encode_codes(images).detach()
         conds = self.cond_model.encode_codes(conds).detach()
-        conds = conds.to(codes.device).view(conds.shape[0], -1)
+        return codes, conds.to(codes.device).view(conds.shape[0], -1)
+
+    @torch.no_grad()
+    def shared_step(self, batch, batch_idx: int) -> torch.Tensor:
+        """reference transformer.py:107-118: tokenize the images, encode the condition, run the teacher-forced forward and take the mean
+        cross-entropy of every code given the condition and the codes before it, on the device (enh_cross_entropy_rows)"""
+        codes, conds = self._tokenize(batch)
         _, _, loss = self.transformer(codes, conds, return_loss=True)
+        return loss
+
+    def loss_and_grads(self, batch, batch_idx: int = 0, *, loss_scale: float = 1.0) -> torch.Tensor:
+        """shared_step's prologue, then GPT.forward_backward: returns the unscaled training loss (also logged as train/total_loss) and leaves
+        loss_scale x its gradient in `.grad` of every parameter of the transformer.  What a training step runs before its optimizer step, which
+        is not built."""
+        codes, conds = self._tokenize(batch)
+        loss = self.transformer.forward_backward(codes, conds, loss_scale=loss_scale)
+        self.log("train/total_loss", loss, on_step=True, on_epoch=True, prog_bar=True, logger=True)
         return loss
 
     def validation_step(self, batch, batch_idx: int) -> torch.Tensor:
@@ -92,7 +107,9 @@ class CondTransformer(nn.Module):
         return loss
 
     def training_step(self, batch, batch_idx: int, optimizer_idx: int = 0):
-        raise NotImplementedError("stage-2 training is not built (no backward pass of the GPT): CondTransformer samples and validates")
+        raise NotImplementedError("stage-2 training is not built (no optimizer step for the GPT yet): CondTransformer samples, validates and, "
+                                  "with loss_and_grads, computes the loss and its gradients")
 
     def configure_optimizers(self):
-        raise NotImplementedError("stage-2 training is not built (no backward pass of the GPT): CondTransformer samples and validates")
+        raise NotImplementedError("stage-2 training is not built (no optimizer step for the GPT yet): CondTransformer samples, validates and, "
+                                  "with loss_and_grads, computes the loss and its gradients")

@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 24  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 25  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -634,6 +634,38 @@ int enh_relu_sq_h16(const float* x, void* y, int64_t n, int dtype, void* stream)
  * fixed-order pass writes mean[0] = sum(nll) / M.  enh_mean_f32 is that pass alone (the mean over several calls' rows). */
 int enh_cross_entropy_rows(const float* logits, const int64_t* target, int64_t M, int V, float* nll, float* mean, void* stream);
 int enh_mean_f32(const float* v, int64_t M, float* mean, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 GPT, backward of the teacher-forced forward (csrc/gpt_attn_bwd.hip: the attention, csrc/gpt_rows.hip: the row kernels).  The gradient
+ * products are enh_gemm_h16's (trans_a / trans_b / accumulate); these are the kernels between them.  No float atomics: the same bits on every run.
+ * ------------------------------------------------------------------------------------------------ */
+/* dqkv [B, N, 3 H D] (16-bit) of enh_causal_attention_forward from qkv, the out and lse it stored, and dout [B, N, H D].  D a multiple of 64 up to
+ * 384, any N >= 1.  Flash-style: P is recomputed from lse, delta = rowsum(dout o out) goes through ws (enh_causal_attention_backward_workspace_bytes:
+ * B H N floats).  Two kernels (dQ; dK and dV); tiles on the masked side of the diagonal are neither loaded nor computed; above D = 128 a workgroup
+ * owns at most 128 output columns (dK / dV: 64 from D = 256).  Query 0 of every sequence sees one key: its dQ row and its dS are exact zeros. */
+size_t enh_causal_attention_backward_workspace_bytes(int B, int N, int H);
+int enh_causal_attention_backward(const enh_h16* qkv, const enh_h16* out, const enh_h16* dout, const float* lse, int B, int N, int H, int D, float scale,
+                                  enh_h16* dqkv, void* ws, size_t ws_bytes, int dtype, void* stream);
+/* nll as enh_cross_entropy_rows (the same bits) and dlogits[m][v] = (softmax(logits[m])[v] - (v == target[m])) * gscale in the operand format,
+ * from one read of the f32 logits.  V a multiple of 8 up to 16384. */
+int enh_cross_entropy_backward(const float* logits, const int64_t* target, int64_t M, int V, float gscale, float* nll, enh_h16* dlogits, int dtype,
+                               void* stream);
+/* dx = dy * 2 relu(h) over n % 8 == 0 elements, with relu(h) = sqrt(y) taken from y = square(relu(h)) in the operand format (what enh_relu_sq_h16
+ * wrote and the p1 product consumed: the hidden activation is kept once). */
+int enh_relu_sq_backward(const float* dy, const enh_h16* y, enh_h16* dx, int64_t n, int dtype, void* stream);
+/* Backward of enh_ln_timeshift: dy [M, D] f32, x the forward's input (row statistics are recomputed from it), w, b (needed with colscale), colscale or
+ * NULL.  dx f32 = the gradient of x (+ dres when given), dx16 an optional copy in the operand format; dw, db and (with colscale) dcolscale [D] are
+ * set, or added to under `accumulate`.  With colscale = tm the gradient reaching ln(x[b, s]) is dy[b, s] tm + dy[b, s + 1] (1 - tm), the second term
+ * only for s + 1 < S.  The column sums go through row-block partials in ws (enh_ln_timeshift_backward_workspace_bytes) and a fixed-order pass. */
+size_t enh_ln_timeshift_backward_workspace_bytes(int64_t M, int D);
+int enh_ln_timeshift_backward(const float* dy, const float* x, const float* w, const float* b, const float* colscale, const float* dres, int64_t M, int S,
+                              int D, float eps, float* dx, enh_h16* dx16, float* dw, float* db, float* dcolscale, int accumulate, void* ws, size_t ws_bytes,
+                              int dtype, void* stream);
+/* Backward of enh_gpt_embed_seq from g [B, S, C] f32: dtok_code [V, C] and dtok_cond [Vc, C] (row v = the sum, in ascending (b, s) order, of the rows
+ * whose fed id is v; rows that do not occur are zero), dpos_code [P, C] (row p = sum_b g[b, p + 1] for p < S - 1, zero beyond) and dpos_cond [C].
+ * Only codes 0 .. S - 2 of a sequence are fed.  accumulate != 0 adds to the four tables instead of setting them.  C % 4 == 0, C <= 8192. */
+int enh_gpt_embed_seq_backward(const float* g, const int64_t* conds, const int64_t* codes, int64_t code_stride, int B, int S, int C, int Vc, int V, int P,
+                               float* dtok_cond, float* dpos_cond, float* dtok_code, float* dpos_code, int accumulate, void* stream);
 
 #ifdef __cplusplus
 }
