@@ -314,8 +314,9 @@ extern "C" int enh_mean_f32(const float* v, int64_t M, float* mean, void* stream
 // (thread t adds columns t, t + 256, ... ascending, the workgroup adds the threads in the fixed tree): nll has that kernel's bits.
 template <typename OT>
 __global__ __launch_bounds__(256) void gpt_ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int V, float gscale,
-                                                         float* __restrict__ nll, uint16_t* __restrict__ dlogits) {
+                                                         float* __restrict__ nll, uint16_t* __restrict__ dlogits, const float* __restrict__ gscale_dev) {
   __shared__ __attribute__((aligned(16))) float s_row[GR_CE_MAX_V];
+  if (gscale_dev) gscale *= *gscale_dev;      // the device loss scale (a power of two: exact)
   __shared__ float s_red[4];
   const int t = threadIdx.x;
   const float* row = logits + (int64_t)blockIdx.x * V;
@@ -342,13 +343,13 @@ __global__ __launch_bounds__(256) void gpt_ce_bwd_kernel(const float* __restrict
 }
 
 extern "C" int enh_cross_entropy_backward(const float* logits, const int64_t* target, int64_t M, int V, float gscale, float* nll, enh_h16* dlogits, int dtype,
-                                          void* stream) {
+                                          const float* gscale_dev, void* stream) {
   ENH_REQUIRE(logits && target && nll && dlogits, ENH_E_BADARG, "enh_cross_entropy_backward: null pointer");
   ENH_REQUIRE_DT(dtype, "enh_cross_entropy_backward");
   ENH_REQUIRE(M >= 1 && M <= 2147483647LL, ENH_E_SHAPE, "enh_cross_entropy_backward: M=%lld", (long long)M);
   ENH_REQUIRE(V >= 8 && V <= GR_CE_MAX_V && V % 8 == 0, ENH_E_SHAPE, "enh_cross_entropy_backward: V must be a multiple of 8 in [8, %d], got %d", GR_CE_MAX_V, V);
   enh_note_kernel("gpt_ce_bwd_kernel", dtype);
-  ENH_DT_DISPATCH(dtype, (gpt_ce_bwd_kernel<OT><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>(logits, target, V, gscale, nll, dlogits)));
+  ENH_DT_DISPATCH(dtype, (gpt_ce_bwd_kernel<OT><<<(unsigned)M, 256, 0, (hipStream_t)stream>>>(logits, target, V, gscale, nll, dlogits, gscale_dev)));
   return enh_check_launch("enh_cross_entropy_backward");
 }
 

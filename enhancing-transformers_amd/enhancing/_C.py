@@ -30,6 +30,7 @@ DETERMINISTIC = os.environ.get("ENH_DETERMINISTIC", "1") != "0"
 
 _c = ctypes
 _vp, _i64, _i32, _f32, _sz = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_float, _c.c_size_t
+_f64 = _c.c_double
 _u64, _u32 = _c.c_uint64, _c.c_uint32
 
 # name -> (restype, argtypes); must list every symbol include/enh_hip.h declares (checked by tests)
@@ -127,6 +128,7 @@ SIGNATURES = {
     "enh_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _f32, _i32, _vp]),
     "enh_grad_clip_coef_workspace_bytes": (_sz, [_i64]),
     "enh_grad_clip_coef": (_i32, [_vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "enh_adam_step_segments": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _f32, _f64, _f64, _f32, _f32, _vp, _vp, _vp, _f32, _i32, _vp]),
     "enh_loss_scale_update": (_i32, [_vp, _vp, _vp, _f32, _f32, _i32, _vp]),
     "enh_nonfinite_flag": (_i32, [_vp, _i64, _vp, _vp]),
     "enh_skinny_gemm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
@@ -145,7 +147,7 @@ SIGNATURES = {
     "enh_mean_f32": (_i32, [_vp, _i64, _vp, _vp]),
     "enh_causal_attention_backward_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "enh_causal_attention_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _i32, _vp]),
-    "enh_cross_entropy_backward": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _i32, _vp]),
+    "enh_cross_entropy_backward": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _i32, _vp, _vp]),
     "enh_relu_sq_backward": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
     "enh_ln_timeshift_backward_workspace_bytes": (_sz, [_i64, _i32]),
     "enh_ln_timeshift_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _i32, _vp]),
@@ -154,7 +156,7 @@ SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 25  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 26  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -634,6 +636,50 @@ def adamw_step(p, g, m, v, p_bf16, step: int, lr: float, beta1: float = 0.9, bet
                                                p.numel(), step, lr, beta1, beta2, eps, weight_decay, grad_scale, _p(skip_flag, F32, "skip_flag"),
                                                _p(loss_scale, F32, "loss_scale"), _p(clip_coef, F32, "clip_coef"), float(clip_value), _dt(p_bf16),
                                                _stream()), "enh_adamw_step"), unit="byte")
+
+
+def adam_segment_table(segments, n: int, arena_n: int, device):
+    """the device segment table of adam_step_segments from a host list of (begin, end, dst16, weight_decay): checked here, once, because the kernel
+    trusts it — sorted, disjoint, inside [0, n), every bound a multiple of 64, destinations (dst16 = -1: none) inside the arena, multiples of 8 and
+    disjoint.  Returns an int64 [nseg, 4] tensor (32 bytes per entry: begin, end, dst16, the f32 bits of weight_decay in the low word)."""
+    import struct
+    rows, last, dsts = [], 0, []
+    for b, e, d, wd in segments:
+        b, e, d = int(b), int(e), int(d)
+        if not (last <= b < e <= n) or b % 64 or e % 64:
+            raise RuntimeError(f"adam_segment_table: segment [{b}, {e}) must follow the one before it, lie inside [0, {n}) and have bounds that are multiples of 64")
+        if d != -1:
+            if d < 0 or d % 8 or d + (e - b) > arena_n:
+                raise RuntimeError(f"adam_segment_table: destination {d} of segment [{b}, {e}) must be a multiple of 8 inside the arena of {arena_n} elements")
+            dsts.append((d, d + e - b))
+        rows.append([b, e, d, struct.unpack("<q", struct.pack("<fi", float(wd), 0))[0]])
+        last = e
+    if not rows:
+        raise RuntimeError("adam_segment_table: no segment")
+    dsts.sort()
+    if any(a[1] > b[0] for a, b in zip(dsts, dsts[1:])):
+        raise RuntimeError("adam_segment_table: two segments share arena elements")
+    return torch.tensor(rows, dtype=I64).to(device)
+
+
+def adam_step_segments(p, g, m, v, arena, table, state, lr: float, beta1: float = 0.9, beta2: float = 0.96, eps: float = 1e-8, grad_scale: float = 1.0,
+                       skip_flag=None, loss_scale=None, clip_coef=None, clip_value: float = 0.0, dtype=None):
+    """one torch.optim.Adam step over flat f32 p, g, m, v driven by `table` (adam_segment_table: per segment an L2 weight decay and an optional
+    destination in the 16-bit operand `arena`, which receives the new p in the same pass); state: device f64 [4] = (t, beta1^t, beta2^t, 0), advanced on
+    the device unless skip_flag is set, in which case nothing at all is written.  dtype: the arena's format when there is no arena tensor."""
+    n = p.numel()
+    if g.numel() != n or m.numel() != n or v.numel() != n:
+        raise RuntimeError("adam_step_segments: p, g, m and v must be equally long")
+    if table.dim() != 2 or table.shape[1] != 4 or state.numel() != 4:
+        raise RuntimeError("adam_step_segments: table must be [nseg, 4] (adam_segment_table) and state f64 [4]")
+    dt = _dt(arena) if arena is not None else (DT_F16 if dtype == F16 else DT_BF16)
+    # 30 B per parameter: p, g, m, v read (16) + p, m, v written (12) + the 16-bit operand written (2; only the segments with a destination)
+    _timed(None, 30.0 * n,
+           lambda: _check(lib().enh_adam_step_segments(_p(p, F32, "p"), _p(g, F32, "g"), _p(m, F32, "m"), _p(v, F32, "v"), n, _p(arena, H16, "arena"),
+                                                       0 if arena is None else arena.numel(), _p(table, I64, "table"), table.shape[0],
+                                                       _p(state, F64, "state"), float(lr), float(beta1), float(beta2), float(eps), float(grad_scale),
+                                                       _p(skip_flag, F32, "skip_flag"), _p(loss_scale, F32, "loss_scale"), _p(clip_coef, F32, "clip_coef"),
+                                                       float(clip_value), dt, _stream()), "enh_adam_step_segments"), unit="byte")
 
 
 def loss_scale_update(scale, found_inf, tracker, growth: float = 2.0, backoff: float = 0.5, interval: int = 2000):
@@ -1165,13 +1211,15 @@ def causal_attention_backward(qkv, out, dout, lse, B: int, N: int, H: int, D: in
                           "enh_causal_attention_backward"))
 
 
-def cross_entropy_backward(logits, target, nll, dlogits, gscale: float):
-    """nll[m] as cross_entropy_rows (the same bits) and dlogits [M,V] 16-bit = (softmax(logits[m]) - onehot(target[m])) * gscale; V % 8 == 0"""
+def cross_entropy_backward(logits, target, nll, dlogits, gscale: float, gscale_dev=None):
+    """nll[m] as cross_entropy_rows (the same bits) and dlogits [M,V] 16-bit = (softmax(logits[m]) - onehot(target[m])) * gscale; V % 8 == 0.
+    gscale_dev (device f32 [1], optional) multiplies gscale: a loss scale that lives on the device"""
     M, V = logits.shape
     if target.numel() != M or nll.numel() != M or tuple(dlogits.shape) != (M, V):
         raise RuntimeError("cross_entropy_backward: one target and one result per row, dlogits as the logits")
     _timed(None, 6.0 * M * V, lambda: _check(lib().enh_cross_entropy_backward(_p(logits, F32, "logits"), _p(target, I64, "target"), M, V, float(gscale),
-                                                                               _p(nll, F32, "nll"), _p(dlogits, H16, "dlogits"), _dt(dlogits), _stream()),
+                                                                               _p(nll, F32, "nll"), _p(dlogits, H16, "dlogits"), _dt(dlogits),
+                                                                               _p(gscale_dev, F32, "gscale_dev"), _stream()),
                                              "enh_cross_entropy_backward"), unit="byte")
 
 

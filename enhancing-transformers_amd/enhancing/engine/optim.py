@@ -175,3 +175,210 @@ class FlatAdamW(_GradClip):
         s.step_count = int(sd["step"])
         s.m.copy_(sd["m"]); s.v.copy_(sd["v"])
         self.param_groups = sd["param_groups"]
+
+
+def gpt_param_groups(gpt):
+    """(decay, no_decay): the sorted parameter names of the reference's two Adam groups (modules/stage2/transformer.py:140-180, after minGPT): the
+    weights of the Linear layers get the L2 decay; biases, LayerNorm and Embedding weights, the position tables and time_mix get none.  Every
+    parameter is in exactly one group (the reference asserts it; so does this)."""
+    import torch.nn as nn
+    decay, no_decay = set(), set()
+    for mn, mod in gpt.named_modules():
+        for pn, _ in mod.named_parameters(recurse=False):
+            fpn = f"{mn}.{pn}" if mn else pn
+            if pn.endswith("bias"):
+                no_decay.add(fpn)
+            elif pn.endswith("weight") and isinstance(mod, nn.Linear):
+                decay.add(fpn)
+            elif pn.endswith("weight") and isinstance(mod, (nn.LayerNorm, nn.Embedding)):
+                no_decay.add(fpn)
+            elif "time_" in pn or pn in ("pos_emb_cond", "pos_emb_code", "pos_emb_depth"):
+                no_decay.add(fpn)
+    names = {n for n, _ in gpt.named_parameters()}
+    if decay & no_decay or names != decay | no_decay:
+        raise RuntimeError(f"gpt_param_groups: parameters in both groups {sorted(decay & no_decay)} or in neither {sorted(names - decay - no_decay)}")
+    return sorted(decay), sorted(no_decay)
+
+
+class GPTAdam(_GradClip):
+    """The reference's stage-2 optimizer (modules/stage2/transformer.py:176-181: torch.optim.Adam(betas=(0.9, 0.96)), L2 weight decay 0.01 on the
+    Linear weights, 0 on everything else) as ONE launch of enh_adam_step_segments (csrc/gpt_adam.hip) over the GPT's flat buffers.
+
+    Building it changes where the GPT's tensors live, not their values:
+      * the parameters are re-homed, one by one (never two copies of the model), into one flat f32 buffer `p` with `GPT.flat_grad`'s layout
+        (registration order, each padded to 64 elements); state_dict keys and load_state_dict keep working (load_state_dict copies in place);
+      * flat `m` and `v` are allocated, and the flat gradient (`GPT._flat_grads`);
+      * the 16-bit GEMM operands move into one arena ([3C, C] wqkv | wproj | w0 | w1 per layer, then the head) that the step kernel rewrites in the
+        same pass as the masters; `GPT._operand_copies` returns views into it and the per-layer copies it kept before are dropped.  The small f32
+        copies that are no view of a master (the q | k | v bias concatenation) are rebuilt with torch after every step.
+    Moving or replacing the parameters afterwards, or changing ENH_PRECISION, is refused with an error by the GPT and by step().
+
+    With the fp16 operand format step() is GradScaler's step on the device: found-inf (or the norm pass, which also finds it), the update with
+    skip / unscale, enh_loss_scale_update; initial scale ENH_LOSS_SCALE (65536), growth interval ENH_LOSS_SCALE_INTERVAL (2000): torch's defaults.
+    Under bf16 there is no scale and no skip.  The step count lives on the device (a dropped step does not advance it, and the host cannot know of
+    a drop); only state_dict() reads it.  state_dict() copies m and v to the host: 88 GB at the shipped size (10.98 G parameters)."""
+
+    def __init__(self, gpt, lr: float, betas=(0.9, 0.96), eps: float = 1e-8, weight_decay: float = 0.01, init_scale: float = None,
+                 growth_interval: int = None) -> None:
+        import os
+        import torch
+        from .. import _C
+        params = list(gpt.named_parameters())
+        if not params or not all(p.is_cuda for _, p in params):
+            raise RuntimeError("GPTAdam: the GPT's parameters must be on a ROCm device (model.to('cuda') first): the optimizer step is a HIP kernel and "
+                               "there is no CPU path")
+        if any(p.dtype != torch.float32 for _, p in params):
+            raise RuntimeError("GPTAdam: the GPT's parameters must be float32 (the masters; the 16-bit operands are the optimizer's arena)")
+        if any(p.numel() % 64 for _, p in params):      # a segment of the step kernel begins and ends on a multiple of 64 elements
+            raise RuntimeError("GPTAdam: every parameter's element count must be a multiple of 64 (embed_dim is one for every GPT this package builds)")
+        dev = params[0][1].device
+        self.gpt = gpt
+        self.dt = gpt._operand_dtype(True, "GPTAdam")
+        decay, no_decay = gpt_param_groups(gpt)
+        self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, names=decay),
+                             dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0.0, names=no_decay)]
+        self.grad_scale = 1.0
+        self._clip_out = None
+        # ---- flat masters: GPT._flat_grads' layout ----
+        offs, total = [], 0
+        for _, p in params:
+            offs.append(total)
+            total += (p.numel() + 63) // 64 * 64
+        self.p = torch.zeros(total, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            for (_, p), o in zip(params, offs):
+                dst = self.p[o:o + p.numel()].view(p.shape)
+                dst.copy_(p.data)
+                p.data = dst          # the old storage is released here, one parameter at a time
+        self.m = torch.zeros_like(self.p)
+        self.v = torch.zeros_like(self.p)
+        self.state = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64, device=dev)      # t, beta1^t, beta2^t
+        # ---- operand arena ----
+        C, V, L = gpt.embed_dim, gpt.vocab_img_size, len(gpt.blocks)
+        per_layer = 12 * C * C
+        self.arena = torch.zeros(L * per_layer + V * C, dtype=self.dt, device=dev)
+        where = {"head.weight": L * per_layer}
+        for i in range(L):
+            b = i * per_layer
+            for nm, o in (("attn.query", 0), ("attn.key", C * C), ("attn.value", 2 * C * C), ("attn.proj", 3 * C * C), ("mlp.p0", 4 * C * C),
+                          ("mlp.p1", 8 * C * C)):
+                where[f"blocks.{i}.{nm}.weight"] = b + o
+        wd_of = {n: weight_decay for n in decay}
+        segs = [(o, o + p.numel(), where.get(n, -1), wd_of.get(n, 0.0)) for (n, p), o in zip(params, offs)]
+        self._dst = [(p, where[n]) for n, p in params if n in where]
+        self.table = _C.adam_segment_table(segs, total, self.arena.numel(), dev)
+        gpt._operands.clear()          # the per-layer copies (22 GB at the shipped size)
+        ops = dict(layers=[], head=self.arena[L * per_layer:].view(V, C))
+        for i, blk in enumerate(gpt.blocks):
+            a, b = blk.attn, i * per_layer
+            view = lambda o, r, c: self.arena[b + o:b + o + r * c].view(r, c)
+            bqkv = torch.cat([a.query.bias, a.key.bias, a.value.bias]).detach().float().contiguous() if a.query.bias is not None else None
+            ops["layers"].append(dict(wqkv=view(0, 3 * C, C), bqkv=bqkv, wproj=view(3 * C * C, C, C), w0=view(4 * C * C, 4 * C, C),
+                                      w1=view(8 * C * C, C, 4 * C), time_mix=a.time_mix.detach().reshape(-1)))
+        self._ptrs = tuple(p.data_ptr() for _, p in params)
+        gpt._arena = dict(dt=self.dt, ptrs=self._ptrs, ops=ops, versions=None, refresh=self.refresh_operands)
+        self.refresh_operands()
+        gpt._flat_grads(dev)
+        # ---- GradScaler on the device (fp16 operands only) ----
+        self.scaler = None
+        if self.dt == torch.float16:
+            self.scaler = LossScaler(dev, init_scale=float(os.environ.get("ENH_LOSS_SCALE", 65536.0)) if init_scale is None else init_scale,
+                                     growth_interval=growth_interval)
+            self.scaler.enabled = True
+
+    @property
+    def loss_scale(self):
+        """device f32 [1]: what forward_backward(loss_scale=...) takes; None under bf16"""
+        return None if self.scaler is None else self.scaler.scale_t
+
+    @property
+    def grad_norm(self):
+        """2-norm of the gradient the last step applied, before clipping (device f32 [1]; None until a step ran with clipping by norm or tracking on)"""
+        return None if self._clip_out is None else self._clip_out[:1]
+
+    def refresh_operands(self) -> None:
+        """the arena and the q | k | v bias copies rebuilt from the masters with torch (one rounding from f32, as the copies the arena replaces).
+        Runs at construction and whenever torch wrote a master in place (load_state_dict, an init): GPT._operand_copies sees the masters' version
+        counters move and calls it.  The step kernel writes masters and arena together and moves no counter, so a step never comes here."""
+        import torch
+        gpt = self.gpt
+        with torch.no_grad():
+            for p, d in self._dst:
+                self.arena[d:d + p.numel()].copy_(p.detach().view(-1))
+            self._refresh_bias_copies()
+        gpt._arena["versions"] = tuple(p._version for p in gpt.parameters())
+
+    def _refresh_bias_copies(self) -> None:
+        import torch
+        for blk, W in zip(self.gpt.blocks, self.gpt._arena["ops"]["layers"]):
+            if W["bqkv"] is not None:
+                a = blk.attn
+                torch.cat([a.query.bias.detach(), a.key.bias.detach(), a.value.bias.detach()], out=W["bqkv"])
+
+    def zero_grad(self, set_to_none: bool = False) -> None:
+        if self.gpt.flat_grad is not None:
+            self.gpt.flat_grad.zero_()
+
+    def _check_home(self) -> None:
+        gpt = self.gpt
+        if gpt._arena is None or gpt._arena["ptrs"] is not self._ptrs or tuple(p.data_ptr() for p in gpt.parameters()) != self._ptrs:
+            raise RuntimeError("GPTAdam.step: the GPT's parameters were moved or replaced after this optimizer was built (or a newer GPTAdam owns them): "
+                               "its flat buffers no longer belong to them; build a new GPTAdam (configure_optimizers)")
+        if gpt._operand_dtype(True, "GPTAdam.step") != self.dt:
+            raise RuntimeError(f"GPTAdam.step: the operand arena holds {self.dt} but the engine's operand format (ENH_PRECISION) changed; build a new GPTAdam")
+
+    def step(self) -> None:
+        import torch
+        from .. import _C
+        self._check_home()
+        gpt, g, h = self.gpt, self.gpt.flat_grad, self.param_groups[0]
+        if g is None or g.numel() != self.p.numel():
+            raise RuntimeError("GPTAdam.step: no gradients (run GPT.forward_backward / CondTransformer.training_step first)")
+        scale = self.grad_scale
+        clip_norm, clip_value = self._clip_args()
+        kw = dict(lr=h["lr"], beta1=h["betas"][0], beta2=h["betas"][1], eps=h["eps"], grad_scale=scale)
+        if clip_norm is not None:
+            if self._clip_out is None:
+                self._clip_out = torch.zeros(2, dtype=torch.float32, device=g.device)
+            if clip_norm != float("inf"):
+                kw["clip_coef"] = self._clip_out[1:]
+        if clip_value is not None:
+            kw["clip_value"] = clip_value
+        sc = self.scaler
+        if sc is not None:        # the backward ran on scale_t x the loss: inf / nan check, unscale inside the update, GradScaler.update — no host sync
+            sc.found_inf.zero_()
+            if clip_norm is not None:
+                _C.grad_clip_coef(g, clip_norm, scale, self._clip_out, loss_scale=sc.scale_t, found_inf=sc.found_inf)
+            else:
+                _C.nonfinite_flag(g, sc.found_inf)
+            _C.adam_step_segments(self.p, g, self.m, self.v, self.arena, self.table, self.state, skip_flag=sc.found_inf, loss_scale=sc.scale_t, **kw)
+            _C.loss_scale_update(sc.scale_t, sc.found_inf, sc.tracker, 2.0, 0.5, sc.growth_interval)
+        else:
+            if clip_norm is not None:
+                _C.grad_clip_coef(g, clip_norm, scale, self._clip_out)
+            _C.adam_step_segments(self.p, g, self.m, self.v, self.arena, self.table, self.state, **kw)
+        # the kernel wrote the masters through raw pointers: the f32 copies that are no view of a master are rebuilt (3C elements per layer), and
+        # operand copies of any other format (the exact mode's f32 q | k | v) are dropped so that their next use rebuilds them
+        self._refresh_bias_copies()
+        gpt._operands.clear()
+
+    def state_dict(self) -> dict:
+        """step count, m, v and the scaler's state on the host (m and v: 88 GB at the shipped size).  The one place the device step count is read."""
+        st = self.state.detach().cpu()
+        sd = dict(step=int(st[0].item()), state=st, m=self.m.detach().cpu(), v=self.v.detach().cpu(),
+                  param_groups=[{k: v for k, v in g.items()} for g in self.param_groups])
+        if self.scaler is not None:
+            sd["scaler"] = dict(scale=self.scaler.scale_t.detach().cpu(), tracker=self.scaler.tracker.detach().cpu())
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        import torch
+        if "state" in sd:
+            self.state.copy_(sd["state"])
+        else:
+            t, (b1, b2) = int(sd["step"]), self.param_groups[0]["betas"]
+            self.state.copy_(torch.tensor([float(t), b1 ** t, b2 ** t, 0.0], dtype=torch.float64))
+        self.m.copy_(sd["m"]); self.v.copy_(sd["v"])
+        self.param_groups = [dict(g) for g in sd["param_groups"]]
+        if self.scaler is not None and "scaler" in sd:
+            self.scaler.scale_t.copy_(sd["scaler"]["scale"]); self.scaler.tracker.copy_(sd["scaler"]["tracker"])

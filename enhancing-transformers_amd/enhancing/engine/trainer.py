@@ -2,7 +2,10 @@
 installable in this environment).  It drives the Lightning protocol of ``ViTVQ`` the way Lightning 1.5 does for
 the stage-1 configs: per batch, ``training_step(batch, batch_idx, optimizer_idx)`` for each optimizer, gradient
 accumulation over ``accumulate_grad_batches`` batches, ``strategy="ddp"`` = one process per GPU with gradient
-all-reduce (RCCL), a ``{"state_dict": ...}`` checkpoint per epoch (general.py:49-55), scalar logs to a JSONL sink."""
+all-reduce (RCCL), a ``{"state_dict": ...}`` checkpoint per epoch (general.py:49-55), scalar logs to a JSONL sink.
+
+A stage-2 ``CondTransformer`` runs through the same loop on one GPU: it has no stage-1 engine, one optimizer (engine/optim.py GPTAdam) and its
+operand format is ENH_PRECISION, which ``precision`` must agree with (16 -> fp16 with the device loss scale, "bf16"; 32 is refused)."""
 from __future__ import annotations
 
 import json
@@ -87,15 +90,35 @@ class Trainer:
         out["val_images_per_rank"] = weight
         return out
 
+    def _stage2_setup(self, model, want: str):
+        """what fit() checks and prepares for a CondTransformer in place of a stage-1 engine (there is none: returns None): one GPU, a 16-bit operand
+        format that agrees with ENH_PRECISION, the GPT on this rank's device before configure_optimizers re-homes its parameters"""
+        if self.world > 1:
+            raise NotImplementedError("stage-2 training runs on one GPU: the gradient all-reduce of the GPT's flat buffer (DDP) is not built")
+        if want == "fp32":
+            raise NotImplementedError("Trainer(precision=32) on a CondTransformer: the exact-f32 backward of the GPT is not built; use precision=16 "
+                                      "(fp16 operands, loss scale on the device) or 'bf16'")
+        have = os.environ.get("ENH_PRECISION", "fp16")
+        if have != want:
+            raise RuntimeError(f"Trainer(precision={self.precision}) asks for {want} operands but ENH_PRECISION is {have!r}: the stage-2 GPT takes its "
+                               "operand format from ENH_PRECISION")
+        model.transformer.to(torch.device("cuda", self.local_rank))
+        return None
+
     def fit(self, model, data) -> None:
         self.rank, self.local_rank, self.world = init_process_group_from_env()
         torch.cuda.set_device(self.local_rank)
         want = {16: "fp16", "bf16": "bf16", 32: "fp32"}[self.precision]
-        if getattr(model, "_engine", None) is None and hasattr(model, "precision") and model.precision is None:
-            model.precision = want          # engine not bound yet: bind it in the requested mode
-        eng = model.engine
-        if getattr(eng, "precision", want) != want:
-            raise RuntimeError(f"Trainer(precision={self.precision}) asks for the {want} engine mode but the model is bound to {eng.precision}")
+        from ..modules.stage2.transformer import CondTransformer
+        stage2 = isinstance(model, CondTransformer)
+        if stage2:
+            eng = self._stage2_setup(model, want)
+        else:
+            if getattr(model, "_engine", None) is None and hasattr(model, "precision") and model.precision is None:
+                model.precision = want          # engine not bound yet: bind it in the requested mode
+            eng = model.engine
+            if getattr(eng, "precision", want) != want:
+                raise RuntimeError(f"Trainer(precision={self.precision}) asks for the {want} engine mode but the model is bound to {eng.precision}")
         if self.world > 1:
             eng.comm = GradSync(eng.store)
             eng.comm.broadcast_parameters(0)
@@ -128,7 +151,8 @@ class Trainer:
                 # Lightning also steps on the LAST batch of an epoch when the window is incomplete (a trailing partial window is not dropped)
                 last = (batch_idx + 1) % self.accum == 0 or (n_batches is not None and batch_idx + 1 == n_batches)
                 # Lightning 1.5 order: per optimizer, training_step -> backward -> step, so the discriminator step sees the updated autoencoder
-                eng.sync_grads = last   # accumulate locally, all-reduce the window's sum once (what DDP's no_sync gives Lightning)
+                if eng is not None:
+                    eng.sync_grads = last   # accumulate locally, all-reduce the window's sum once (what DDP's no_sync gives Lightning)
                 for o in opts[1:]:
                     if getattr(o, "comm", None) is not None:
                         o.comm.enabled = last
@@ -138,7 +162,8 @@ class Trainer:
                         if sched is not None:
                             # LambdaLR(lr_lambda=scheduler.schedule), vitvqgan.py:172 (a bare callable is taken as the lr_lambda itself)
                             mult = sched.schedule(self.global_step) if hasattr(sched, "schedule") else sched(self.global_step)
-                            o.param_groups[0]["lr"] = base_lr * mult
+                            for group in o.param_groups:
+                                group["lr"] = base_lr * mult
                         o.step()
                 seen += batch["image"].shape[0] * self.world
                 self._hook("on_train_batch_end", model, None, batch, batch_idx)
@@ -163,8 +188,9 @@ class Trainer:
             if self.rank == 0:
                 ck = os.path.join(self.root, "ckpt")
                 os.makedirs(ck, exist_ok=True)
+                states = [o.state_dict() for o in opts]      # once: a stage-2 optimizer's state is two host copies the size of the model
                 torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()}, "epoch": epoch,
-                            "global_step": self.global_step, "optimizer": opt.state_dict(), "optimizer_states": [o.state_dict() for o in opts]}, os.path.join(ck, f"epoch={epoch:02d}.ckpt"))
+                            "global_step": self.global_step, "optimizer": states[0], "optimizer_states": states}, os.path.join(ck, f"epoch={epoch:02d}.ckpt"))
             if self.max_steps is not None and self.global_step >= self.max_steps:
                 break
         for o in opts:      # the autograd hooks of attach_sync must not outlive this fit (a second fit would otherwise reduce every bucket twice: ADVICE r5)

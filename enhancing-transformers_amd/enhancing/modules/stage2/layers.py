@@ -1,5 +1,5 @@
-"""Stage-2 GPT prior (reference enhancing/modules/stage2/layers.py:23-303): sampling, the teacher-forced forward, and the loss with its gradients
-(no optimizer step yet).
+"""Stage-2 GPT prior (reference enhancing/modules/stage2/layers.py:23-303): sampling, the teacher-forced forward, and the loss with its gradients;
+the optimizer step over them is engine/optim.py GPTAdam.
 
 The modules below are parameter containers with the reference's names, shapes and init, so its checkpoints and yaml load.  `GPT.sample` is the
 reference's cached sampling loop restated per step on the device (csrc/gpt_decode.hip, gpt_rows.hip).  With cond_num_tokens == 1 every step is one token per
@@ -20,8 +20,11 @@ loss gradient fused with the cross-entropy, every product an enh_gemm_h16 call (
 that every `p.grad` is a view into), the f32 gradient of the residual stream carried through the LayerNorm / time-shift, relu^2 and embedding
 backward kernels of csrc/gpt_rows.hip and the causal flash-attention backward of csrc/gpt_attn_bwd.hip.  16-bit operand formats only.
 
-Left out: RQTransformer, the optimizer step and training_step, overflow detection and loss-scale updates, an exact-f32 backward, more than one
-condition token, HIP-graph capture, relu^2 / LayerNorm fused into GEMM epilogues."""
+`GPTAdam` (engine/optim.py) re-homes the parameters into one flat f32 buffer with `flat_grad`'s layout and owns a 16-bit operand arena that its step
+kernel (csrc/gpt_adam.hip) rewrites together with the masters; `_operand_copies` then returns views into that arena (`_arena`), so forward, sample and
+forward_backward see stepped weights without a rebuild.
+
+Left out: RQTransformer, an exact-f32 backward, more than one condition token, HIP-graph capture, relu^2 / LayerNorm fused into GEMM epilogues."""
 import os
 from typing import Optional, Tuple
 
@@ -108,6 +111,7 @@ class GPT(nn.Module):
         self._bwd_states = {}     # (chunk, dtype, device) -> the buffers of forward_backward()
         self._grad_key = None     # the parameters whose .grad are views into flat_grad
         self.flat_grad = None
+        self._arena = None        # set by engine/optim.py GPTAdam: dict(dt, ptrs, ops, versions, refresh) — the operand arena its step kernel keeps current
 
     def _init_weights(self, module: nn.Module) -> None:
         if isinstance(module, (nn.Linear, nn.Embedding)):
@@ -227,18 +231,20 @@ class GPT(nn.Module):
         return st
 
     @torch.no_grad()
-    def forward_backward(self, codes: torch.Tensor, conds: torch.Tensor, *, use_fp16: bool = True, loss_scale: float = 1.0) -> torch.Tensor:
+    def forward_backward(self, codes: torch.Tensor, conds: torch.Tensor, *, use_fp16: bool = True, loss_scale=1.0, accumulate: bool = False) -> torch.Tensor:
         """the teacher-forced loss and its gradients in one call: returns the unscaled mean cross-entropy over all B T positions (0-dim f32 on the
         device: what forward(..., return_loss=True)[2] returns, and with the same chunking the same bits) and leaves in `p.grad` of EVERY
         parameter loss_scale x the gradient of that mean (f32, views into the flat buffer `flat_grad`: what GradScaler.scale(loss).backward()
-        leaves).  The call SETS the gradients; rows of the token tables whose id does not occur are exactly zero.
+        leaves).  loss_scale is a float or a device f32 [1] tensor (a loss scale that lives on the device: engine/optim.py GPTAdam; the cross-entropy
+        backward reads it there, no host round trip).  The call SETS the gradients, or with accumulate=True ADDS to them (accumulate_grad_batches);
+        rows of the token tables whose id does not occur are exactly zero when set.
 
         use_fp16=True runs the 16-bit operand format of ENH_PRECISION: every product is an enh_gemm_h16 call (weight gradients accumulate in f32),
         the residual stream's gradient stays f32, the kernels between the products are csrc/gpt_rows.hip's and csrc/gpt_attn_bwd.hip's.  The
         exact-f32 backward is not built: use_fp16=False raises.  Device tensors only.  Batches run in chunks of whole sequences sized so that the
         activations saved for the backward stay under `backward_saved_cap` bytes (saved_bytes_per_token() per token row); weight gradients
         accumulate across the chunks in a fixed order, so two runs give the same bits.  Any B T works: a chunk's row buffers are rounded up to 8 rows
-        and the tail rows of every gradient operand are zero.  No optimizer step, no overflow check: later work."""
+        and the tail rows of every gradient operand are zero.  The optimizer step and the overflow check are GPTAdam.step()."""
         if not use_fp16:
             raise NotImplementedError("GPT.forward_backward(use_fp16=False): the exact-f32 backward is not built; use the 16-bit operand format")
         if not (torch.is_tensor(codes) and torch.is_tensor(conds) and codes.is_cuda and conds.is_cuda):
@@ -252,15 +258,20 @@ class GPT(nn.Module):
         self._flat_grads(dev)
         st = self._backward_state(chunk, dt, dev)
         nll = torch.empty(B, T, dtype=torch.float32, device=dev)
+        scale_dev = None
+        if torch.is_tensor(loss_scale):
+            if not (loss_scale.is_cuda and loss_scale.dtype == torch.float32 and loss_scale.numel() == 1):
+                raise ValueError("GPT.forward_backward: a tensor loss_scale must be a device f32 tensor of one element")
+            scale_dev, loss_scale = loss_scale.view(1), 1.0
         gscale = float(loss_scale) / float(B * T)
         for s in range(0, B, chunk):
             e = min(s + chunk, B)
-            self._backward_rows(st, codes[s:e], conds[s:e], nll[s:e], dt, gscale, accumulate=s > 0)
+            self._backward_rows(st, codes[s:e], conds[s:e], nll[s:e], dt, gscale, accumulate=accumulate or s > 0, gscale_dev=scale_dev)
         mean = torch.empty(1, dtype=torch.float32, device=dev)
         _C.mean_f32(nll.view(-1), mean)
         return mean[0]
 
-    def _backward_rows(self, st, codes, conds, nll, dt, gscale: float, accumulate: bool) -> None:
+    def _backward_rows(self, st, codes, conds, nll, dt, gscale: float, accumulate: bool, gscale_dev=None) -> None:
         """one chunk: the saving forward, then the backward of DESIGN.md §3.7, setting (accumulate=False) or adding to every parameter's gradient"""
         from ... import _C
         b, T, C, H, V = codes.shape[0], self.img_num_tokens, self.embed_dim, self.n_heads, self.vocab_img_size
@@ -285,7 +296,10 @@ class GPT(nn.Module):
             else:
                 _C.gemm(dy, w, M, K, N, trans_b=True, out_bf16=out)
 
-        _C.cross_entropy_backward(logits, codes.reshape(-1), nll.view(-1), dlogits, gscale)
+        if gscale_dev is None:
+            _C.cross_entropy_backward(logits, codes.reshape(-1), nll.view(-1), dlogits, gscale)
+        else:
+            _C.cross_entropy_backward(logits, codes.reshape(-1), nll.view(-1), dlogits, gscale, gscale_dev=gscale_dev)
         wgrad(st["dlogits"], st["a"], self.head.weight.grad, V, C)
         dgrad(dlogits, ops["head"], d32)
         ln = self.layer_norm
@@ -391,7 +405,20 @@ class GPT(nn.Module):
     # ---- operand copies -------------------------------------------------------------------------
     def _operand_copies(self, dt: torch.dtype):
         """the GEMM weights in the operand format `dt` (torch.float32: the exact mode's packed f32 q|k|v), built once from the fp32 masters and
-        rebuilt when a master was replaced or written in place (load_state_dict, an optimizer step): the masters' version counters are the key"""
+        rebuilt when a master was replaced or written in place (load_state_dict): the masters' version counters are the key.  Under a GPTAdam
+        (`_arena`) the 16-bit operands are views into the optimizer's arena, which its step kernel rewrites with the masters: nothing is rebuilt, and
+        a module whose parameters were moved or replaced since, or whose operand format changed, is refused."""
+        ar = getattr(self, "_arena", None)
+        if ar is not None and dt != torch.float32:
+            if dt != ar["dt"]:
+                raise RuntimeError(f"GPT: the optimizer's operand arena holds {ar['dt']} but the engine's operand format (ENH_PRECISION) is now {dt}: "
+                                   "build a new GPTAdam (configure_optimizers) under the format you train in")
+            if tuple(p.data_ptr() for p in self.parameters()) != ar["ptrs"]:
+                raise RuntimeError("GPT: the parameters were moved or replaced after GPTAdam was built (.to(), .half(), assigning .data): the optimizer's "
+                                   "flat buffers and operand arena no longer belong to them; build a new GPTAdam (configure_optimizers)")
+            if tuple(p._version for p in self.parameters()) != ar["versions"]:      # torch wrote a master in place (load_state_dict): recast the arena
+                ar["refresh"]()
+            return ar["ops"]
         masters = [p for _, p in sorted(self.named_parameters())]
         key = tuple((p.data_ptr(), p._version) for p in masters)
         hit = self._operands.get(dt)

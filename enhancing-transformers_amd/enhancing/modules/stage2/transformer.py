@@ -1,7 +1,8 @@
 """CondTransformer (reference enhancing/modules/stage2/transformer.py:23-95): a condition model, a frozen stage-1 tokenizer and the GPT prior; `sample`
 draws codes on the device and decodes them with the tokenizer; `forward` / `validation_step` give the teacher-forced logits and the reference's
-val/total_loss; `loss_and_grads` returns the training loss and leaves the gradient of every GPT parameter on the device (GPT.forward_backward).
-The optimizer step (`training_step`, `configure_optimizers`) is not built."""
+val/total_loss; `loss_and_grads` returns the training loss and leaves the gradient of every GPT parameter on the device (GPT.forward_backward);
+`configure_optimizers` returns the reference's Adam as one device launch (engine/optim.py GPTAdam) and `training_step` runs the loss-scaled
+forward + backward against it (Trainer.fit drives both, on one GPU)."""
 from typing import List, Optional, Tuple
 
 import torch
@@ -93,8 +94,7 @@ class CondTransformer(nn.Module):
 
     def loss_and_grads(self, batch, batch_idx: int = 0, *, loss_scale: float = 1.0) -> torch.Tensor:
         """shared_step's prologue, then GPT.forward_backward: returns the unscaled training loss (also logged as train/total_loss) and leaves
-        loss_scale x its gradient in `.grad` of every parameter of the transformer.  What a training step runs before its optimizer step, which
-        is not built."""
+        loss_scale x its gradient in `.grad` of every parameter of the transformer.  training_step is this with the optimizer's device loss scale."""
         codes, conds = self._tokenize(batch)
         loss = self.transformer.forward_backward(codes, conds, loss_scale=loss_scale)
         self.log("train/total_loss", loss, on_step=True, on_epoch=True, prog_bar=True, logger=True)
@@ -106,10 +106,34 @@ class CondTransformer(nn.Module):
         self.log("val/total_loss", loss, on_step=True, on_epoch=True, prog_bar=True, logger=True)
         return loss
 
-    def training_step(self, batch, batch_idx: int, optimizer_idx: int = 0):
-        raise NotImplementedError("stage-2 training is not built (no optimizer step for the GPT yet): CondTransformer samples, validates and, "
-                                  "with loss_and_grads, computes the loss and its gradients")
+    def training_step(self, batch, batch_idx: int, optimizer_idx: int = 0, *, zero_grad: bool = True) -> torch.Tensor:
+        """reference transformer.py:120-124 with Lightning's backward folded in: tokenize the batch, run GPT.forward_backward with the optimizer's
+        device loss scale (fp16 operands; none under bf16), log train/total_loss and return the unscaled loss.  zero_grad=False adds to the
+        gradients of the batches before it (accumulate_grad_batches).  The optimizer of configure_optimizers() then steps: Trainer.fit, or
+        `opt.step()` by hand."""
+        opt = self.__dict__.get("_optimizer")
+        if opt is None:
+            raise NotImplementedError("stage-2 training needs its optimizer first: set `learning_rate` and call configure_optimizers() before "
+                                      "training_step (it builds the flat buffers and the loss scale the step runs against)")
+        codes, conds = self._tokenize(batch)
+        scale = opt.loss_scale
+        loss = self.transformer.forward_backward(codes, conds, loss_scale=1.0 if scale is None else scale, accumulate=not zero_grad)
+        self.log("train/total_loss", loss, on_step=True, on_epoch=True, prog_bar=True, logger=True)
+        return loss
 
     def configure_optimizers(self):
-        raise NotImplementedError("stage-2 training is not built (no optimizer step for the GPT yet): CondTransformer samples, validates and, "
-                                  "with loss_and_grads, computes the loss and its gradients")
+        """reference transformer.py:132-194: Adam(lr, betas=(0.9, 0.96)) with the L2 decay 0.01 on the Linear weights only -> ([GPTAdam], schedulers)
+        (engine/optim.py; one launch over the GPT's flat buffers).  The transformer must be on the device.  Calling it again builds a new optimizer
+        (fresh moments) over the same parameters."""
+        lr = self.__dict__.get("learning_rate")
+        if lr is None:
+            raise NotImplementedError("stage-2 training needs a learning rate: set `model.learning_rate` (main.py does) before configure_optimizers()")
+        from ...engine.optim import GPTAdam
+        opt = GPTAdam(self.transformer, lr=lr, betas=(0.9, 0.96), weight_decay=0.01)
+        self.__dict__["_optimizer"] = opt
+        schedulers = []
+        if self.scheduler is not None:
+            self.scheduler.params.start = lr
+            sched = initialize_from_config(self.scheduler)
+            schedulers = [{"scheduler": sched, "interval": "step", "frequency": 1}]
+        return [opt], schedulers

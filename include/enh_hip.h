@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 25  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 26  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -408,6 +408,22 @@ int enh_nonfinite_flag(const float* x, int64_t n, float* flag, void* stream);
 size_t enh_grad_clip_coef_workspace_bytes(int64_t n);
 int enh_grad_clip_coef(const float* g, int64_t n, float max_norm, float grad_scale, const float* loss_scale_dev, float* found_inf, float* out,
                        void* ws, size_t ws_bytes, void* stream);
+/* One torch.optim.Adam step (no amsgrad, no maximize) of the stage-2 GPT (reference modules/stage2/transformer.py:132-194: betas (0.9, 0.96), L2 weight
+ * decay 0.01 on the Linear weights only) over flat f32 p, g, m, v [n] (16-byte aligned, n % 64 == 0, int64 indices), in ONE launch driven by a device
+ * segment table (csrc/gpt_adam.hip).  segments: nseg entries of 32 bytes {int64 begin, int64 end, int64 dst16, float weight_decay, int32 0}, sorted by
+ * begin, disjoint, every bound a multiple of 64; elements outside every segment are never written.  Per element, in f32:
+ *   gg = g * grad_scale / *loss_scale_dev * *clip_coef_dev;  clamp to +-clip_value if > 0;  gg += weight_decay * p;
+ *   m = m + (gg - m) * (1 - beta1);  v = v * beta2 + gg * gg * (1 - beta2);  p -= (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps))
+ * (grad_scale, loss_scale_dev, clip_coef_dev, clip_value and skip_flag as in enh_adamw_step; 1 - beta is formed in double and rounded to float once).
+ * dst16 >= 0: the new p of the segment is also written, round-to-nearest-even in the call's `dtype`, to arena[dst16 + (e - begin)] (dst16 % 8 == 0;
+ * arena: arena_n 16-bit elements, may be NULL with arena_n = 0); other arena bytes are never written.
+ * state: device double[4] = {t, beta1^t, beta2^t, unused}, {0, 1, 1, 0} before the first step.  A one-workgroup launch advances it when skip_flag is
+ * NULL or zero; the step then uses bc1 = 1 - state[1], bc2 = 1 - state[2].  With a non-zero skip_flag NOTHING is written: p, m, v, arena and state keep
+ * their bits (torch.cuda.amp.GradScaler does not advance the optimizer's step when it drops one).  No host round trip, no atomics; the same bits on
+ * every run.  A gradient multiplied by a power of two S with *loss_scale_dev = S gives the bits of the plain gradient with loss_scale_dev NULL. */
+int enh_adam_step_segments(float* p, const float* g, float* m, float* v, int64_t n, enh_h16* arena, int64_t arena_n, const void* segments, int nseg,
+                           double* state, float lr, double beta1, double beta2, float eps, float grad_scale, const float* skip_flag,
+                           const float* loss_scale_dev, const float* clip_coef_dev, float clip_value, int dtype, void* stream);
 
 /* Device-side tail of the input pipeline (enhancing/dataloader/imagenet.py:26-54: ... RandomCrop / CenterCrop -> RandomHorizontalFlip -> ToTensor):
  * src uint8 [B,Hs,Ws,3] (decoded + resized images, each in the top-left corner of its slot), meta int32 [B,3] = (y0, x0, flip) -> out f32 [B,3,R,R] in [0,1].
@@ -647,9 +663,10 @@ size_t enh_causal_attention_backward_workspace_bytes(int B, int N, int H);
 int enh_causal_attention_backward(const enh_h16* qkv, const enh_h16* out, const enh_h16* dout, const float* lse, int B, int N, int H, int D, float scale,
                                   enh_h16* dqkv, void* ws, size_t ws_bytes, int dtype, void* stream);
 /* nll as enh_cross_entropy_rows (the same bits) and dlogits[m][v] = (softmax(logits[m])[v] - (v == target[m])) * gscale in the operand format,
- * from one read of the f32 logits.  V a multiple of 8 up to 16384. */
+ * from one read of the f32 logits.  V a multiple of 8 up to 16384.  gscale_dev (optional device float) multiplies gscale: the loss scale of an fp16
+ * backward, kept on the device (enh_loss_scale_update); with NULL the kernel is the one without it, bit for bit. */
 int enh_cross_entropy_backward(const float* logits, const int64_t* target, int64_t M, int V, float gscale, float* nll, enh_h16* dlogits, int dtype,
-                               void* stream);
+                               const float* gscale_dev, void* stream);
 /* dx = dy * 2 relu(h) over n % 8 == 0 elements, with relu(h) = sqrt(y) taken from y = square(relu(h)) in the operand format (what enh_relu_sq_h16
  * wrote and the p1 product consumed: the hidden activation is kept once). */
 int enh_relu_sq_backward(const float* dy, const enh_h16* y, enh_h16* dx, int64_t n, int dtype, void* stream);
