@@ -145,6 +145,9 @@ SIGNATURES = {
     "enh_relu_sq_h16": (_i32, [_vp, _vp, _i64, _i32, _vp]),
     "enh_cross_entropy_rows": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "enh_mean_f32": (_i32, [_vp, _i64, _vp, _vp]),
+    "enh_rq_embed_seq": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "enh_ln_rows_strided": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _i64, _vp]),
+    "enh_short_causal_attention_forward": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp]),
     "enh_causal_attention_backward_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "enh_causal_attention_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _i32, _vp]),
     "enh_cross_entropy_backward": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _i32, _vp, _vp]),
@@ -156,7 +159,7 @@ SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 26  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 27  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -1190,6 +1193,47 @@ def cross_entropy_rows(logits, target, nll, mean=None):
 
 def mean_f32(v, mean):
     _check(lib().enh_mean_f32(_p(v, F32, "v"), v.numel(), _p(mean, F32, "mean"), _stream()), "enh_mean_f32")
+
+
+# ------------------------------------------------------------------------------------------------
+# stage-2 RQTransformer forward (csrc/rq_prefill.hip): the embedding stage, the strided LayerNorm and the short-sequence attention
+# ------------------------------------------------------------------------------------------------
+def rq_embed_seq(conds, codes, tok_cond, pos_cond, tok_code, pos_code, pos_depth, spatial, depth):
+    """spatial [B,T,C] f32 (the condition row, then the depth sums of positions 0 .. T - 2) and slots 1 .. D - 1 of depth [B*T,D,C] f32 (the running
+    sums) from conds [B] and codes [B,T,D] (int64, contiguous); pos_code [>= T - 1, C], pos_depth [D - 1, C]; slot 0 of depth is left alone"""
+    B, T, C = spatial.shape
+    if conds.dtype != I64 or conds.numel() != B or codes.dtype != I64 or codes.dim() != 3 or tuple(codes.shape[:2]) != (B, T):
+        raise RuntimeError("rq_embed_seq: conds [B] and codes [B,T,D] must be int64 device tensors")
+    D = codes.shape[2]
+    if tuple(depth.shape) != (B * T, D, C) or pos_code.shape[0] < T - 1 or pos_code.shape[-1] != C or tuple(pos_depth.shape) != (D - 1, C) \
+            or tok_cond.shape[1] != C or tok_code.shape[1] != C or pos_cond.numel() != C:
+        raise RuntimeError(f"rq_embed_seq: depth {tuple(depth.shape)}, pos_code {tuple(pos_code.shape)}, pos_depth {tuple(pos_depth.shape)} do not fit "
+                           f"B={B} T={T} D={D} C={C}")
+    _check(lib().enh_rq_embed_seq(_p(conds, I64, "conds"), _p(codes, I64, "codes"), _p(tok_cond, F32, "tok_cond"), _p(pos_cond, F32, "pos_cond"),
+                                  _p(tok_code, F32, "tok_code"), _p(pos_code, F32, "pos_code"), _p(pos_depth, F32, "pos_depth"), B, T, D, C,
+                                  tok_cond.shape[0], tok_code.shape[0], _p(spatial, F32, "spatial"), _p(depth, F32, "depth"), _stream()), "enh_rq_embed_seq")
+
+
+def ln_rows_strided(x, w, b, out, out_stride: int, eps: float = 1e-5):
+    """row m of LayerNorm(x [M,D] f32) written at out.view(-1)[m * out_stride:][:D]: `out` is any contiguous f32 tensor that holds those rows"""
+    M, D = x.shape
+    if w.numel() != D or b.numel() != D or out.numel() < (M - 1) * int(out_stride) + D:
+        raise RuntimeError(f"ln_rows_strided: x {tuple(x.shape)} with row stride {out_stride} does not fit out {tuple(out.shape)}")
+    _check(lib().enh_ln_rows_strided(_p(x, F32, "x"), _p(w, F32, "w"), _p(b, F32, "b"), M, D, eps, _p(out, F32, "out"), int(out_stride), _stream()),
+           "enh_ln_rows_strided")
+
+
+def short_causal_attention(qkv, NSEQ: int, L: int, H: int, D: int, out, lse=None, scale: Optional[float] = None):
+    """out [NSEQ,L,H*D] = causal softmax attention of NSEQ sequences of L <= 8 tokens, qkv packed [NSEQ,L,3*H*D]; 16-bit tensors of one format;
+    lse [NSEQ,H,L] f32 optional; scale defaults to D ** -0.5"""
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    if qkv.numel() != NSEQ * L * 3 * H * D or out.numel() != NSEQ * L * H * D or (lse is not None and lse.numel() != NSEQ * H * L):
+        raise RuntimeError(f"short_causal_attention: qkv {tuple(qkv.shape)} out {tuple(out.shape)} do not fit NSEQ={NSEQ} L={L} H={H} D={D}")
+    L_ = lib()
+    # algorithmic HBM bytes: q, k and v read once, out written once
+    _timed(None, 8.0 * NSEQ * L * H * D,
+           lambda: _check(L_.enh_short_causal_attention_forward(_p(qkv, H16, "qkv"), NSEQ, L, H, D, scale, _p(out, H16, "out"), _p(lse, F32, "lse"),
+                                                                _dt(qkv, out), _stream()), "enh_short_causal_attention_forward"), unit="byte")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -24,7 +24,14 @@ backward kernels of csrc/gpt_rows.hip and the causal flash-attention backward of
 kernel (csrc/gpt_adam.hip) rewrites together with the masters; `_operand_copies` then returns views into that arena (`_arena`), so forward, sample and
 forward_backward see stepped weights without a rebuild.
 
-Left out: RQTransformer, an exact-f32 backward, more than one condition token, HIP-graph capture, relu^2 / LayerNorm fused into GEMM epilogues."""
+`RQTransformer` (reference layers.py:306-547) is the prior over a residual quantizer's [B, T, D] codes: `RQTransformer.forward` is the teacher-forced
+forward and the validation loss.  Its spatial transformer is `GPT.forward`'s per-layer launch sequence (`_block_rows`, shared); the
+embedding stage, ln_spatial written into slot 0 of the depth sequences and the depth transformer's attention over B T sequences of D <= 8 slots are
+csrc/rq_prefill.hip.  The reference's forward sums the code embeddings along the CHANNELS (`codes.cumsum(-1)`) where its sampler sums along DEPTH:
+keyword `code_sum` chooses, "depth" by default (see the class docstring).
+
+Left out: RQTransformer's sampling, backward and optimizer step, an exact-f32 backward, more than one condition token, HIP-graph capture, relu^2 /
+LayerNorm fused into GEMM epilogues."""
 import os
 from typing import Optional, Tuple
 
@@ -69,6 +76,56 @@ class Block(nn.Module):
         self.ln2 = nn.LayerNorm(embed_dim)
         self.attn = MultiHeadSelfAttention(ctx_len=ctx_len, cond_len=cond_len, embed_dim=embed_dim, n_heads=n_heads, attn_bias=attn_bias)
         self.mlp = FFN(embed_dim=embed_dim, mlp_bias=mlp_bias)
+
+
+# ---- what the teacher-forced forwards of GPT and RQTransformer share: the products, one block's launches, the operand copies ----------------
+def _row_linear(M: int, dt: torch.dtype):
+    """linear(inp, w, out, bias, res, relu_sq) over the leading M rows: out = inp w^T (+ bias) (+ res) in the operand format `dt`"""
+    from ... import _C
+    if dt == torch.float32:
+        def linear(inp, w, out, bias=None, res=None, relu_sq=False):      # tree-ordered sums: enh_gemm_f32 adds K terms in ascending order (DESIGN §3.5)
+            for m0 in range(0, M, MAX_BATCH):
+                m1 = min(m0 + MAX_BATCH, M)
+                _C.skinny_gemm_f32(inp[m0:m1], w, out[m0:m1], bias=bias, relu_sq=relu_sq, res=None if res is None else res[m0:m1])
+    else:
+        def linear(inp, w, out, bias=None, res=None, relu_sq=False):
+            N, K = w.shape
+            if out.dtype == torch.float32:
+                _C.gemm(inp, w, M, N, K, bias=bias, res=res, res_rows=M if res is not None else 0, out_f32=out)
+            else:
+                _C.gemm(inp, w, M, N, K, bias=bias, out_bf16=out)
+    return linear
+
+
+def _block_rows(blk, W, linear, dt, S: int, attention, x, x_out, a, a2, qkv, att, x2, hid32, hid) -> None:
+    """the launches of one Block over whole sequences of S rows: x -> x_out (both f32).  attention(qkv, att) is the block's causal attention."""
+    from ... import _C
+    _C.ln_timeshift(x, blk.ln1.weight, blk.ln1.bias, a, S, colscale=W["time_mix"], eps=blk.ln1.eps)
+    linear(a, W["wqkv"], qkv, bias=W["bqkv"])
+    attention(qkv, att)
+    linear(att, W["wproj"], x2, bias=blk.attn.proj.bias, res=x)
+    _C.ln_timeshift(x2, blk.ln2.weight, blk.ln2.bias, a2, S, eps=blk.ln2.eps)
+    if dt == torch.float32:
+        linear(a2, W["w0"], hid32, bias=blk.mlp.p0.bias, relu_sq=True)
+        linear(hid32, W["w1"], x_out, bias=blk.mlp.p1.bias, res=x2)
+    else:
+        # relu^2 on the f32 product, one rounding to the operand format (in place on a 16-bit product it would be two)
+        linear(a2, W["w0"], hid32, bias=blk.mlp.p0.bias)
+        _C.relu_sq(hid, hid32)
+        linear(hid, W["w1"], x_out, bias=blk.mlp.p1.bias, res=x2)
+
+
+def _layer_operands(blocks, cast) -> list:
+    """per Block: the fused q|k|v weight and bias, proj, p0 and p1 through `cast`, and time_mix as a flat f32 vector"""
+    layers = []
+    for blk in blocks:
+        a, m = blk.attn, blk.mlp
+        bias = None
+        if a.query.bias is not None:
+            bias = torch.cat([a.query.bias, a.key.bias, a.value.bias]).detach().float().contiguous()
+        layers.append(dict(wqkv=cast(torch.cat([a.query.weight, a.key.weight, a.value.weight], 0)), bqkv=bias, wproj=cast(a.proj.weight),
+                           w0=cast(m.p0.weight), w1=cast(m.p1.weight), time_mix=a.time_mix.detach().reshape(-1).contiguous()))
+    return layers
 
 
 class GPT(nn.Module):
@@ -362,18 +419,7 @@ class GPT(nn.Module):
         M, hs = b * T, C // H
         ops = self._operand_copies(dt)
         x, x2, a, qkv, att, hid32, hid = (None if st.get(k) is None else st[k][:M] for k in ("x", "x2", "a", "qkv", "att", "hid32", "hid"))
-        if dt == torch.float32:
-            def linear(inp, w, out, bias=None, res=None, relu_sq=False):      # tree-ordered sums: enh_gemm_f32 adds K terms in ascending order
-                for m0 in range(0, M, MAX_BATCH):
-                    m1 = min(m0 + MAX_BATCH, M)
-                    _C.skinny_gemm_f32(inp[m0:m1], w, out[m0:m1], bias=bias, relu_sq=relu_sq, res=None if res is None else res[m0:m1])
-        else:
-            def linear(inp, w, out, bias=None, res=None, relu_sq=False):
-                N, K = w.shape
-                if out.dtype == torch.float32:
-                    _C.gemm(inp, w, M, N, K, bias=bias, res=res, res_rows=M if res is not None else 0, out_f32=out)
-                else:
-                    _C.gemm(inp, w, M, N, K, bias=bias, out_bf16=out)
+        linear = _row_linear(M, dt)
         x_out, a2, lse = x, a, None
         if saved is not None:
             x = saved[0]["x"][:M]
@@ -384,19 +430,8 @@ class GPT(nn.Module):
                 a, qkv, att, x2, a2, hid = (saved[i][k][:M] for k in ("a", "qkv", "att", "x2", "a2", "hid"))
                 lse = saved[i]["lse"][:b * H * T]
                 x_out = saved[i + 1]["x"][:M] if i + 1 < len(saved) else st["x"][:M]
-            _C.ln_timeshift(x, blk.ln1.weight, blk.ln1.bias, a, T, colscale=W["time_mix"], eps=blk.ln1.eps)
-            linear(a, W["wqkv"], qkv, bias=W["bqkv"])
-            _C.causal_attention(qkv, b, T, H, hs, att, lse=lse)
-            linear(att, W["wproj"], x2, bias=blk.attn.proj.bias, res=x)
-            _C.ln_timeshift(x2, blk.ln2.weight, blk.ln2.bias, a2, T, eps=blk.ln2.eps)
-            if dt == torch.float32:
-                linear(a2, W["w0"], hid32, bias=blk.mlp.p0.bias, relu_sq=True)
-                linear(hid32, W["w1"], x_out, bias=blk.mlp.p1.bias, res=x2)
-            else:
-                # relu^2 on the f32 product, one rounding to the operand format (in place on a 16-bit product it would be two)
-                linear(a2, W["w0"], hid32, bias=blk.mlp.p0.bias)
-                _C.relu_sq(hid, hid32)
-                linear(hid, W["w1"], x_out, bias=blk.mlp.p1.bias, res=x2)
+            _block_rows(blk, W, linear, dt, T, lambda qkv_, att_, lse_=lse: _C.causal_attention(qkv_, b, T, H, hs, att_, lse=lse_),
+                        x, x_out, a, a2, qkv, att, x2, hid32, hid)
             x = x_out
         a = st["a"][:M]
         _C.ln_timeshift(x, self.layer_norm.weight, self.layer_norm.bias, a, T, eps=self.layer_norm.eps)
@@ -425,15 +460,7 @@ class GPT(nn.Module):
         if hit is not None and hit[0] == key:
             return hit[1]
         cast = (lambda w: w.detach().to(dt).contiguous())
-        layers = []
-        for blk in self.blocks:
-            a, m = blk.attn, blk.mlp
-            bias = None
-            if a.query.bias is not None:
-                bias = torch.cat([a.query.bias, a.key.bias, a.value.bias]).detach().float().contiguous()
-            layers.append(dict(wqkv=cast(torch.cat([a.query.weight, a.key.weight, a.value.weight], 0)), bqkv=bias, wproj=cast(a.proj.weight),
-                               w0=cast(m.p0.weight), w1=cast(m.p1.weight), time_mix=a.time_mix.detach().reshape(-1).contiguous()))
-        ops = dict(layers=layers, head=cast(self.head.weight))
+        ops = dict(layers=_layer_operands(self.blocks, cast), head=cast(self.head.weight))
         self._operands[dt] = (key, ops)
         return ops
 
@@ -511,3 +538,189 @@ class GPT(nn.Module):
             linear(hid, W["w1"], x, bias=blk.mlp.p1.bias, res=x2)
         _C.row_ln_scale(x, self.layer_norm.weight, self.layer_norm.bias, a, eps=self.layer_norm.eps)
         linear(a, st["ops"]["head"], st["logits"])
+
+
+MAX_DEPTH = 8           # enh_rq_embed_seq, enh_short_causal_attention_forward: the stage-1 residual quantizer's cap on num_quantizers
+CODE_SUMS = ("depth", "channels")
+
+
+class RQTransformer(nn.Module):
+    """reference layers.py:306-395: a spatial transformer over the T positions of an image, whose input at a position is built from the D residual
+    codes of the position before it, and a depth transformer over the D slots of every position: slot 0 is ln_spatial of the spatial output, slot
+    d >= 1 is built from codes 0 .. d - 1 of the position; logits [B T, D, V].  The reference's constructor arguments, parameter names, shapes and
+    init.  Built here: the teacher-forced forward and the validation loss.  Not built: sampling, the backward, the optimizer step.
+
+    The code-sum quirk.  The reference's forward computes `codes.cumsum(-1)` on the [B, T, D, C] embeddings: a running sum along the embedding
+    CHANNELS, not along depth.  Its own sampler (sample_spatial_step / sample_depth_step: `codes.sum(1)`) and the RQ-VAE formulation sum over
+    DEPTH, so a model trained through the reference's forward is not the model its sampler draws from.  Keyword `code_sum` selects:
+      "depth" (default)   spatial row t + 1 = sum_j emb(code[b, t, j]) + pos_emb_code[t]; slot d >= 1 = sum_{j < d} emb(code[b, t, j]) +
+                          pos_emb_depth[d - 1]: what the sampler assumes; one launch (enh_rq_embed_seq)
+      "channels"          the reference's line in meaning: spatial row t + 1 = cumsum_C(emb(code[b, t, D - 1])) + pos_emb_code[t]; slot d =
+                          cumsum_C(emb(code[b, t, d - 1])) + pos_emb_depth[d - 1].  A parity instrument (the reference's own forward is then the
+                          golden of everything behind the embedding): the two input tensors are built with torch ops on the device, every launch
+                          after them is the default mode's."""
+
+    def __init__(self, vocab_cond_size: int, vocab_img_size: int, embed_dim: int, cond_num_tokens: int, img_num_tokens: int, depth_num_tokens: int,
+                 spatial_n_heads: int, depth_n_heads: int, spatial_n_layers: int, depth_n_layers: int, mlp_bias: bool = True, attn_bias: bool = True,
+                 *, code_sum: str = "depth") -> None:
+        super().__init__()
+        if cond_num_tokens != 1:
+            raise ValueError(f"RQTransformer: cond_num_tokens must be 1 (class conditioning), got {cond_num_tokens}")
+        if depth_num_tokens == 1:
+            raise ValueError("RQTransformer: depth_num_tokens == 1 is one code per position: use GPT")
+        if not 2 <= depth_num_tokens <= MAX_DEPTH:
+            raise ValueError(f"RQTransformer: depth_num_tokens must be in [2, {MAX_DEPTH}] (the residual quantizer's num_quantizers), got {depth_num_tokens}")
+        for who, n in (("spatial_n_heads", spatial_n_heads), ("depth_n_heads", depth_n_heads)):
+            if embed_dim % n:
+                raise ValueError(f"RQTransformer: embed_dim {embed_dim} is not a multiple of {who} {n}")
+            if (embed_dim // n) % 64 or embed_dim // n > MAX_HEAD:
+                raise ValueError(f"RQTransformer: the head size embed_dim / {who} must be a multiple of 64 up to {MAX_HEAD}, got {embed_dim // n}")
+        if vocab_img_size > MAX_VOCAB:
+            raise ValueError(f"RQTransformer: vocab_img_size must be at most {MAX_VOCAB}, got {vocab_img_size}")
+        if embed_dim > MAX_EMBED:
+            raise ValueError(f"RQTransformer: embed_dim must be at most {MAX_EMBED}, got {embed_dim}")
+        if vocab_img_size % 8:
+            raise ValueError(f"RQTransformer: vocab_img_size must be a multiple of 8 (the head's GEMM), got {vocab_img_size}")
+        if img_num_tokens > MAX_TOKENS:
+            raise ValueError(f"RQTransformer: img_num_tokens must be at most {MAX_TOKENS}, got {img_num_tokens}")
+        if code_sum not in CODE_SUMS:
+            raise ValueError(f"RQTransformer: code_sum must be one of {CODE_SUMS}, got {code_sum!r}")
+        self.img_num_tokens = img_num_tokens
+        self.depth_num_tokens = depth_num_tokens
+        self.vocab_cond_size = vocab_cond_size
+        self.vocab_img_size = vocab_img_size
+        self.embed_dim = embed_dim
+        self.spatial_n_heads = spatial_n_heads
+        self.depth_n_heads = depth_n_heads
+        self.code_sum = code_sum
+        self.tok_emb_cond = nn.Embedding(vocab_cond_size, embed_dim)
+        self.pos_emb_cond = nn.Parameter(torch.rand(1, cond_num_tokens, embed_dim))
+        self.tok_emb_code = nn.Embedding(vocab_img_size, embed_dim)
+        self.pos_emb_code = nn.Parameter(torch.rand(1, img_num_tokens, embed_dim))
+        self.pos_emb_depth = nn.Parameter(torch.rand(1, depth_num_tokens - 1, embed_dim))
+        self.spatial_transformer = nn.Sequential(*[Block(ctx_len=cond_num_tokens + img_num_tokens, cond_len=cond_num_tokens, embed_dim=embed_dim,
+                                                         n_heads=spatial_n_heads, mlp_bias=mlp_bias, attn_bias=attn_bias)
+                                                   for _ in range(spatial_n_layers)])
+        self.depth_transformer = nn.Sequential(*[Block(ctx_len=depth_num_tokens, cond_len=0, embed_dim=embed_dim, n_heads=depth_n_heads,
+                                                       mlp_bias=mlp_bias, attn_bias=attn_bias) for _ in range(depth_n_layers)])
+        self.ln_spatial = nn.LayerNorm(embed_dim)
+        self.ln_depth = nn.LayerNorm(embed_dim)
+        self.head = nn.Linear(embed_dim, vocab_img_size, bias=False)
+        self.apply(self._init_weights)
+        self._operands = {}       # operand format -> (versions of the masters, operand copies)
+        self._fwd_states = {}     # (chunk, dtype, device) -> the buffers of forward()
+        self.forward_hidden_cap = FORWARD_HIDDEN_CAP
+
+    _init_weights = GPT._init_weights
+    _on_device_conds = GPT._on_device_conds
+    _operand_dtype = staticmethod(GPT._operand_dtype)
+
+    @torch.no_grad()
+    def forward(self, codes: torch.Tensor, conds: torch.Tensor, *, use_fp16: bool = True, return_loss: bool = False):
+        """reference layers.py:370-395: logits [B T, D, V] (f32) of every code given the condition, the positions before it and the shallower
+        codes of its own position; with return_loss=True (logits, nll [B T, D], mean): the cross-entropy against `codes` and its mean (the
+        reference's val/total_loss), both on the device.  codes [B, T, D] (or [B, h, w, D]), conds [B] or [B, 1].
+
+        Inference only: the call runs under torch.no_grad.  The spatial stream has S = T rows (the condition and the first T - 1 positions:
+        position T - 1's codes reach only its own depth slots).  use_fp16=True runs the 16-bit operand format of ENH_PRECISION as GPT.forward
+        does, with the short-sequence attention (csrc/rq_prefill.hip) in the depth transformer; ENH_RQ_DEPTH_ATTN=tile runs it on the tile kernel
+        of the spatial transformer at N = D instead (A/B only).  False is the exact mode.  Device tensors only.  Batches run in chunks of whole
+        images sized so that the depth transformer's hidden activation ([chunk T D, 4C], f32 and its operand copy) stays under
+        `forward_hidden_cap` bytes.  A module whose parameters are not on the device of `codes` is moved there."""
+        if not (torch.is_tensor(codes) and torch.is_tensor(conds) and codes.is_cuda and conds.is_cuda):
+            raise NotImplementedError("RQTransformer.forward runs on a ROCm device only: codes and conds must be device tensors (there is no CPU path "
+                                      "for the teacher-forced forward)")
+        from ... import _C
+        dev = codes.device
+        B, T, D, V = codes.shape[0], self.img_num_tokens, self.depth_num_tokens, self.vocab_img_size
+        if codes.shape[-1] != D or codes.numel() != B * T * D:
+            raise ValueError(f"RQTransformer.forward: codes must be [B, img_num_tokens = {T}, depth_num_tokens = {D}], got {tuple(codes.shape)}")
+        codes = codes.reshape(B, T, D).to(torch.int64).contiguous()
+        conds = self._on_device_conds(conds, B, "RQTransformer.forward")
+        if int(codes.min()) < 0 or int(codes.max()) >= V:
+            raise ValueError(f"RQTransformer.forward: codes outside [0, {V})")
+        if int(conds.min()) < 0 or int(conds.max()) >= self.vocab_cond_size:
+            raise ValueError(f"RQTransformer.forward: conds outside [0, {self.vocab_cond_size})")
+        dt = self._operand_dtype(use_fp16, "RQTransformer.forward")
+        chunk = max(1, min(B, int(self.forward_hidden_cap) // (T * D * 4 * self.embed_dim * (4 + (2 if use_fp16 else 0)))))
+        logits = torch.empty(B * T, D, V, dtype=torch.float32, device=dev)
+        nll = torch.empty(B * T, D, dtype=torch.float32, device=dev) if return_loss else None
+        st = self._forward_state(chunk, dt, dev)
+        for s in range(0, B, chunk):
+            e = min(s + chunk, B)
+            self._forward_rows(st, codes[s:e], conds[s:e], logits[s * T:e * T], dt)
+            if return_loss:
+                _C.cross_entropy_rows(logits[s * T:e * T].view(-1, V), codes[s:e].reshape(-1), nll[s * T:e * T].view(-1))
+        if not return_loss:
+            return logits
+        mean = torch.empty(1, dtype=torch.float32, device=dev)
+        _C.mean_f32(nll.view(-1), mean)
+        return logits, nll, mean[0]
+
+    def _forward_state(self, b: int, dt: torch.dtype, dev) -> dict:
+        """the buffers of a chunk of b images, kept per (b, dtype): the spatial stream xs [b T, C], the depth stream xd [b T D, C] and the
+        activations at the depth transformer's row count, whose leading b T rows serve the spatial transformer"""
+        key = (b, dt, str(dev))
+        st = self._fwd_states.get(key)
+        if st is None:
+            f32, C, Ms = torch.float32, self.embed_dim, b * self.img_num_tokens
+            M = Ms * self.depth_num_tokens
+            e = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=dev)
+            st = dict(xs=e(Ms, C, dtype=f32), xd=e(M, C, dtype=f32), x2=e(M, C, dtype=f32), a=e(M, C), qkv=e(M, 3 * C), att=e(M, C),
+                      hid32=e(M, 4 * C, dtype=f32), hid=e(M, 4 * C) if dt != f32 else None)
+            self._fwd_states = {key: st}      # one chunk size at a time
+        return st
+
+    def _embed_channels(self, codes, conds, xs, xd) -> None:
+        """code_sum="channels": the reference's cumsum along the embedding channels, with torch ops on the device"""
+        b, T, D = codes.shape
+        C = self.embed_dim
+        cs = self.tok_emb_code.weight.detach()[codes].cumsum(-1)      # [b, T, D, C]
+        xs = xs.view(b, T, C)
+        xs[:, 0] = self.tok_emb_cond.weight.detach()[conds] + self.pos_emb_cond.detach()[0, 0]
+        xs[:, 1:] = cs[:, :T - 1, D - 1] + self.pos_emb_code.detach()[0, :T - 1]
+        xd.view(b * T, D, C)[:, 1:] = cs[:, :, :D - 1].reshape(b * T, D - 1, C) + self.pos_emb_depth.detach()[0]
+
+    def _forward_rows(self, st, codes, conds, logits, dt) -> None:
+        """one chunk of b whole images: logits [b T, D, V] f32.  The embedding stage, the spatial Blocks over b sequences of T rows (GPT's launches),
+        ln_spatial into slot 0 of the depth stream, the depth Blocks over b T sequences of D rows, ln_depth and the head."""
+        from ... import _C
+        b, T, D, C, V = codes.shape[0], self.img_num_tokens, self.depth_num_tokens, self.embed_dim, self.vocab_img_size
+        Ms, M = b * T, b * T * D
+        Hs, Hd = self.spatial_n_heads, self.depth_n_heads
+        ops = self._operand_copies(dt)
+        xs, xd = st["xs"][:Ms], st["xd"][:M]
+        if self.code_sum == "depth":
+            _C.rq_embed_seq(conds, codes, self.tok_emb_cond.weight.detach(), self.pos_emb_cond.detach()[0, 0], self.tok_emb_code.weight.detach(),
+                            self.pos_emb_code.detach()[0], self.pos_emb_depth.detach()[0], xs.view(b, T, C), xd.view(Ms, D, C))
+        else:
+            self._embed_channels(codes, conds, xs, xd)
+        x2, a, qkv, att, hid32, hid = (None if st[k] is None else st[k][:Ms] for k in ("x2", "a", "qkv", "att", "hid32", "hid"))
+        linear = _row_linear(Ms, dt)
+        for blk, W in zip(self.spatial_transformer, ops["spatial"]):
+            _block_rows(blk, W, linear, dt, T, lambda q, o: _C.causal_attention(q, b, T, Hs, C // Hs, o), xs, xs, a, a, qkv, att, x2, hid32, hid)
+        _C.ln_rows_strided(xs, self.ln_spatial.weight, self.ln_spatial.bias, xd, D * C, eps=self.ln_spatial.eps)
+        x2, a, qkv, att, hid32, hid = (None if st[k] is None else st[k][:M] for k in ("x2", "a", "qkv", "att", "hid32", "hid"))
+        linear = _row_linear(M, dt)
+        if dt == torch.float32 or os.environ.get("ENH_RQ_DEPTH_ATTN") == "tile":
+            attention = lambda q, o: _C.causal_attention(q, Ms, D, Hd, C // Hd, o)
+        else:
+            attention = lambda q, o: _C.short_causal_attention(q, Ms, D, Hd, C // Hd, o)
+        for blk, W in zip(self.depth_transformer, ops["depth"]):
+            _block_rows(blk, W, linear, dt, D, attention, xd, xd, a, a, qkv, att, x2, hid32, hid)
+        _C.ln_timeshift(xd, self.ln_depth.weight, self.ln_depth.bias, a, D, eps=self.ln_depth.eps)
+        linear(a, ops["head"], logits.view(M, V))
+
+    def _operand_copies(self, dt: torch.dtype):
+        """the GEMM weights in the operand format `dt`, built once from the fp32 masters and rebuilt when a master was replaced or written in
+        place (load_state_dict): the masters' version counters are the key, as in GPT._operand_copies"""
+        masters = [p for _, p in sorted(self.named_parameters())]
+        key = tuple((p.data_ptr(), p._version) for p in masters)
+        hit = self._operands.get(dt)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        cast = (lambda w: w.detach().to(dt).contiguous())
+        ops = dict(spatial=_layer_operands(self.spatial_transformer, cast), depth=_layer_operands(self.depth_transformer, cast),
+                   head=cast(self.head.weight))
+        self._operands[dt] = (key, ops)
+        return ops

@@ -2,14 +2,17 @@
 draws codes on the device and decodes them with the tokenizer; `forward` / `validation_step` give the teacher-forced logits and the reference's
 val/total_loss; `loss_and_grads` returns the training loss and leaves the gradient of every GPT parameter on the device (GPT.forward_backward);
 `configure_optimizers` returns the reference's Adam as one device launch (engine/optim.py GPTAdam) and `training_step` runs the loss-scaled
-forward + backward against it (Trainer.fit drives both, on one GPU)."""
+forward + backward against it (Trainer.fit drives both, on one GPU).
+
+With an `RQTransformer` and a residual stage 1 (codes [B, N, D]) `forward`, `shared_step` and `validation_step` work the same way; `sample`,
+`loss_and_grads`, `training_step` and `configure_optimizers` raise NotImplementedError: the RQ prior's sampling, backward and optimizer are not built."""
 from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from ...utils.general import initialize_from_config
-from .layers import GPT  # noqa: F401  (the reference's `from .layers import *`)
+from .layers import GPT, RQTransformer  # noqa: F401  (the reference's `from .layers import *`)
 
 
 class CondTransformer(nn.Module):
@@ -54,6 +57,7 @@ class CondTransformer(nn.Module):
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
                use_fp16: bool = True, **kw) -> torch.Tensor:
         """reference transformer.py:78-95.  **kw goes to GPT.sample (seed, forced_codes, ...).  The drawn codes are kept in `last_codes`."""
+        self._gpt_only("sample", "RQ sampling (the spatial / depth decode loop)")
         conds = conds.view(conds.shape[0], -1)
         kw.setdefault("return_logits", False)
         _, codes = self.transformer.sample(conds=conds, top_k=top_k, top_p=top_p, softmax_temperature=softmax_temperature, use_fp16=use_fp16, **kw)
@@ -70,6 +74,11 @@ class CondTransformer(nn.Module):
         if x.dtype == torch.double:
             x = x.float()
         return x.contiguous()
+
+    def _gpt_only(self, what: str, missing: str) -> None:
+        if isinstance(getattr(self, "transformer", None), RQTransformer):
+            raise NotImplementedError(f"CondTransformer.{what} with an RQTransformer: {missing} is not built (the teacher-forced forward and the "
+                                      "validation loss are: forward, shared_step, validation_step)")
 
     def log(self, name: str, value, **_) -> None:
         """Lightning's ``self.log`` as the stage-1 module keeps it: the last value per name, in `logged`"""
@@ -95,6 +104,7 @@ class CondTransformer(nn.Module):
     def loss_and_grads(self, batch, batch_idx: int = 0, *, loss_scale: float = 1.0) -> torch.Tensor:
         """shared_step's prologue, then GPT.forward_backward: returns the unscaled training loss (also logged as train/total_loss) and leaves
         loss_scale x its gradient in `.grad` of every parameter of the transformer.  training_step is this with the optimizer's device loss scale."""
+        self._gpt_only("loss_and_grads", "the RQ prior's backward")
         codes, conds = self._tokenize(batch)
         loss = self.transformer.forward_backward(codes, conds, loss_scale=loss_scale)
         self.log("train/total_loss", loss, on_step=True, on_epoch=True, prog_bar=True, logger=True)
@@ -111,6 +121,7 @@ class CondTransformer(nn.Module):
         device loss scale (fp16 operands; none under bf16), log train/total_loss and return the unscaled loss.  zero_grad=False adds to the
         gradients of the batches before it (accumulate_grad_batches).  The optimizer of configure_optimizers() then steps: Trainer.fit, or
         `opt.step()` by hand."""
+        self._gpt_only("training_step", "RQ training (the backward and the optimizer step)")
         opt = self.__dict__.get("_optimizer")
         if opt is None:
             raise NotImplementedError("stage-2 training needs its optimizer first: set `learning_rate` and call configure_optimizers() before "
@@ -125,6 +136,7 @@ class CondTransformer(nn.Module):
         """reference transformer.py:132-194: Adam(lr, betas=(0.9, 0.96)) with the L2 decay 0.01 on the Linear weights only -> ([GPTAdam], schedulers)
         (engine/optim.py; one launch over the GPT's flat buffers).  The transformer must be on the device.  Calling it again builds a new optimizer
         (fresh moments) over the same parameters."""
+        self._gpt_only("configure_optimizers", "RQ training (the optimizer step)")
         lr = self.__dict__.get("learning_rate")
         if lr is None:
             raise NotImplementedError("stage-2 training needs a learning rate: set `model.learning_rate` (main.py does) before configure_optimizers()")

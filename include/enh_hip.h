@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 26  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 27  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -650,6 +650,24 @@ int enh_relu_sq_h16(const float* x, void* y, int64_t n, int dtype, void* stream)
  * fixed-order pass writes mean[0] = sum(nll) / M.  enh_mean_f32 is that pass alone (the mean over several calls' rows). */
 int enh_cross_entropy_rows(const float* logits, const int64_t* target, int64_t M, int V, float* nll, float* mean, void* stream);
 int enh_mean_f32(const float* v, int64_t M, float* mean, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 RQTransformer, teacher-forced forward (csrc/rq_prefill.hip): what it needs beyond the GPT's kernels above.  No float atomics.
+ * ------------------------------------------------------------------------------------------------ */
+/* The embedding stage of B images of T positions with Dp codes each (2 <= Dp <= 8; codes [B, T, Dp] contiguous), one launch.
+ * spatial [B, T, C] f32: row (b, 0) = tok_cond[conds[b]] + pos_cond, row (b, s) = sum_j tok_code[codes[b, s - 1, j]] + pos_code[s - 1] (S = T rows:
+ * position T - 1 has none).  depth [B T, Dp, C] f32: slot d >= 1 of sequence b T + t = sum_{j < d} tok_code[codes[b, t, j]] + pos_depth[d - 1]; slot 0
+ * is left alone (enh_ln_rows_strided writes it).  Sums in ascending depth, one rounding per addition.  C % 4 == 0; ids outside a table are clamped. */
+int enh_rq_embed_seq(const int64_t* conds, const int64_t* codes, const float* tok_cond, const float* pos_cond, const float* tok_code,
+                     const float* pos_code, const float* pos_depth, int B, int T, int Dp, int C, int Vc, int V, float* spatial, float* depth,
+                     void* stream);
+/* LayerNorm (biased variance, f32 statistics) of M contiguous rows of width D (D % 8 == 0, D <= 8192); row m of the f32 output starts at
+ * out + m out_stride (out_stride >= D, a multiple of 4): ln_spatial written into slot 0 of every depth sequence. */
+int enh_ln_rows_strided(const float* x, const float* w, const float* b, int64_t M, int D, float eps, float* out, int64_t out_stride, void* stream);
+/* Causal softmax attention of NSEQ sequences of L tokens, 1 <= L <= 8: qkv packed [NSEQ, L, 3 H D], out [NSEQ, L, H D], lse [NSEQ, H, L] f32 or NULL;
+ * D a multiple of 64 up to 384 (anything else: ENH_E_SHAPE).  The arithmetic contract of enh_causal_attention_forward (f32 scores, exp(s - max)
+ * rounded to the format before P V, one rounding of out); eight lanes own a (sequence, head) pair and a workgroup 32 pairs, nothing staged in LDS. */
+int enh_short_causal_attention_forward(const enh_h16* qkv, int NSEQ, int L, int H, int D, float scale, enh_h16* out, float* lse, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stage-2 GPT, backward of the teacher-forced forward (csrc/gpt_attn_bwd.hip: the attention, csrc/gpt_rows.hip: the row kernels).  The gradient

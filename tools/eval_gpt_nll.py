@@ -2,7 +2,8 @@
 before it.  python tools/eval_gpt_nll.py -c configs/imagenet_gpt_vitvq_base.yaml --ckpt last.ckpt [--split validation | --synthetic N]
 
 Builds the config's CondTransformer, loads `--ckpt` (a {"state_dict": ...} file; without it the config's own `path` entries or the random init are
-used) and runs CondTransformer.validation_step (tokenizer -> teacher-forced GPT.forward -> device cross-entropy) over the config's dataset split, or
+used) and runs CondTransformer.validation_step (tokenizer -> teacher-forced GPT.forward or RQTransformer.forward -> device cross-entropy; an RQ
+prior has depth_num_tokens codes per position) over the config's dataset split, or
 over N images of the in-repo synthetic generator at the tokenizer's resolution.  Prints one JSON line: the mean NLL in nats per code (batches
 weighted by their size), bits per code, and the counts."""
 import argparse
@@ -46,7 +47,7 @@ def main(argv=None):
         data.setup()
         loader = {"train": data.train_dataloader, "validation": data.val_dataloader, "test": data.test_dataloader}[args.split]()
     total, codes, images = 0.0, 0, 0
-    T = model.transformer.img_num_tokens
+    T = model.transformer.img_num_tokens * getattr(model.transformer, "depth_num_tokens", 1)      # codes per image (RQTransformer: D per position)
     for i, batch in enumerate(loader):
         if args.max_batches is not None and i >= args.max_batches:
             break
