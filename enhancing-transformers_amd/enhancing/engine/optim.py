@@ -206,10 +206,10 @@ class GPTAdam(_GradClip):
 
     Building it changes where the GPT's tensors live, not their values:
       * the parameters are re-homed, one by one (never two copies of the model), into one flat f32 buffer `p` with `GPT.flat_grad`'s layout
-        (registration order, each padded to 64 elements); state_dict keys and load_state_dict keep working (load_state_dict copies in place);
+        (modules/stage2/prior.py `flat_layout`); state_dict keys and load_state_dict keep working (load_state_dict copies in place);
       * flat `m` and `v` are allocated, and the flat gradient (`GPT._flat_grads`);
-      * the 16-bit GEMM operands move into one arena ([3C, C] wqkv | wproj | w0 | w1 per layer, then the head) that the step kernel rewrites in the
-        same pass as the masters; `GPT._operand_copies` returns views into it and the per-layer copies it kept before are dropped.  The small f32
+      * the 16-bit GEMM operands move into one arena ([3C, C] wqkv | wproj | w0 | w1 per layer: prior.py `ARENA_LAYER`, then the head) that the
+        step kernel rewrites in the same pass as the masters; `GPT._operand_copies` returns views into it and the per-layer copies it kept before are dropped.  The small f32
         copies that are no view of a master (the q | k | v bias concatenation) are rebuilt with torch after every step.
     Moving or replacing the parameters afterwards, or changing ENH_PRECISION, is refused with an error by the GPT and by step().
 
@@ -223,6 +223,7 @@ class GPTAdam(_GradClip):
         import os
         import torch
         from .. import _C
+        from ..modules.stage2.prior import ARENA_LAYER, ARENA_LAYER_SIZE, flat_layout, qkv_bias
         params = list(gpt.named_parameters())
         if not params or not all(p.is_cuda for _, p in params):
             raise RuntimeError("GPTAdam: the GPT's parameters must be on a ROCm device (model.to('cuda') first): the optimizer step is a HIP kernel and "
@@ -239,42 +240,39 @@ class GPTAdam(_GradClip):
                              dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0.0, names=no_decay)]
         self.grad_scale = 1.0
         self._clip_out = None
-        # ---- flat masters: GPT._flat_grads' layout ----
-        offs, total = [], 0
-        for _, p in params:
-            offs.append(total)
-            total += (p.numel() + 63) // 64 * 64
+        # ---- flat masters: the gradients' layout ----
+        layout, total = flat_layout(gpt)
         self.p = torch.zeros(total, dtype=torch.float32, device=dev)
         with torch.no_grad():
-            for (_, p), o in zip(params, offs):
-                dst = self.p[o:o + p.numel()].view(p.shape)
+            for (_, p), (o, n) in zip(params, layout):
+                dst = self.p[o:o + n].view(p.shape)
                 dst.copy_(p.data)
                 p.data = dst          # the old storage is released here, one parameter at a time
         self.m = torch.zeros_like(self.p)
         self.v = torch.zeros_like(self.p)
         self.state = torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64, device=dev)      # t, beta1^t, beta2^t
-        # ---- operand arena ----
-        C, V, L = gpt.embed_dim, gpt.vocab_img_size, len(gpt.blocks)
-        per_layer = 12 * C * C
-        self.arena = torch.zeros(L * per_layer + V * C, dtype=self.dt, device=dev)
-        where = {"head.weight": L * per_layer}
-        for i in range(L):
-            b = i * per_layer
-            for nm, o in (("attn.query", 0), ("attn.key", C * C), ("attn.value", 2 * C * C), ("attn.proj", 3 * C * C), ("mlp.p0", 4 * C * C),
-                          ("mlp.p1", 8 * C * C)):
-                where[f"blocks.{i}.{nm}.weight"] = b + o
+        # ---- operand arena: one ARENA_LAYER slice per Block, stack after stack, then the head ----
+        C, V, stacks = gpt.embed_dim, gpt.vocab_img_size, gpt._block_stacks()
+        CC = C * C
+        head = sum(len(stack) for _, stack in stacks.values()) * ARENA_LAYER_SIZE * CC
+        self.arena = torch.zeros(head + V * C, dtype=self.dt, device=dev)
+        gpt._operands.clear()          # the per-layer copies (22 GB at the shipped size)
+        where, ops, base = {"head.weight": head}, dict(head=self.arena[head:].view(V, C)), 0      # where: master -> its offset in the arena
+        for key, (attr, stack) in stacks.items():
+            ops[key] = []
+            for i, blk in enumerate(stack):
+                W = dict(bqkv=qkv_bias(blk.attn), time_mix=blk.attn.time_mix.detach().reshape(-1))
+                for operand, masters, off, r, c in ARENA_LAYER:
+                    o = base + off * CC
+                    W[operand] = self.arena[o:o + r * c * CC].view(r * C, c * C)
+                    for j, nm in enumerate(masters):
+                        where[f"{attr}.{i}.{nm}.weight"] = o + j * (r * c * CC // len(masters))
+                ops[key].append(W)
+                base += ARENA_LAYER_SIZE * CC
         wd_of = {n: weight_decay for n in decay}
-        segs = [(o, o + p.numel(), where.get(n, -1), wd_of.get(n, 0.0)) for (n, p), o in zip(params, offs)]
+        segs = [(o, o + n_el, where.get(n, -1), wd_of.get(n, 0.0)) for (n, _), (o, n_el) in zip(params, layout)]
         self._dst = [(p, where[n]) for n, p in params if n in where]
         self.table = _C.adam_segment_table(segs, total, self.arena.numel(), dev)
-        gpt._operands.clear()          # the per-layer copies (22 GB at the shipped size)
-        ops = dict(layers=[], head=self.arena[L * per_layer:].view(V, C))
-        for i, blk in enumerate(gpt.blocks):
-            a, b = blk.attn, i * per_layer
-            view = lambda o, r, c: self.arena[b + o:b + o + r * c].view(r, c)
-            bqkv = torch.cat([a.query.bias, a.key.bias, a.value.bias]).detach().float().contiguous() if a.query.bias is not None else None
-            ops["layers"].append(dict(wqkv=view(0, 3 * C, C), bqkv=bqkv, wproj=view(3 * C * C, C, C), w0=view(4 * C * C, 4 * C, C),
-                                      w1=view(8 * C * C, C, 4 * C), time_mix=a.time_mix.detach().reshape(-1)))
         self._ptrs = tuple(p.data_ptr() for _, p in params)
         gpt._arena = dict(dt=self.dt, ptrs=self._ptrs, ops=ops, versions=None, refresh=self.refresh_operands)
         self.refresh_operands()
@@ -309,11 +307,10 @@ class GPTAdam(_GradClip):
         gpt._arena["versions"] = tuple(p._version for p in gpt.parameters())
 
     def _refresh_bias_copies(self) -> None:
-        import torch
-        for blk, W in zip(self.gpt.blocks, self.gpt._arena["ops"]["layers"]):
-            if W["bqkv"] is not None:
-                a = blk.attn
-                torch.cat([a.query.bias.detach(), a.key.bias.detach(), a.value.bias.detach()], out=W["bqkv"])
+        from ..modules.stage2.prior import qkv_bias
+        for key, (_, stack) in self.gpt._block_stacks().items():
+            for blk, W in zip(stack, self.gpt._arena["ops"][key]):
+                qkv_bias(blk.attn, out=W["bqkv"])
 
     def zero_grad(self, set_to_none: bool = False) -> None:
         if self.gpt.flat_grad is not None:

@@ -1,0 +1,316 @@
+"""What the stage-2 priors of layers.py (GPT, RQTransformer) and their optimizer (engine/optim.py GPTAdam) share, each stated once: the limits of
+the kernels, the launches of one Block over whole sequences forward (`_block_rows`) and backward (`_block_rows_backward`) with the products between
+them (`_row_linear`, `_grad_linears`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`), the flat parameter layout
+(`flat_layout`), a layer's slice of the optimizer's operand arena (`ARENA_LAYER`), and `Prior`, the base class: init, input checks, the
+version-keyed operand cache, the one-chunk-at-a-time buffer cache and the teacher-forced driver (chunks, cross-entropy rows, mean)."""
+import os
+
+import torch
+import torch.nn as nn
+
+MAX_BATCH = 64          # rows of one decode step (enh_skinny_gemm_h16); larger batches run in chunks
+MAX_EMBED = 8192        # enh_row_ln_scale
+MAX_VOCAB = 16384       # enh_sample_logits
+MAX_HEAD = 384          # enh_decode_attention
+MAX_TOKENS = 8192       # enh_decode_attention: slots of the k / v cache
+FORWARD_HIDDEN_CAP = 2 << 30   # bytes of forward()'s [chunk T, 4C] hidden activation (f32 + operand copy): shipped size, 6 sequences per chunk
+OPERAND_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
+
+# one layer's slice of GPTAdam's 16-bit operand arena: (operand, the Linear masters that are its row blocks, offset / C^2, rows / C, cols / C)
+ARENA_LAYER = (("wqkv", ("attn.query", "attn.key", "attn.value"), 0, 3, 1), ("wproj", ("attn.proj",), 3, 1, 1), ("w0", ("mlp.p0",), 4, 4, 1),
+               ("w1", ("mlp.p1",), 8, 1, 4))
+ARENA_LAYER_SIZE = sum(r * c for *_, r, c in ARENA_LAYER)      # 12, in units of C^2
+
+
+def check_limits(who: str, embed_dim: int, heads: dict, cond_num_tokens: int, vocab_img_size: int, img_num_tokens: int) -> None:
+    """the shapes the kernels take, as ValueErrors of class `who`; heads: constructor argument -> head count"""
+    if cond_num_tokens != 1:
+        raise ValueError(f"{who}: cond_num_tokens must be 1 (class conditioning: every sampling step is one token), got {cond_num_tokens}")
+    for arg, n in heads.items():
+        if embed_dim % n:
+            raise ValueError(f"{who}: embed_dim {embed_dim} is not a multiple of {arg} {n}")
+        if (embed_dim // n) % 64 or embed_dim // n > MAX_HEAD:
+            raise ValueError(f"{who}: the head size embed_dim / {arg} must be a multiple of 64 up to {MAX_HEAD}, got {embed_dim // n}")
+    if vocab_img_size > MAX_VOCAB:
+        raise ValueError(f"{who}: vocab_img_size must be at most {MAX_VOCAB}, got {vocab_img_size}")
+    if embed_dim > MAX_EMBED:
+        raise ValueError(f"{who}: embed_dim must be at most {MAX_EMBED}, got {embed_dim}")
+    if vocab_img_size % 8:
+        raise ValueError(f"{who}: vocab_img_size must be a multiple of 8 (the head's GEMM), got {vocab_img_size}")
+    if img_num_tokens > MAX_TOKENS:
+        raise ValueError(f"{who}: img_num_tokens must be at most {MAX_TOKENS} (the cache of the decode attention), got {img_num_tokens}")
+
+
+def flat_layout(module: nn.Module):
+    """([(offset, numel) per parameter], total): the flat f32 buffers of gradients, masters and moments (engine/stage1.py ParamStore's layout:
+    registration order, every parameter padded to 64 elements)"""
+    table, total = [], 0
+    for _, p in module.named_parameters():
+        table.append((total, p.numel()))
+        total += (p.numel() + 63) // 64 * 64
+    return table, total
+
+
+def qkv_bias(attn, out=None):
+    """the q | k | v bias concatenation, one f32 vector beside the fused [3C, C] weight (None without biases); out= rewrites an earlier one"""
+    if attn.query.bias is None:
+        return None
+    return torch.cat([lin.bias.detach() for lin in (attn.query, attn.key, attn.value)], out=out).float().contiguous()
+
+
+def _layer_operands(blocks, cast) -> list:
+    """per Block: the fused q|k|v weight and bias, proj, p0 and p1 through `cast`, and time_mix as a flat f32 vector"""
+    layers = []
+    for blk in blocks:
+        a, m = blk.attn, blk.mlp
+        layers.append(dict(wqkv=cast(torch.cat([a.query.weight, a.key.weight, a.value.weight], 0)), bqkv=qkv_bias(a), wproj=cast(a.proj.weight),
+                           w0=cast(m.p0.weight), w1=cast(m.p1.weight), time_mix=a.time_mix.detach().reshape(-1).contiguous()))
+    return layers
+
+
+# ---- the products --------------------------------------------------------------------------------------------------------------------------
+def _row_linear(M: int, dt: torch.dtype):
+    """linear(inp, w, out, bias, res, relu_sq) over the leading M rows: out = inp w^T (+ bias) (+ res) in the operand format `dt`"""
+    from ... import _C
+    if dt == torch.float32:
+        def linear(inp, w, out, bias=None, res=None, relu_sq=False):      # tree-ordered sums: enh_gemm_f32 adds K terms in ascending order
+            for m0 in range(0, M, MAX_BATCH):
+                m1 = min(m0 + MAX_BATCH, M)
+                _C.skinny_gemm_f32(inp[m0:m1], w, out[m0:m1], bias=bias, relu_sq=relu_sq, res=None if res is None else res[m0:m1])
+    else:
+        def linear(inp, w, out, bias=None, res=None, relu_sq=False):
+            N, K = w.shape
+            if out.dtype == torch.float32:
+                _C.gemm(inp, w, M, N, K, bias=bias, res=res, res_rows=M if res is not None else 0, out_f32=out)
+            else:
+                _C.gemm(inp, w, M, N, K, bias=bias, out_bf16=out)
+    return linear
+
+
+def _grad_linears(M: int, Mp: int, accumulate: bool):
+    """(wgrad, dgrad), the two products of a linear layer's backward over a chunk of M rows in buffers of Mp = M rounded up to 8 (the contraction
+    length of a weight-gradient product; the tail rows of its operands are zero)"""
+    from ... import _C
+
+    def wgrad(dy, inp, grad, n_out: int, k_in: int, lda=None):      # grad [n_out, k_in] (+)= dy^T inp over the chunk's Mp rows
+        _C.gemm(dy, inp, n_out, k_in, Mp, trans_a=True, trans_b=True, accumulate=accumulate, out_f32=grad, lda=lda, ldb=k_in)
+
+    def dgrad(dy, w, out):      # out [M, K] = dy [M, N] w [N, K]
+        N, K = w.shape
+        if out.dtype == torch.float32:
+            _C.gemm(dy, w, M, K, N, trans_b=True, out_f32=out)
+        else:
+            _C.gemm(dy, w, M, K, N, trans_b=True, out_bf16=out)
+    return wgrad, dgrad
+
+
+# ---- one Block over whole sequences --------------------------------------------------------------------------------------------------------
+def _block_rows(blk, W, linear, dt, S: int, attention, x, x_out, a, a2, qkv, att, x2, hid32, hid) -> None:
+    """the launches of one Block over whole sequences of S rows: x -> x_out (both f32).  attention(qkv, att) is the block's causal attention."""
+    from ... import _C
+    _C.ln_timeshift(x, blk.ln1.weight, blk.ln1.bias, a, S, colscale=W["time_mix"], eps=blk.ln1.eps)
+    linear(a, W["wqkv"], qkv, bias=W["bqkv"])
+    attention(qkv, att)
+    linear(att, W["wproj"], x2, bias=blk.attn.proj.bias, res=x)
+    _C.ln_timeshift(x2, blk.ln2.weight, blk.ln2.bias, a2, S, eps=blk.ln2.eps)
+    if dt == torch.float32:
+        linear(a2, W["w0"], hid32, bias=blk.mlp.p0.bias, relu_sq=True)
+        linear(hid32, W["w1"], x_out, bias=blk.mlp.p1.bias, res=x2)
+    else:
+        # relu^2 on the f32 product, one rounding to the operand format (in place on a 16-bit product it would be two)
+        linear(a2, W["w0"], hid32, bias=blk.mlp.p0.bias)
+        _C.relu_sq(hid, hid32)
+        linear(hid, W["w1"], x_out, bias=blk.mlp.p1.bias, res=x2)
+
+
+def _block_rows_backward(blk, W, wgrad, dgrad, accumulate: bool, S: int, attention_backward, sv, st, g, g2, d32, g16, dh16, dqkv, datt, hid32) -> None:
+    """the backward of _block_rows, setting (accumulate=False) or adding to the Block's parameter gradients.  sv: what the forward
+    kept of the layer (x, a, qkv, att, lse, x2, a2, hid); st: the chunk's gradient buffers at their full Mp rows, which the weight-gradient
+    products contract over; g .. hid32: their leading M rows.  In: g, the f32 gradient of the Block's output, and g16, its operand copy; out: the
+    same two for the Block's input.  attention_backward(sv, datt, dqkv) is the backward of the block's causal attention."""
+    from ... import _C
+    at, ml = blk.attn, blk.mlp
+    M, C = g.shape
+    # p1, relu^2, p0
+    wgrad(st["g16"], sv["hid"], ml.p1.weight.grad, C, 4 * C)
+    if ml.p1.bias is not None:
+        _C.colsum(g16, M, C, ml.p1.bias.grad, accumulate)
+    dgrad(g16, W["w1"], hid32)
+    _C.relu_sq_backward(hid32, sv["hid"][:M], dh16)
+    wgrad(st["dh16"], sv["a2"], ml.p0.weight.grad, 4 * C, C)
+    if ml.p0.bias is not None:
+        _C.colsum(dh16, M, 4 * C, ml.p0.bias.grad, accumulate)
+    dgrad(dh16, W["w0"], d32)
+    _C.ln_timeshift_backward(d32, sv["x2"][:M], blk.ln2.weight, S, g2, blk.ln2.weight.grad, blk.ln2.bias.grad, dres=g, dx16=g16, eps=blk.ln2.eps,
+                             accumulate=accumulate)
+    # proj, attention, q | k | v
+    wgrad(st["g16"], sv["att"], at.proj.weight.grad, C, C)
+    if at.proj.bias is not None:
+        _C.colsum(g16, M, C, at.proj.bias.grad, accumulate)
+    dgrad(g16, W["wproj"], datt)
+    attention_backward(sv, datt, dqkv)
+    flat = st["dqkv"].view(-1)      # the gradient of the fused [3C, C] operand, split back: column block j of dqkv is lin's output gradient
+    for j, lin in enumerate((at.query, at.key, at.value)):
+        wgrad(flat[j * C:], sv["a"], lin.weight.grad, C, C, lda=3 * C)
+    if at.query.bias is not None:
+        _C.colsum(dqkv, M, 3 * C, st["dbqkv"], False)
+        for j, lin in enumerate((at.query, at.key, at.value)):
+            if accumulate:
+                lin.bias.grad.add_(st["dbqkv"][j * C:(j + 1) * C])
+            else:
+                lin.bias.grad.copy_(st["dbqkv"][j * C:(j + 1) * C])
+    dgrad(dqkv, W["wqkv"], d32)
+    _C.ln_timeshift_backward(d32, sv["x"][:M], blk.ln1.weight, S, g, blk.ln1.weight.grad, blk.ln1.bias.grad, b=blk.ln1.bias, colscale=W["time_mix"],
+                             dcolscale=at.time_mix.grad.view(-1), dres=g2, dx16=g16, eps=blk.ln1.eps, accumulate=accumulate)
+
+
+class Prior(nn.Module):
+    """the chassis under GPT and RQTransformer.  A subclass registers its parameters (the registration order is the flat layout), names its
+    stacks of Blocks in STACKS (operand key -> attribute) and gives `_forward_buffers` and `_forward_rows`."""
+    STACKS = {}
+
+    def __init__(self, vocab_cond_size: int, vocab_img_size: int, embed_dim: int, cond_num_tokens: int, img_num_tokens: int, **heads) -> None:
+        super().__init__()
+        check_limits(type(self).__name__, embed_dim, heads, cond_num_tokens, vocab_img_size, img_num_tokens)
+        self.img_num_tokens = img_num_tokens
+        self.vocab_cond_size = vocab_cond_size
+        self.vocab_img_size = vocab_img_size
+        self.embed_dim = embed_dim
+        self._operands = {}       # operand format -> (versions of the masters, operand copies)
+        self._fwd_states = {}     # (chunk, dtype, device) -> the buffers of forward()
+        self.forward_hidden_cap = FORWARD_HIDDEN_CAP
+        self._arena = None        # set by engine/optim.py GPTAdam: dict(dt, ptrs, ops, versions, refresh) — the operand arena its step kernel keeps current
+        self._grad_key = None     # the parameters whose .grad are views into flat_grad
+        self.flat_grad = None
+
+    def _init_weights(self, module: nn.Module) -> None:
+        if isinstance(module, (nn.Linear, nn.Embedding)):
+            module.weight.data.normal_(mean=0.0, std=0.02)
+            if isinstance(module, nn.Linear) and module.bias is not None:
+                module.bias.data.zero_()
+        elif isinstance(module, nn.LayerNorm):
+            module.bias.data.zero_()
+            module.weight.data.fill_(1.0)
+
+    def _block_stacks(self) -> dict:
+        """operand key -> (attribute name, the nn.Sequential of Blocks)"""
+        return {key: (attr, getattr(self, attr)) for key, attr in self.STACKS.items()}
+
+    # ---- what the entries begin with --------------------------------------------------------------
+    def _on_device_conds(self, conds: torch.Tensor, B: int, who: str) -> torch.Tensor:
+        """moves a module whose parameters are elsewhere to the device of `conds`; returns the [B] int64 column of the one condition token per row"""
+        if self.head.weight.device != conds.device:
+            self.to(conds.device)
+        conds = conds.reshape(B, -1)
+        if conds.shape[1] != 1:
+            raise ValueError(f"{who}: one condition token per row (cond_num_tokens == 1), got {conds.shape[1]}")
+        return conds[:, 0].to(torch.int64).contiguous()
+
+    @staticmethod
+    def _operand_dtype(use_fp16: bool, who: str) -> torch.dtype:
+        """use_fp16 -> the 16-bit operand format of ENH_PRECISION (default fp16), else f32: the exact mode"""
+        if not use_fp16:
+            return torch.float32
+        prec = os.environ.get("ENH_PRECISION", "fp16")
+        if prec not in OPERAND_DTYPE:
+            raise ValueError(f"{who}(use_fp16=True): ENH_PRECISION must be 'fp16' or 'bf16' for the 16-bit mode, got {prec!r}")
+        return OPERAND_DTYPE[prec]
+
+    def _check_inputs(self, codes, conds, who: str, why: str = "there is no CPU path"):
+        """what the teacher-forced entries accept: device tensors, returned as (codes [B, T] int64, or [B, T, D] where the class has a depth_num_tokens,
+        conds [B] int64), ranges checked"""
+        if not (torch.is_tensor(codes) and torch.is_tensor(conds) and codes.is_cuda and conds.is_cuda):
+            raise NotImplementedError(f"{who} runs on a ROCm device only: codes and conds must be device tensors ({why})")
+        B, T, V, D = codes.shape[0], self.img_num_tokens, self.vocab_img_size, getattr(self, "depth_num_tokens", None)
+        if D is not None:
+            if codes.shape[-1] != D or codes.numel() != B * T * D:
+                raise ValueError(f"{who}: codes must be [B, img_num_tokens = {T}, depth_num_tokens = {D}], got {tuple(codes.shape)}")
+            codes = codes.reshape(B, T, D).to(torch.int64).contiguous()
+        else:
+            codes = codes.reshape(B, -1).to(torch.int64).contiguous()
+            if codes.shape[1] != T:
+                raise ValueError(f"{who}: codes must hold img_num_tokens = {T} codes per row, got {codes.shape[1]}")
+        conds = self._on_device_conds(conds, B, who)
+        if int(codes.min()) < 0 or int(codes.max()) >= V:
+            raise ValueError(f"{who}: codes outside [0, {V})")
+        if int(conds.min()) < 0 or int(conds.max()) >= self.vocab_cond_size:
+            raise ValueError(f"{who}: conds outside [0, {self.vocab_cond_size})")
+        return codes, conds
+
+    # ---- caches -----------------------------------------------------------------------------------
+    def _chunk_state(self, cache: str, build, b: int, dt: torch.dtype, dev) -> dict:
+        """build(b, dt, dev), the buffers of a chunk of b batch items, kept in the dict attribute `cache` from call to call; a shorter last chunk
+        uses their leading rows.  One chunk size at a time: the buffers of a shipped-size chunk are gigabytes"""
+        key = (b, dt, str(dev))
+        if key not in getattr(self, cache):
+            setattr(self, cache, {key: build(b, dt, dev)})
+        return getattr(self, cache)[key]
+
+    def _operand_copies(self, dt: torch.dtype):
+        """the GEMM weights in the operand format `dt` (torch.float32: the exact mode's packed f32 q|k|v): per stack of STACKS its
+        `_layer_operands`, and the head.  Built once from the fp32 masters and rebuilt when a master was replaced or written in place
+        (load_state_dict): the masters' version counters are the key.  Under a GPTAdam (`_arena`) the 16-bit operands are views into the
+        optimizer's arena, which its step kernel rewrites with the masters: nothing is rebuilt, and a module whose parameters were moved or
+        replaced since, or whose operand format changed, is refused."""
+        ar, who = self._arena, type(self).__name__
+        if ar is not None and dt != torch.float32:
+            if dt != ar["dt"]:
+                raise RuntimeError(f"{who}: the optimizer's operand arena holds {ar['dt']} but the engine's operand format (ENH_PRECISION) is now {dt}: "
+                                   "build a new GPTAdam (configure_optimizers) under the format you train in")
+            if tuple(p.data_ptr() for p in self.parameters()) != ar["ptrs"]:
+                raise RuntimeError(f"{who}: the parameters were moved or replaced after GPTAdam was built (.to(), .half(), assigning .data): the "
+                                   "optimizer's flat buffers and operand arena no longer belong to them; build a new GPTAdam (configure_optimizers)")
+            if tuple(p._version for p in self.parameters()) != ar["versions"]:      # torch wrote a master in place (load_state_dict): recast the arena
+                ar["refresh"]()
+            return ar["ops"]
+        masters = [p for _, p in sorted(self.named_parameters())]
+        key = tuple((p.data_ptr(), p._version) for p in masters)
+        hit = self._operands.get(dt)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        cast = (lambda w: w.detach().to(dt).contiguous())
+        ops = {k: _layer_operands(stack, cast) for k, (_, stack) in self._block_stacks().items()}
+        ops["head"] = cast(self.head.weight)
+        self._operands[dt] = (key, ops)
+        return ops
+
+    def _flat_grads(self, dev) -> torch.Tensor:
+        """one flat f32 buffer that every parameter's .grad is a view into (`flat_layout`), allocated on first use and kept while the parameters
+        stay where they are"""
+        params = list(self.named_parameters())
+        key = (str(dev),) + tuple(p.data_ptr() for _, p in params)
+        if self._grad_key != key or any(p.grad is None for _, p in params):
+            table, total = flat_layout(self)
+            self.flat_grad = torch.zeros(total, dtype=torch.float32, device=dev)
+            for (_, p), (o, n) in zip(params, table):
+                p.grad = self.flat_grad[o:o + n].view(p.shape)
+            self._grad_key = key
+        return self.flat_grad
+
+    # ---- the teacher-forced driver ------------------------------------------------------------------
+    def _teacher_forced(self, who: str, codes, conds, use_fp16: bool, return_loss: bool, why: str):
+        """forward() of both priors: logits (f32) and, with return_loss=True, (logits, nll, mean); nll has the shape of the codes with their
+        leading axes folded ([B, T], or [B T, D]), logits one more axis of V.  Batches run in chunks of whole batch items sized so that the MLP's
+        hidden activation ([rows, 4C], f32 and its operand copy) stays under `forward_hidden_cap` bytes;
+        `_forward_rows(st, codes, conds, logits [b, rows per item, V], dt)` runs a chunk in the buffers of `_forward_buffers`."""
+        codes, conds = self._check_inputs(codes, conds, who, why)
+        from ... import _C
+        dev, B, V = codes.device, codes.shape[0], self.vocab_img_size
+        dt = self._operand_dtype(use_fp16, who)
+        rows = codes[0].numel()       # of the hidden activation, per batch item
+        chunk = max(1, min(B, int(self.forward_hidden_cap) // (rows * 4 * self.embed_dim * (4 + (2 if use_fp16 else 0)))))
+        shape = codes.view(-1, codes.shape[-1]).shape
+        logits = torch.empty(*shape, V, dtype=torch.float32, device=dev)
+        nll = torch.empty(*shape, dtype=torch.float32, device=dev) if return_loss else None
+        st = self._chunk_state("_fwd_states", self._forward_buffers, chunk, dt, dev)
+        for s in range(0, B, chunk):
+            e = min(s + chunk, B)
+            lg = logits.view(B, rows, V)[s:e]
+            self._forward_rows(st, codes[s:e], conds[s:e], lg, dt)
+            if return_loss:
+                _C.cross_entropy_rows(lg.view(-1, V), codes[s:e].reshape(-1), nll.view(B, rows)[s:e].view(-1))
+        if not return_loss:
+            return logits
+        mean = torch.empty(1, dtype=torch.float32, device=dev)
+        _C.mean_f32(nll.view(-1), mean)
+        return logits, nll, mean[0]
