@@ -387,13 +387,14 @@ extern "C" int enh_relu_sq_backward(const float* dy, const enh_h16* y, enh_h16* 
 // condition, so a row needs its own statistics only (recomputed from x, as the forward recomputes its neighbour's).  Without colscale g = dy.
 // A workgroup walks GR_LNB_ROWS consecutive rows, one at a time as gpt_prefill_ln_kernel holds a row, and keeps its column sums of dw, db and
 // d tm in registers; they go to part[block][3][D], which gpt_ln_bwd_reduce_kernel adds in ascending block order.
+// Row m of dy starts at dy + m dys (dys = D: contiguous rows; rq_ln_strided_bwd_kernel below passes the stride of slot 0 of the depth sequences);
+// x, dres, dx and dx16 are contiguous [M, D].
 #define GR_LNB_ROWS 8
 template <typename OT>
-__global__ __launch_bounds__(256) void gpt_ln_timeshift_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ w,
-                                                                   const float* __restrict__ bias, const float* __restrict__ colscale,
-                                                                   const float* __restrict__ dres, int64_t M, int S, int D, float eps,
-                                                                   float* __restrict__ dx, uint16_t* __restrict__ dx16, float* __restrict__ part) {
-  __shared__ float s_red[4];
+__device__ __forceinline__ void gpt_ln_bwd_rows(const float* __restrict__ dy, int64_t dys, const float* __restrict__ x, const float* __restrict__ w,
+                                                const float* __restrict__ bias, const float* __restrict__ colscale, const float* __restrict__ dres, int64_t M,
+                                                int S, int D, float eps, float* __restrict__ dx, uint16_t* __restrict__ dx16, float* __restrict__ part,
+                                                float* s_red) {
   const int t = threadIdx.x;
   const int nv = D >> 2;
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -413,11 +414,11 @@ __global__ __launch_bounds__(256) void gpt_ln_timeshift_bwd_kernel(const float* 
       const int c = t + 256 * i;
       if (c >= nv) continue;
       const f32x4 gw = *reinterpret_cast<const f32x4*>(w + 4 * c);
-      f32x4 g = *reinterpret_cast<const f32x4*>(dy + m * D + 4 * c);
+      f32x4 g = *reinterpret_cast<const f32x4*>(dy + m * dys + 4 * c);
       const f32x4 xh = (v[i] - mean) * rstd;
       if (colscale) {
         const f32x4 tm = *reinterpret_cast<const f32x4*>(colscale + 4 * c), bb = *reinterpret_cast<const f32x4*>(bias + 4 * c);
-        const f32x4 gn = has_next ? *reinterpret_cast<const f32x4*>(dy + (m + 1) * D + 4 * c) : zero;
+        const f32x4 gn = has_next ? *reinterpret_cast<const f32x4*>(dy + (m + 1) * dys + 4 * c) : zero;
         at[i] = at[i] + (xh * gw + bb) * (g - gn);
         g = g * tm + gn * (1.0f - tm);
       }
@@ -456,6 +457,26 @@ __global__ __launch_bounds__(256) void gpt_ln_timeshift_bwd_kernel(const float* 
   }
 }
 
+template <typename OT>
+__global__ __launch_bounds__(256) void gpt_ln_timeshift_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ w,
+                                                                   const float* __restrict__ bias, const float* __restrict__ colscale,
+                                                                   const float* __restrict__ dres, int64_t M, int S, int D, float eps,
+                                                                   float* __restrict__ dx, uint16_t* __restrict__ dx16, float* __restrict__ part) {
+  __shared__ float s_red[4];
+  gpt_ln_bwd_rows<OT>(dy, (int64_t)D, x, w, bias, colscale, dres, M, S, D, eps, dx, dx16, part, s_red);
+}
+
+// The backward of rq_prefill.hip's rq_ln_strided_kernel (ln_spatial, whose output is slot 0 of every depth sequence): the same body over a strided dy
+// with the colscale / dres arguments passed as null pointers at run time, so the arithmetic is the instruction sequence of the kernel above.
+template <typename OT>
+__global__ __launch_bounds__(256) void rq_ln_strided_bwd_kernel(const float* __restrict__ dy, int64_t dys, const float* __restrict__ x, const float* __restrict__ w,
+                                                                const float* __restrict__ bias, const float* __restrict__ colscale,
+                                                                const float* __restrict__ dres, int64_t M, int D, float eps, float* __restrict__ dx,
+                                                                uint16_t* __restrict__ dx16, float* __restrict__ part) {
+  __shared__ float s_red[4];
+  gpt_ln_bwd_rows<OT>(dy, dys, x, w, bias, colscale, dres, M, 1, D, eps, dx, dx16, part, s_red);
+}
+
 // out_k[c] (+)= sum over blocks of part[block][k][c], ascending; blockIdx.y = k (0 dw, 1 db, 2 d colscale)
 __global__ __launch_bounds__(256) void gpt_ln_bwd_reduce_kernel(const float* __restrict__ part, int nblk, int D, float* __restrict__ dw, float* __restrict__ db,
                                                                 float* __restrict__ dcs, int accumulate) {
@@ -488,6 +509,24 @@ extern "C" int enh_ln_timeshift_backward(const float* dy, const float* x, const 
   ENH_DT_DISPATCH(dtype, (gpt_ln_timeshift_bwd_kernel<OT><<<(unsigned)nblk, 256, 0, s>>>(dy, x, w, b, colscale, dres, M, S, D, eps, dx, dx16, (float*)ws)));
   gpt_ln_bwd_reduce_kernel<<<dim3((unsigned)((D + 255) / 256), colscale ? 3 : 2), 256, 0, s>>>((const float*)ws, nblk, D, dw, db, colscale ? dcolscale : nullptr, accumulate);
   return enh_check_launch("enh_ln_timeshift_backward");
+}
+
+extern "C" int enh_ln_rows_strided_backward(const float* dy, int64_t dy_stride, const float* x, const float* w, int64_t M, int D, float eps, float* dx,
+                                            enh_h16* dx16, float* dw, float* db, int accumulate, void* ws, size_t ws_bytes, int dtype, void* stream) {
+  ENH_REQUIRE(dy && x && w && dx && dw && db, ENH_E_BADARG, "enh_ln_rows_strided_backward: null pointer");
+  ENH_REQUIRE_DT(dtype, "enh_ln_rows_strided_backward");
+  ENH_REQUIRE(M >= 1 && M <= 2147483647LL, ENH_E_SHAPE, "enh_ln_rows_strided_backward: M=%lld", (long long)M);
+  ENH_REQUIRE(D >= 8 && D <= GR_LN_MAX_D && D % 8 == 0, ENH_E_SHAPE, "enh_ln_rows_strided_backward: D must be a multiple of 8 in [8, %d], got %d", GR_LN_MAX_D, D);
+  ENH_REQUIRE(dy_stride >= D && dy_stride % 4 == 0, ENH_E_SHAPE, "enh_ln_rows_strided_backward: the row stride of dy must be a multiple of 4 that is at least D=%d, got %lld",
+              D, (long long)dy_stride);
+  ENH_REQUIRE(ws && ws_bytes >= enh_ln_timeshift_backward_workspace_bytes(M, D), ENH_E_WORKSPACE, "enh_ln_rows_strided_backward: workspace too small (%zu bytes)", ws_bytes);
+  const int nblk = (int)((M + GR_LNB_ROWS - 1) / GR_LNB_ROWS);
+  hipStream_t s = (hipStream_t)stream;
+  const float* none = nullptr;
+  enh_note_kernel("rq_ln_strided_bwd_kernel", dtype);
+  ENH_DT_DISPATCH(dtype, (rq_ln_strided_bwd_kernel<OT><<<(unsigned)nblk, 256, 0, s>>>(dy, dy_stride, x, w, none, none, none, M, D, eps, dx, dx16, (float*)ws)));
+  gpt_ln_bwd_reduce_kernel<<<dim3((unsigned)((D + 255) / 256), 2), 256, 0, s>>>((const float*)ws, nblk, D, dw, db, nullptr, accumulate);
+  return enh_check_launch("enh_ln_rows_strided_backward");
 }
 
 // ---------------------------------------------------------------------------------------------

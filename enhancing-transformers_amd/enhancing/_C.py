@@ -156,10 +156,13 @@ SIGNATURES = {
     "enh_ln_timeshift_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _i32, _vp]),
     "enh_gpt_embed_seq_backward": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "enh_sample_logits": (_i32, [_vp, _i32, _i32, _f32, _i32, _f32, _vp, _u64, _u32, _u32, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "enh_short_causal_attention_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp]),
+    "enh_ln_rows_strided_backward": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _i32, _vp]),
+    "enh_rq_embed_seq_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 
 _LIB = None
-ABI_VERSION = 27  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 28  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -1299,3 +1302,57 @@ def gpt_embed_seq_backward(g, conds, codes, dtok_cond, dpos_cond, dtok_code, dpo
                                                            dpos_code.shape[0], _p(dtok_cond, F32, "dtok_cond"), _p(dpos_cond, F32, "dpos_cond"),
                                                            _p(dtok_code, F32, "dtok_code"), _p(dpos_code, F32, "dpos_code"), int(accumulate), _stream()),
                           "enh_gpt_embed_seq_backward"), unit="byte")
+
+
+# ------------------------------------------------------------------------------------------------
+# stage-2 RQTransformer backward (csrc/rq_backward.hip; the strided LayerNorm backward: csrc/gpt_rows.hip)
+# ------------------------------------------------------------------------------------------------
+def short_causal_attention_backward(qkv, out, dout, lse, NSEQ: int, L: int, H: int, D: int, dqkv, scale: Optional[float] = None):
+    """dqkv [NSEQ,L,3*H*D] of short_causal_attention from qkv, the out and lse [NSEQ,H,L] it stored, and dout [NSEQ,L,H*D]; 16-bit tensors of one
+    format; L <= 8"""
+    scale = float(D) ** -0.5 if scale is None else float(scale)
+    if qkv.numel() != NSEQ * L * 3 * H * D or dqkv.numel() != qkv.numel() or out.numel() != NSEQ * L * H * D or dout.numel() != out.numel() \
+            or lse.numel() != NSEQ * H * L:
+        raise RuntimeError(f"short_causal_attention_backward: qkv {tuple(qkv.shape)} out {tuple(out.shape)} dout {tuple(dout.shape)} lse {tuple(lse.shape)} "
+                           f"do not fit NSEQ={NSEQ} L={L} H={H} D={D}")
+    L_ = lib()
+    # algorithmic HBM bytes: q, k, v, out and dout read once, dq, dk and dv written once
+    _timed(None, 16.0 * NSEQ * L * H * D,
+           lambda: _check(L_.enh_short_causal_attention_backward(_p(qkv, H16, "qkv"), _p(out, H16, "out"), _p(dout, H16, "dout"), _p(lse, F32, "lse"), NSEQ, L, H,
+                                                                 D, scale, _p(dqkv, H16, "dqkv"), _dt(qkv, out, dout, dqkv), _stream()),
+                          "enh_short_causal_attention_backward"), unit="byte")
+
+
+def ln_rows_strided_backward(dy, dy_stride: int, x, w, dx, dw, db, dx16=None, eps: float = 1e-5, accumulate: bool = False):
+    """backward of ln_rows_strided: row m of dy is dy.view(-1)[m * dy_stride:][:D] (`dy` any contiguous f32 tensor that holds those rows; nothing
+    between them is read), x [M,D] f32 -> dx f32 [M,D], dx16 an optional 16-bit copy; dw, db [D] set or (accumulate) added to"""
+    M, D = x.shape
+    if w.numel() != D or dw.numel() != D or db.numel() != D or dx.numel() != M * D or dy.numel() < (M - 1) * int(dy_stride) + D \
+            or (dx16 is not None and dx16.numel() != M * D):
+        raise RuntimeError(f"ln_rows_strided_backward: x {tuple(x.shape)} with row stride {dy_stride} does not fit dy {tuple(dy.shape)}, dx {tuple(dx.shape)}")
+    L = lib()
+    nb = L.enh_ln_timeshift_backward_workspace_bytes(M, D)
+    ws = _workspace(nb, x.device)
+    _timed(None, 4.0 * M * D * 3,
+           lambda: _check(L.enh_ln_rows_strided_backward(_p(dy, F32, "dy"), int(dy_stride), _p(x, F32, "x"), _p(w, F32, "w"), M, D, eps, _p(dx, F32, "dx"),
+                                                         _p(dx16, H16, "dx16"), _p(dw, F32, "dw"), _p(db, F32, "db"), int(accumulate), _p(ws), ws.numel(),
+                                                         _dt(dx16), _stream()), "enh_ln_rows_strided_backward"), unit="byte")
+
+
+def rq_embed_seq_backward(gs, gd, conds, codes, dtok_cond, dpos_cond, dtok_code, dpos_code, dpos_depth, accumulate: bool = False):
+    """gradients of rq_embed_seq's five tables from gs [B,T,C] and gd [B*T,D,C] f32 (slot 0 of gd is not read): dtok_cond [Vc,C], dpos_cond [C],
+    dtok_code [V,C], dpos_code [P >= T-1, C], dpos_depth [D-1, C]; conds [B], codes [B,T,D] int64 contiguous"""
+    B, T, C = gs.shape
+    if conds.dtype != I64 or conds.numel() != B or codes.dtype != I64 or codes.dim() != 3 or tuple(codes.shape[:2]) != (B, T):
+        raise RuntimeError("rq_embed_seq_backward: conds [B] and codes [B,T,D] must be int64 device tensors")
+    D = codes.shape[2]
+    if tuple(gd.shape) != (B * T, D, C) or dpos_code.dim() != 2 or dpos_code.shape[0] < T - 1 or dpos_code.shape[1] != C or tuple(dpos_depth.shape) != (D - 1, C) \
+            or dtok_cond.shape[1] != C or dtok_code.shape[1] != C or dpos_cond.numel() != C:
+        raise RuntimeError(f"rq_embed_seq_backward: gd {tuple(gd.shape)}, dpos_code {tuple(dpos_code.shape)}, dpos_depth {tuple(dpos_depth.shape)} do not fit "
+                           f"B={B} T={T} D={D} C={C}")
+    _timed(None, 4.0 * (B * T * D * C + dtok_cond.numel() + dtok_code.numel() + dpos_code.numel() + dpos_depth.numel() + C),
+           lambda: _check(lib().enh_rq_embed_seq_backward(_p(gs, F32, "gs"), _p(gd, F32, "gd"), _p(conds, I64, "conds"), _p(codes, I64, "codes"), B, T, D, C,
+                                                          dtok_cond.shape[0], dtok_code.shape[0], dpos_code.shape[0], _p(dtok_cond, F32, "dtok_cond"),
+                                                          _p(dpos_cond, F32, "dpos_cond"), _p(dtok_code, F32, "dtok_code"), _p(dpos_code, F32, "dpos_code"),
+                                                          _p(dpos_depth, F32, "dpos_depth"), int(accumulate), _stream()),
+                          "enh_rq_embed_seq_backward"), unit="byte")

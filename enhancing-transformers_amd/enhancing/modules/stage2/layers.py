@@ -12,11 +12,11 @@ copies, the input checks, the chunked teacher-forced driver, the limits) is prio
   * `forward_backward` is that forward with its activations kept per layer, then a hand-written backward (§3.7; `_block_rows_backward`): weight
     gradients accumulate in f32 into one flat buffer that every `p.grad` is a view into.  16-bit operand formats only.
 
-`RQTransformer` (reference layers.py:306-547), the prior over a residual quantizer's [B, T, D] codes: `forward` only (§3.9).  Its spatial and
-depth transformers are stacks of the same Blocks; the embedding stage, ln_spatial into slot 0 of the depth sequences and the attention over B T
-sequences of D <= 8 slots are csrc/rq_prefill.hip.
+`RQTransformer` (reference layers.py:306-547), the prior over a residual quantizer's [B, T, D] codes: `forward` (§3.9) and `forward_backward`
+(§3.10).  Its spatial and depth transformers are stacks of the same Blocks; the embedding stage, ln_spatial into slot 0 of the depth sequences and
+the attention over B T sequences of D <= 8 slots are csrc/rq_prefill.hip, their backward csrc/rq_backward.hip.
 
-Left out: RQTransformer's sampling, backward and optimizer step, an exact-f32 backward, more than one condition token, HIP-graph capture, relu^2 /
+Left out: RQTransformer's sampling, an exact-f32 backward, more than one condition token, HIP-graph capture, relu^2 /
 LayerNorm fused into GEMM epilogues."""
 import os
 from typing import Optional, Tuple
@@ -87,7 +87,7 @@ class GPT(Prior):
         """reference layers.py:193-211: logits [B, T, V] (f32) of every code given the condition and the codes before it; with return_loss=True
         (logits, nll [B, T], mean): the per-position cross-entropy against `codes` and its mean (the reference's val/total_loss), both on the device.
 
-        Inference only: the call runs under torch.no_grad and the result carries no autograd graph (stage-2 training is not built).
+        Inference only: the call runs under torch.no_grad and the result carries no autograd graph (training is forward_backward).
         S = T rows are built, the condition and the first T - 1 codes: the causal mask keeps the last code's row from every logit that is kept.
         use_fp16=True runs the 16-bit operand format of ENH_PRECISION (default fp16) through enh_gemm_h16 and the MFMA causal attention; biases,
         residuals and LayerNorms stay on the f32 residual stream.  False is the exact mode: f32 operands, tree-ordered sums (enh_skinny_gemm_f32
@@ -164,28 +164,8 @@ class GPT(Prior):
         activations saved for the backward stay under `backward_saved_cap` bytes (saved_bytes_per_token() per token row); weight gradients
         accumulate across the chunks in a fixed order, so two runs give the same bits.  Any B T works: a chunk's row buffers are rounded up to 8 rows
         and the tail rows of every gradient operand are zero.  The optimizer step and the overflow check are GPTAdam.step()."""
-        if not use_fp16:
-            raise NotImplementedError("GPT.forward_backward(use_fp16=False): the exact-f32 backward is not built; use the 16-bit operand format")
-        codes, conds = self._check_inputs(codes, conds, "GPT.forward_backward")
-        from ... import _C
-        dev, (B, T) = codes.device, codes.shape
-        dt = self._operand_dtype(True, "GPT.forward_backward")
-        chunk = max(1, min(B, int(self.backward_saved_cap) // (T * self.saved_bytes_per_token())))
-        self._flat_grads(dev)
-        st = self._chunk_state("_bwd_states", self._backward_buffers, chunk, dt, dev)
-        nll = torch.empty(B, T, dtype=torch.float32, device=dev)
-        scale_dev = None
-        if torch.is_tensor(loss_scale):
-            if not (loss_scale.is_cuda and loss_scale.dtype == torch.float32 and loss_scale.numel() == 1):
-                raise ValueError("GPT.forward_backward: a tensor loss_scale must be a device f32 tensor of one element")
-            scale_dev, loss_scale = loss_scale.view(1), 1.0
-        gscale = float(loss_scale) / float(B * T)
-        for s in range(0, B, chunk):
-            e = min(s + chunk, B)
-            self._backward_rows(st, codes[s:e], conds[s:e], nll[s:e], dt, gscale, accumulate=accumulate or s > 0, gscale_dev=scale_dev)
-        mean = torch.empty(1, dtype=torch.float32, device=dev)
-        _C.mean_f32(nll.view(-1), mean)
-        return mean[0]
+        return self._teacher_forced_backward("GPT.forward_backward", codes, conds, use_fp16, loss_scale, accumulate,
+                                             self.img_num_tokens * self.saved_bytes_per_token())
 
     def _backward_rows(self, st, codes, conds, nll, dt, gscale: float, accumulate: bool, gscale_dev=None) -> None:
         """one chunk: the saving forward, then the backward of DESIGN.md §3.7, setting (accumulate=False) or adding to every parameter's gradient:
@@ -301,7 +281,7 @@ class RQTransformer(Prior):
     """reference layers.py:306-395: a spatial transformer over the T positions of an image, whose input at a position is built from the D residual
     codes of the position before it, and a depth transformer over the D slots of every position: slot 0 is ln_spatial of the spatial output, slot
     d >= 1 is built from codes 0 .. d - 1 of the position; logits [B T, D, V].  The reference's constructor arguments, parameter names, shapes and
-    init.  Built here: the teacher-forced forward and the validation loss.  Not built: sampling, the backward, the optimizer step.
+    init.  Built here: the teacher-forced forward, the validation loss and forward_backward (training: engine/optim.py GPTAdam).  Not built: sampling.
 
     The code-sum quirk.  The reference's forward computes `codes.cumsum(-1)` on the [B, T, D, C] embeddings: a running sum along the embedding
     CHANNELS, not along depth.  Its own sampler (sample_spatial_step / sample_depth_step: `codes.sum(1)`) and the RQ-VAE formulation sum over
@@ -343,6 +323,8 @@ class RQTransformer(Prior):
         self.ln_depth = nn.LayerNorm(embed_dim)
         self.head = nn.Linear(embed_dim, vocab_img_size, bias=False)
         self.apply(self._init_weights)
+        self.backward_saved_cap = BACKWARD_SAVED_CAP      # bytes of forward_backward()'s saved activations of all layers in one chunk
+        self._bwd_states = {}     # (chunk, dtype, device) -> the buffers of forward_backward()
 
     @torch.no_grad()
     def forward(self, codes: torch.Tensor, conds: torch.Tensor, *, use_fp16: bool = True, return_loss: bool = False):
@@ -377,32 +359,169 @@ class RQTransformer(Prior):
         xs[:, 1:] = cs[:, :T - 1, D - 1] + self.pos_emb_code.detach()[0, :T - 1]
         xd.view(b * T, D, C)[:, 1:] = cs[:, :, :D - 1].reshape(b * T, D - 1, C) + self.pos_emb_depth.detach()[0]
 
-    def _forward_rows(self, st, codes, conds, logits, dt) -> None:
+    def _forward_rows(self, st, codes, conds, logits, dt, saved=None) -> None:
         """one chunk of b whole images: logits [b, T D, V] f32.  The embedding stage, the spatial Blocks over b sequences of T rows (GPT's launches),
-        ln_spatial into slot 0 of the depth stream, the depth Blocks over b T sequences of D rows, ln_depth and the head."""
+        ln_spatial into slot 0 of the depth stream, the depth Blocks over b T sequences of D rows, ln_depth and the head.  saved (forward_backward):
+        dict(spatial=[...], depth=[...]), one dict of buffers per layer as in GPT._forward_rows; a layer's input x, a, qkv, att, lse, x2, a2 and hid
+        then stay there (the embedding stage and ln_spatial write the first layers' x), and the stacks' outputs go to st["xs"] (the input of
+        ln_spatial) and st["xd"] (of ln_depth).  The launches and their arguments are the same: so are the bits."""
         from ... import _C
         b, T, D, C, V = codes.shape[0], self.img_num_tokens, self.depth_num_tokens, self.embed_dim, self.vocab_img_size
         Ms, M = b * T, b * T * D
         Hs, Hd = self.spatial_n_heads, self.depth_n_heads
         ops = self._operand_copies(dt)
         xs, xd = st["xs"][:Ms], st["xd"][:M]
+
+        def bufs(stack: str, i: int, R: int, x_last, n_lse: int):
+            """_block_rows' buffers of layer i of a stack over R rows (x, x_out, a, a2, qkv, att, x2, hid32, hid), then the attention's lse"""
+            x2, a, qkv, att, hid32, hid = (None if st[k] is None else st[k][:R] for k in ("x2", "a", "qkv", "att", "hid32", "hid"))
+            if saved is None:
+                return x_last, x_last, a, a, qkv, att, x2, hid32, hid, None
+            sv, nxt = saved[stack][i], saved[stack][i + 1:i + 2]
+            return (sv["x"][:R], nxt[0]["x"][:R] if nxt else x_last, sv["a"][:R], sv["a2"][:R], sv["qkv"][:R], sv["att"][:R], sv["x2"][:R], hid32,
+                    sv["hid"][:R], sv["lse"][:n_lse])
+
+        xs_in = bufs("spatial", 0, Ms, xs, 0)[0] if len(self.spatial_transformer) else xs
+        xd_in = bufs("depth", 0, M, xd, 0)[0] if len(self.depth_transformer) else xd
         if self.code_sum == "depth":
             _C.rq_embed_seq(conds, codes, self.tok_emb_cond.weight.detach(), self.pos_emb_cond.detach()[0, 0], self.tok_emb_code.weight.detach(),
-                            self.pos_emb_code.detach()[0], self.pos_emb_depth.detach()[0], xs.view(b, T, C), xd.view(Ms, D, C))
+                            self.pos_emb_code.detach()[0], self.pos_emb_depth.detach()[0], xs_in.view(b, T, C), xd_in.view(Ms, D, C))
         else:
-            self._embed_channels(codes, conds, xs, xd)
-        x2, a, qkv, att, hid32, hid = (None if st[k] is None else st[k][:Ms] for k in ("x2", "a", "qkv", "att", "hid32", "hid"))
+            self._embed_channels(codes, conds, xs_in, xd_in)
         linear = _row_linear(Ms, dt)
-        for blk, W in zip(self.spatial_transformer, ops["spatial"]):
-            _block_rows(blk, W, linear, dt, T, lambda q, o: _C.causal_attention(q, b, T, Hs, C // Hs, o), xs, xs, a, a, qkv, att, x2, hid32, hid)
-        _C.ln_rows_strided(xs, self.ln_spatial.weight, self.ln_spatial.bias, xd, D * C, eps=self.ln_spatial.eps)
-        x2, a, qkv, att, hid32, hid = (None if st[k] is None else st[k][:M] for k in ("x2", "a", "qkv", "att", "hid32", "hid"))
+        for i, (blk, W) in enumerate(zip(self.spatial_transformer, ops["spatial"])):
+            *rows, lse = bufs("spatial", i, Ms, xs, b * Hs * T)
+            _block_rows(blk, W, linear, dt, T, lambda q, o: _C.causal_attention(q, b, T, Hs, C // Hs, o, lse=lse), *rows)
+        _C.ln_rows_strided(xs, self.ln_spatial.weight, self.ln_spatial.bias, xd_in, D * C, eps=self.ln_spatial.eps)
         linear = _row_linear(M, dt)
-        if dt == torch.float32 or os.environ.get("ENH_RQ_DEPTH_ATTN") == "tile":
-            attention = lambda q, o: _C.causal_attention(q, Ms, D, Hd, C // Hd, o)
+        tile = dt == torch.float32 or os.environ.get("ENH_RQ_DEPTH_ATTN") == "tile"
+        for i, (blk, W) in enumerate(zip(self.depth_transformer, ops["depth"])):
+            *rows, lse = bufs("depth", i, M, xd, Ms * Hd * D)
+            if tile:
+                attention = lambda q, o: _C.causal_attention(q, Ms, D, Hd, C // Hd, o, lse=lse)
+            else:
+                attention = lambda q, o: _C.short_causal_attention(q, Ms, D, Hd, C // Hd, o, lse=lse)
+            _block_rows(blk, W, linear, dt, D, attention, *rows)
+        _C.ln_timeshift(xd, self.ln_depth.weight, self.ln_depth.bias, st["a"][:M], D, eps=self.ln_depth.eps)
+        linear(st["a"][:M], ops["head"], logits.view(M, V))
+
+    # ---- teacher-forced loss and its gradients -----------------------------------------------------
+    def saved_bytes_per_image(self) -> int:
+        """bytes forward_backward keeps per image for ALL layers: T rows per spatial layer and T D rows per depth layer, each row
+        GPT.saved_bytes_per_token()'s 28 C + 4 H of its stack"""
+        T, D, C = self.img_num_tokens, self.depth_num_tokens, self.embed_dim
+        return (len(self.spatial_transformer) * T * (28 * C + 4 * self.spatial_n_heads) +
+                len(self.depth_transformer) * T * D * (28 * C + 4 * self.depth_n_heads))
+
+    def _backward_buffers(self, b: int, dt: torch.dtype, dev) -> dict:
+        """the buffers of a chunk of b images.  Row counts are rounded up to 8 (the contraction length of a weight-gradient product): Mp for the
+        depth stage's b T D rows, Mps for the spatial stage's b T rows, which runs in the leading rows of the depth stage's gradient buffers
+        (`spatial`: their views of Mps rows) with a gradient stream of its own (gs: the depth stream's gradient g stays for the embedding).
+        Everything is zero at first so that the tail rows of an operand are finite."""
+        f32, C, V, T, D = torch.float32, self.embed_dim, self.vocab_img_size, self.img_num_tokens, self.depth_num_tokens
+        Hs, Hd = self.spatial_n_heads, self.depth_n_heads
+        Ms, M = b * T, b * T * D
+        Mps, Mp = (Ms + 7) // 8 * 8, (M + 7) // 8 * 8
+        z = lambda *shape, dtype=dt: torch.zeros(*shape, dtype=dtype, device=dev)
+        layer = lambda R, n_lse: dict(x=z(R, C, dtype=f32), a=z(R, C), qkv=z(R, 3 * C), att=z(R, C), lse=z(n_lse, dtype=f32), x2=z(R, C, dtype=f32),
+                                      a2=z(R, C), hid=z(R, 4 * C))
+        saved = dict(spatial=[layer(Mps, b * Hs * T) for _ in self.spatial_transformer], depth=[layer(Mp, Ms * Hd * D) for _ in self.depth_transformer])
+        st = dict(saved=saved, xs=z(Mps, C, dtype=f32), xd=z(Mp, C, dtype=f32), a=z(Mp, C), hid32=z(Mp, 4 * C, dtype=f32), logits=z(Mp, V, dtype=f32),
+                  dlogits=z(Mp, V), g=z(Mp, C, dtype=f32), gs=z(Mps, C, dtype=f32), g2=z(Mp, C, dtype=f32), d32=z(Mp, C, dtype=f32), g16=z(Mp, C),
+                  dh16=z(Mp, 4 * C), dqkv=z(Mp, 3 * C), datt=z(Mp, C), dbqkv=z(3 * C, dtype=f32), x2=None, qkv=None, att=None, hid=None)
+        st["spatial"] = dict(g16=st["g16"][:Mps], dh16=st["dh16"][:Mps], dqkv=st["dqkv"][:Mps], dbqkv=st["dbqkv"])
+        return st
+
+    @torch.no_grad()
+    def forward_backward(self, codes: torch.Tensor, conds: torch.Tensor, *, use_fp16: bool = True, loss_scale=1.0, accumulate: bool = False) -> torch.Tensor:
+        """GPT.forward_backward's contract for the RQ prior: returns the unscaled mean cross-entropy over all B T D codes (0-dim f32 on the device:
+        what forward(..., return_loss=True)[2] returns, and with the same chunking the same bits) and leaves in `p.grad` of EVERY parameter
+        loss_scale x the gradient of that mean (f32, views into `flat_grad`).  loss_scale is a float or a device f32 [1] tensor; the call SETS the
+        gradients, or with accumulate=True ADDS to them; rows of the token tables whose id is never fed are exactly zero when set.
+
+        use_fp16=True runs the 16-bit operand format of ENH_PRECISION; the exact-f32 backward is not built: use_fp16=False raises.  Device tensors
+        only.  The backward: the cross-entropy and the head, ln_depth, the depth Blocks last to first (`_block_rows_backward`
+        over sequences of D rows, with the short-sequence attention backward of csrc/rq_backward.hip; ENH_RQ_DEPTH_ATTN=tile runs the tile kernels
+        of the spatial stack at N = D instead: the A/B and the cross-check), ln_spatial through slot 0 of the depth stream's gradient
+        (enh_ln_rows_strided_backward), the spatial Blocks last to first over sequences of T rows, the embedding (enh_rq_embed_seq_backward).
+        Batches run in chunks of whole images sized so that the saved activations stay under `backward_saved_cap` bytes
+        (saved_bytes_per_image()); weight gradients accumulate across the chunks in a fixed order, so two runs give the same bits.
+
+        code_sum="channels" builds the embedding tables' gradients with torch ops (the reverse cumsum along the channels, index_add_): its
+        tok_emb_code.grad is then NOT bit-reproducible from run to run (index_add_ uses atomics).  Every launch behind the embedding is the
+        default mode's."""
+        return self._teacher_forced_backward("RQTransformer.forward_backward", codes, conds, use_fp16, loss_scale, accumulate,
+                                             self.saved_bytes_per_image())
+
+    def _embed_channels_backward(self, codes, conds, gs, gd, accumulate: bool) -> None:
+        """code_sum="channels": the backward of _embed_channels with torch ops on the device"""
+        b, T, D = codes.shape
+        C = self.embed_dim
+        gs, gd = gs.view(b, T, C), gd.view(b, T, D, C)
+        gcs = torch.zeros(b, T, D, C, dtype=torch.float32, device=gs.device)
+        gcs[:, :, :D - 1] = gd[:, :, 1:]
+        gcs[:, :T - 1, D - 1] += gs[:, 1:]
+        gemb = gcs.flip(-1).cumsum(-1).flip(-1)       # the gradient of cumsum along the channels
+        grads = (self.tok_emb_code.weight.grad, self.tok_emb_cond.weight.grad, self.pos_emb_code.grad, self.pos_emb_depth.grad, self.pos_emb_cond.grad)
+        if not accumulate:
+            for t in grads:
+                t.zero_()
+        grads[0].index_add_(0, codes.reshape(-1), gemb.view(-1, C))
+        grads[1].index_add_(0, conds, gs[:, 0])
+        grads[2][0, :T - 1] += gs[:, 1:].sum(0)
+        grads[3][0] += gd[:, :, 1:].sum((0, 1))
+        grads[4][0, 0] += gs[:, 0].sum(0)
+
+    def _backward_rows(self, st, codes, conds, nll, dt, gscale: float, accumulate: bool, gscale_dev=None) -> None:
+        """one chunk: the saving forward, then the backward of DESIGN.md §3.10, setting (accumulate=False) or adding to every parameter's gradient"""
+        from ... import _C
+        b, T, D, C, V = codes.shape[0], self.img_num_tokens, self.depth_num_tokens, self.embed_dim, self.vocab_img_size
+        Hs, Hd = self.spatial_n_heads, self.depth_n_heads
+        Ms, M = b * T, b * T * D
+        Mps, Mp = (Ms + 7) // 8 * 8, (M + 7) // 8 * 8
+        ops = self._operand_copies(dt)
+        saved = st["saved"]
+        for k in ("dlogits", "g16", "dh16", "dqkv"):      # rows M .. Mp - 1 of the gradient operands may hold a longer chunk's rows
+            st[k][M:Mp].zero_()
+        logits = st["logits"][:M]
+        self._forward_rows(st, codes, conds, logits.view(b, T * D, V), dt, saved=saved)
+        # the head, ln_depth and the depth Blocks: M rows, sequences of D
+        dlogits, g, g2, d32, g16, dh16, dqkv, datt, hid32 = (st[k][:M] for k in ("dlogits", "g", "g2", "d32", "g16", "dh16", "dqkv", "datt", "hid32"))
+        wgrad, dgrad = _grad_linears(M, Mp, accumulate)
+        if gscale_dev is None:
+            _C.cross_entropy_backward(logits, codes.reshape(-1), nll.view(-1), dlogits, gscale)
         else:
-            attention = lambda q, o: _C.short_causal_attention(q, Ms, D, Hd, C // Hd, o)
-        for blk, W in zip(self.depth_transformer, ops["depth"]):
-            _block_rows(blk, W, linear, dt, D, attention, xd, xd, a, a, qkv, att, x2, hid32, hid)
-        _C.ln_timeshift(xd, self.ln_depth.weight, self.ln_depth.bias, a, D, eps=self.ln_depth.eps)
-        linear(a, ops["head"], logits.view(M, V))
+            _C.cross_entropy_backward(logits, codes.reshape(-1), nll.view(-1), dlogits, gscale, gscale_dev=gscale_dev)
+        wgrad(st["dlogits"], st["a"], self.head.weight.grad, V, C)
+        dgrad(dlogits, ops["head"], d32)
+        ln = self.ln_depth
+        _C.ln_timeshift_backward(d32, st["xd"][:M], ln.weight, D, g, ln.weight.grad, ln.bias.grad, dx16=g16, eps=ln.eps, accumulate=accumulate)
+        if os.environ.get("ENH_RQ_DEPTH_ATTN") == "tile":
+            def depth_attention_backward(sv, datt_, dqkv_):
+                _C.causal_attention_backward(sv["qkv"][:M], sv["att"][:M], datt_, sv["lse"][:Ms * Hd * D], Ms, D, Hd, C // Hd, dqkv_)
+        else:
+            def depth_attention_backward(sv, datt_, dqkv_):
+                _C.short_causal_attention_backward(sv["qkv"][:M], sv["att"][:M], datt_, sv["lse"][:Ms * Hd * D], Ms, D, Hd, C // Hd, dqkv_)
+        for i in range(len(self.depth_transformer) - 1, -1, -1):
+            _block_rows_backward(self.depth_transformer[i], ops["depth"][i], wgrad, dgrad, accumulate, D, depth_attention_backward, saved["depth"][i], st,
+                                 g, g2, d32, g16, dh16, dqkv, datt, hid32)
+        # ln_spatial through slot 0 of the depth stream's gradient, then the spatial Blocks: Ms rows, sequences of T, in the leading rows of the
+        # same buffers.  The weight-gradient products now contract over Mps rows: the depth stage left its rows Ms .. Mps - 1 there.
+        for k in ("g16", "dh16", "dqkv"):
+            st[k][Ms:Mps].zero_()
+        gs, g2, d32, g16, dh16, dqkv, datt, hid32 = (st[k][:Ms] for k in ("gs", "g2", "d32", "g16", "dh16", "dqkv", "datt", "hid32"))
+        ln = self.ln_spatial
+        _C.ln_rows_strided_backward(st["g"], D * C, st["xs"][:Ms], ln.weight, gs, ln.weight.grad, ln.bias.grad, dx16=g16, eps=ln.eps, accumulate=accumulate)
+        wgrad, dgrad = _grad_linears(Ms, Mps, accumulate)
+
+        def spatial_attention_backward(sv, datt_, dqkv_):
+            _C.causal_attention_backward(sv["qkv"][:Ms], sv["att"][:Ms], datt_, sv["lse"][:b * Hs * T], b, T, Hs, C // Hs, dqkv_)
+
+        for i in range(len(self.spatial_transformer) - 1, -1, -1):
+            _block_rows_backward(self.spatial_transformer[i], ops["spatial"][i], wgrad, dgrad, accumulate, T, spatial_attention_backward,
+                                 saved["spatial"][i], st["spatial"], gs, g2, d32, g16, dh16, dqkv, datt, hid32)
+        if self.code_sum == "depth":
+            _C.rq_embed_seq_backward(gs.view(b, T, C), g.view(Ms, D, C), conds, codes, self.tok_emb_cond.weight.grad, self.pos_emb_cond.grad.view(-1),
+                                     self.tok_emb_code.weight.grad, self.pos_emb_code.grad.view(-1, C), self.pos_emb_depth.grad.view(-1, C), accumulate)
+        else:
+            self._embed_channels_backward(codes, conds, gs, g, accumulate)

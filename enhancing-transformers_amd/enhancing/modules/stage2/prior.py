@@ -2,7 +2,8 @@
 the kernels, the launches of one Block over whole sequences forward (`_block_rows`) and backward (`_block_rows_backward`) with the products between
 them (`_row_linear`, `_grad_linears`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`), the flat parameter layout
 (`flat_layout`), a layer's slice of the optimizer's operand arena (`ARENA_LAYER`), and `Prior`, the base class: init, input checks, the
-version-keyed operand cache, the one-chunk-at-a-time buffer cache and the teacher-forced driver (chunks, cross-entropy rows, mean)."""
+version-keyed operand cache, the one-chunk-at-a-time buffer cache and the two teacher-forced drivers (forward: chunks, cross-entropy rows, mean; forward_backward: chunks under the
+saved-activation cap, the loss scale, gradients set in the first chunk and added to in the later ones)."""
 import os
 
 import torch
@@ -314,3 +315,33 @@ class Prior(nn.Module):
         mean = torch.empty(1, dtype=torch.float32, device=dev)
         _C.mean_f32(nll.view(-1), mean)
         return logits, nll, mean[0]
+
+    def _teacher_forced_backward(self, who: str, codes, conds, use_fp16: bool, loss_scale, accumulate: bool, item_bytes: int) -> torch.Tensor:
+        """forward_backward() of both priors: the unscaled mean cross-entropy over every code, with loss_scale x its gradient left in every
+        parameter's .grad (views into `flat_grad`).  Batches run in chunks of whole batch items sized so that the activations saved for the
+        backward (`item_bytes` per item) stay under `backward_saved_cap` bytes;
+        `_backward_rows(st, codes, conds, nll, dt, gscale, accumulate, gscale_dev)` runs a chunk in the buffers of `_backward_buffers`, setting
+        the gradients in the first chunk (unless accumulate) and adding to them in the later ones."""
+        if not use_fp16:
+            raise NotImplementedError(f"{who}(use_fp16=False): the exact-f32 backward is not built; use the 16-bit operand format")
+        codes, conds = self._check_inputs(codes, conds, who)
+        from ... import _C
+        dev, B = codes.device, codes.shape[0]
+        dt = self._operand_dtype(True, who)
+        rows = codes[0].numel()       # codes per batch item
+        chunk = max(1, min(B, int(self.backward_saved_cap) // item_bytes))
+        self._flat_grads(dev)
+        st = self._chunk_state("_bwd_states", self._backward_buffers, chunk, dt, dev)
+        nll = torch.empty(B, rows, dtype=torch.float32, device=dev)
+        scale_dev = None
+        if torch.is_tensor(loss_scale):
+            if not (loss_scale.is_cuda and loss_scale.dtype == torch.float32 and loss_scale.numel() == 1):
+                raise ValueError(f"{who}: a tensor loss_scale must be a device f32 tensor of one element")
+            scale_dev, loss_scale = loss_scale.view(1), 1.0
+        gscale = float(loss_scale) / float(B * rows)
+        for s in range(0, B, chunk):
+            e = min(s + chunk, B)
+            self._backward_rows(st, codes[s:e], conds[s:e], nll[s:e], dt, gscale, accumulate=accumulate or s > 0, gscale_dev=scale_dev)
+        mean = torch.empty(1, dtype=torch.float32, device=dev)
+        _C.mean_f32(nll.view(-1), mean)
+        return mean[0]

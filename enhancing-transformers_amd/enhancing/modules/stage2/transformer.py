@@ -1,11 +1,11 @@
-"""CondTransformer (reference enhancing/modules/stage2/transformer.py:23-95): a condition model, a frozen stage-1 tokenizer and the GPT prior; `sample`
-draws codes on the device and decodes them with the tokenizer; `forward` / `validation_step` give the teacher-forced logits and the reference's
-val/total_loss; `loss_and_grads` returns the training loss and leaves the gradient of every GPT parameter on the device (GPT.forward_backward);
-`configure_optimizers` returns the reference's Adam as one device launch (engine/optim.py GPTAdam) and `training_step` runs the loss-scaled
-forward + backward against it (Trainer.fit drives both, on one GPU).
+"""CondTransformer (reference enhancing/modules/stage2/transformer.py:23-95): a condition model, a frozen stage-1 tokenizer and the prior (GPT, or
+RQTransformer over a residual stage 1's codes [B, N, D]); `sample` draws codes on the device and decodes them with the tokenizer; `forward` /
+`validation_step` give the teacher-forced logits and the reference's val/total_loss; `loss_and_grads` returns the training loss and leaves the
+gradient of every parameter of the prior on the device (forward_backward); `configure_optimizers` returns the reference's Adam as one device launch
+(engine/optim.py GPTAdam) and `training_step` runs the loss-scaled forward + backward against it (Trainer.fit drives both, on one GPU).
 
-With an `RQTransformer` and a residual stage 1 (codes [B, N, D]) `forward`, `shared_step` and `validation_step` work the same way; `sample`,
-`loss_and_grads`, `training_step` and `configure_optimizers` raise NotImplementedError: the RQ prior's sampling, backward and optimizer are not built."""
+With an `RQTransformer`, `sample` raises NotImplementedError (RQ sampling is not built), and training exists on a ROCm device only: a prior that
+is elsewhere is refused before the tokenizer runs."""
 from typing import List, Optional, Tuple
 
 import torch
@@ -77,8 +77,16 @@ class CondTransformer(nn.Module):
 
     def _gpt_only(self, what: str, missing: str) -> None:
         if isinstance(getattr(self, "transformer", None), RQTransformer):
-            raise NotImplementedError(f"CondTransformer.{what} with an RQTransformer: {missing} is not built (the teacher-forced forward and the "
-                                      "validation loss are: forward, shared_step, validation_step)")
+            raise NotImplementedError(f"CondTransformer.{what} with an RQTransformer: {missing} is not built (the teacher-forced forward, the "
+                                      "validation loss and training are)")
+
+    def _rq_on_device(self, what: str) -> None:
+        """with an RQTransformer: refuses a prior that is not on a ROCm device, before anything is tokenized (the batch itself may come from the
+        host, as Trainer.fit's does: the tokenizer moves it)"""
+        tr = getattr(self, "transformer", None)
+        if isinstance(tr, RQTransformer) and not tr.head.weight.is_cuda:
+            raise NotImplementedError(f"CondTransformer.{what} with an RQTransformer: RQ training runs on a ROCm device only (the RQ prior's backward "
+                                      "and its optimizer step are HIP kernels: there is no CPU path); move the transformer to the device first")
 
     def log(self, name: str, value, **_) -> None:
         """Lightning's ``self.log`` as the stage-1 module keeps it: the last value per name, in `logged`"""
@@ -102,9 +110,9 @@ class CondTransformer(nn.Module):
         return loss
 
     def loss_and_grads(self, batch, batch_idx: int = 0, *, loss_scale: float = 1.0) -> torch.Tensor:
-        """shared_step's prologue, then GPT.forward_backward: returns the unscaled training loss (also logged as train/total_loss) and leaves
+        """shared_step's prologue, then the prior's forward_backward: returns the unscaled training loss (also logged as train/total_loss) and leaves
         loss_scale x its gradient in `.grad` of every parameter of the transformer.  training_step is this with the optimizer's device loss scale."""
-        self._gpt_only("loss_and_grads", "the RQ prior's backward")
+        self._rq_on_device("loss_and_grads")
         codes, conds = self._tokenize(batch)
         loss = self.transformer.forward_backward(codes, conds, loss_scale=loss_scale)
         self.log("train/total_loss", loss, on_step=True, on_epoch=True, prog_bar=True, logger=True)
@@ -117,14 +125,15 @@ class CondTransformer(nn.Module):
         return loss
 
     def training_step(self, batch, batch_idx: int, optimizer_idx: int = 0, *, zero_grad: bool = True) -> torch.Tensor:
-        """reference transformer.py:120-124 with Lightning's backward folded in: tokenize the batch, run GPT.forward_backward with the optimizer's
+        """reference transformer.py:120-124 with Lightning's backward folded in: tokenize the batch, run the prior's forward_backward with the optimizer's
         device loss scale (fp16 operands; none under bf16), log train/total_loss and return the unscaled loss.  zero_grad=False adds to the
         gradients of the batches before it (accumulate_grad_batches).  The optimizer of configure_optimizers() then steps: Trainer.fit, or
         `opt.step()` by hand."""
-        self._gpt_only("training_step", "RQ training (the backward and the optimizer step)")
+        self._rq_on_device("training_step")
         opt = self.__dict__.get("_optimizer")
         if opt is None:
-            raise NotImplementedError("stage-2 training needs its optimizer first: set `learning_rate` and call configure_optimizers() before "
+            who = "RQ training" if isinstance(getattr(self, "transformer", None), RQTransformer) else "stage-2 training"
+            raise NotImplementedError(f"{who} needs its optimizer first: set `learning_rate` and call configure_optimizers() before "
                                       "training_step (it builds the flat buffers and the loss scale the step runs against)")
         codes, conds = self._tokenize(batch)
         scale = opt.loss_scale
@@ -134,9 +143,9 @@ class CondTransformer(nn.Module):
 
     def configure_optimizers(self):
         """reference transformer.py:132-194: Adam(lr, betas=(0.9, 0.96)) with the L2 decay 0.01 on the Linear weights only -> ([GPTAdam], schedulers)
-        (engine/optim.py; one launch over the GPT's flat buffers).  The transformer must be on the device.  Calling it again builds a new optimizer
+        (engine/optim.py; one launch over the prior's flat buffers).  The transformer must be on the device.  Calling it again builds a new optimizer
         (fresh moments) over the same parameters."""
-        self._gpt_only("configure_optimizers", "RQ training (the optimizer step)")
+        self._rq_on_device("configure_optimizers")
         lr = self.__dict__.get("learning_rate")
         if lr is None:
             raise NotImplementedError("stage-2 training needs a learning rate: set `model.learning_rate` (main.py does) before configure_optimizers()")

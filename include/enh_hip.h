@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 27  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 28  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -701,6 +701,31 @@ int enh_ln_timeshift_backward(const float* dy, const float* x, const float* w, c
  * Only codes 0 .. S - 2 of a sequence are fed.  accumulate != 0 adds to the four tables instead of setting them.  C % 4 == 0, C <= 8192. */
 int enh_gpt_embed_seq_backward(const float* g, const int64_t* conds, const int64_t* codes, int64_t code_stride, int B, int S, int C, int Vc, int V, int P,
                                float* dtok_cond, float* dpos_cond, float* dtok_code, float* dpos_code, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 RQTransformer, backward of the teacher-forced forward (csrc/rq_backward.hip; the strided LayerNorm backward shares its body with
+ * enh_ln_timeshift_backward in csrc/gpt_rows.hip).  The Blocks of both stacks run the GPT's backward kernels above.  No float atomics.
+ * ------------------------------------------------------------------------------------------------ */
+/* dqkv [NSEQ, L, 3 H D] (16-bit) of enh_short_causal_attention_forward from qkv, the out and lse [NSEQ, H, L] it stored, and dout [NSEQ, L, H D];
+ * 1 <= L <= 8, D a multiple of 64 up to 384.  The arithmetic contract of enh_causal_attention_backward (P from lse, delta on the stored out, P and
+ * P o (dP - delta) rounded to the format before their products, one rounding of dq, dk, dv; row 0 of dQ exact zeros).  Eight lanes own a
+ * (sequence, head) pair and write all of its dq, dk and dv: no workspace, nothing staged in LDS. */
+int enh_short_causal_attention_backward(const enh_h16* qkv, const enh_h16* out, const enh_h16* dout, const float* lse, int NSEQ, int L, int H, int D,
+                                        float scale, enh_h16* dqkv, int dtype, void* stream);
+/* Backward of enh_ln_rows_strided: row m of dy starts at dy + m dy_stride (dy_stride >= D, a multiple of 4; nothing between the rows is read), x [M, D]
+ * contiguous.  dx f32 [M, D], dx16 an optional copy in the operand format; dw, db [D] set, or added to under `accumulate`.  The workspace is
+ * enh_ln_timeshift_backward_workspace_bytes(M, D); the bits are those of enh_ln_timeshift_backward(colscale = NULL, dres = NULL, S = 1) on a
+ * compacted copy of dy. */
+int enh_ln_rows_strided_backward(const float* dy, int64_t dy_stride, const float* x, const float* w, int64_t M, int D, float eps, float* dx, enh_h16* dx16,
+                                 float* dw, float* db, int accumulate, void* ws, size_t ws_bytes, int dtype, void* stream);
+/* Backward of enh_rq_embed_seq from gs [B, T, C] f32 (the gradient of the spatial stream) and gd [B T, Dp, C] f32 (of the depth stream; slot 0 is
+ * never read).  Every fed occurrence (b, t, j) of a code adds [t <= T - 2] gs[b, t + 1] + sum_{d = j + 1}^{Dp - 1} gd[(b, t), d] to its row of
+ * dtok_code [V, C], in ascending (b, t, j) order, the spatial term first, then d ascending; code (b, T - 1, Dp - 1) is never fed.  dpos_code [P, C]
+ * (row t = sum_b gs[b, t + 1] for t <= T - 2, zero beyond), dpos_depth [Dp - 1, C] (row d - 1 = sum_{b, t} gd[(b, t), d]), dtok_cond [Vc, C]
+ * (row conds[b] += gs[b, 0]) and dpos_cond [C].  Rows that do not occur are zero; accumulate != 0 adds to the five tables and leaves those rows
+ * alone.  2 <= Dp <= 8, C % 4 == 0, C <= 8192; ids outside a table are clamped. */
+int enh_rq_embed_seq_backward(const float* gs, const float* gd, const int64_t* conds, const int64_t* codes, int B, int T, int Dp, int C, int Vc, int V, int P,
+                              float* dtok_cond, float* dpos_cond, float* dtok_code, float* dpos_code, float* dpos_depth, int accumulate, void* stream);
 
 #ifdef __cplusplus
 }
