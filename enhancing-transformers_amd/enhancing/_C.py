@@ -159,10 +159,12 @@ SIGNATURES = {
     "enh_short_causal_attention_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp]),
     "enh_ln_rows_strided_backward": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _i32, _vp]),
     "enh_rq_embed_seq_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "enh_rq_embed_step": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "enh_short_decode_attention": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
 }
 
 _LIB = None
-ABI_VERSION = 28  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 29  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -1356,3 +1358,36 @@ def rq_embed_seq_backward(gs, gd, conds, codes, dtok_cond, dpos_cond, dtok_code,
                                                           _p(dpos_cond, F32, "dpos_cond"), _p(dtok_code, F32, "dtok_code"), _p(dpos_code, F32, "dpos_code"),
                                                           _p(dpos_depth, F32, "dpos_depth"), int(accumulate), _stream()),
                           "enh_rq_embed_seq_backward"), unit="byte")
+
+
+# ------------------------------------------------------------------------------------------------
+# stage-2 RQTransformer sampling (csrc/rq_decode.hip): a step's input row from the codes on the device, the decode attention over a short cache
+# ------------------------------------------------------------------------------------------------
+def rq_embed_step(table, ids, pos_row, out):
+    """out[b] = (((e_0 + e_1) + ...) + e_{n-1}) + pos_row, e_j = table[ids[b, j]]: ids an int64 device view [B, n], 1 <= n <= 8, whose rows are
+    contiguous (any row stride, e.g. codes[:, t - 1, :] or codes[:, t, :d] of the sampler's [B, T, D] codes); table [V,C], pos_row [C], out [B,C] f32"""
+    B, C = out.shape
+    if not ids.is_cuda or ids.dtype != I64 or ids.dim() != 2 or ids.shape[0] != B:
+        raise RuntimeError("rq_embed_step: ids must be a 2-D int64 tensor on the device, one row of n ids per output row")
+    n = ids.shape[1]
+    if n > 1 and ids.stride(1) != 1:
+        raise RuntimeError("rq_embed_step: the n ids of a row must be contiguous")
+    stride = ids.stride(0) if B > 1 else n
+    if table.shape[1] != C or pos_row.numel() != C:
+        raise RuntimeError(f"rq_embed_step: table {tuple(table.shape)}, pos_row {tuple(pos_row.shape)} do not fit out {tuple(out.shape)}")
+    _check(lib().enh_rq_embed_step(_p(table, F32, "table"), ctypes.c_void_p(ids.data_ptr()), int(stride), n, _p(pos_row, F32, "pos_row"), B, C,
+                                   table.shape[0], _p(out, F32, "out"), _stream()), "enh_rq_embed_step")
+
+
+def short_decode_attention(qkv, k_cache, v_cache, t: int, out):
+    """decode_attention for caches [B,H,Tmax <= 8,hs] (the depth transformer's): the same arguments and arithmetic contract, eight lanes per
+    (row, head) pair, no workspace (enh_short_decode_attention)"""
+    B, H, Tmax, hs = k_cache.shape
+    if tuple(v_cache.shape) != (B, H, Tmax, hs) or tuple(qkv.shape) != (B, 3 * H * hs) or tuple(out.shape) != (B, H * hs):
+        raise RuntimeError(f"short_decode_attention: qkv {tuple(qkv.shape)} caches {tuple(k_cache.shape)} {tuple(v_cache.shape)} out {tuple(out.shape)} do not fit")
+    dt = qkv.dtype
+    if dt not in _DT_OF:
+        raise RuntimeError(f"short_decode_attention: dtype must be bf16, fp16 or f32, got {dt}")
+    _timed(None, 2.0 * qkv.element_size() * B * H * (int(t) + 1) * hs,
+           lambda: _check(lib().enh_short_decode_attention(_p(qkv, dt, "qkv"), _p(k_cache, dt, "k_cache"), _p(v_cache, dt, "v_cache"), B, H, hs, Tmax, int(t),
+                                                           _p(out, dt, "out"), _DT_OF[dt], _stream()), "enh_short_decode_attention"), unit="byte")

@@ -12,11 +12,13 @@ copies, the input checks, the chunked teacher-forced driver, the limits) is prio
   * `forward_backward` is that forward with its activations kept per layer, then a hand-written backward (§3.7; `_block_rows_backward`): weight
     gradients accumulate in f32 into one flat buffer that every `p.grad` is a view into.  16-bit operand formats only.
 
-`RQTransformer` (reference layers.py:306-547), the prior over a residual quantizer's [B, T, D] codes: `forward` (§3.9) and `forward_backward`
-(§3.10).  Its spatial and depth transformers are stacks of the same Blocks; the embedding stage, ln_spatial into slot 0 of the depth sequences and
-the attention over B T sequences of D <= 8 slots are csrc/rq_prefill.hip, their backward csrc/rq_backward.hip.
+`RQTransformer` (reference layers.py:306-547), the prior over a residual quantizer's [B, T, D] codes: `forward` (§3.9), `forward_backward`
+(§3.10) and `sample` (§3.11).  Its spatial and depth transformers are stacks of the same Blocks; the embedding stage, ln_spatial into slot 0 of the
+depth sequences and the attention over B T sequences of D <= 8 slots are csrc/rq_prefill.hip, their backward csrc/rq_backward.hip.  `sample` is the
+spatial / depth decode loop: both stacks run GPT's decode launches (prior.py `_block_step`), the spatial one under a cache of T slots, the depth
+one under a cache of D slots; a step's input row and the attention over the short cache are csrc/rq_decode.hip.
 
-Left out: RQTransformer's sampling, an exact-f32 backward, more than one condition token, HIP-graph capture, relu^2 /
+Left out: an exact-f32 backward, more than one condition token, HIP-graph capture, relu^2 /
 LayerNorm fused into GEMM epilogues."""
 import os
 from typing import Optional, Tuple
@@ -25,11 +27,12 @@ import torch
 import torch.nn as nn
 
 from .prior import (FORWARD_HIDDEN_CAP, MAX_BATCH, MAX_EMBED, MAX_HEAD, MAX_TOKENS, MAX_VOCAB, OPERAND_DTYPE, Prior,  # noqa: F401  (re-exported)
-                    _block_rows, _block_rows_backward, _grad_linears, _row_linear)
+                    _block_rows, _block_rows_backward, _block_step, _grad_linears, _row_linear)
 
 BACKWARD_SAVED_CAP = 16 << 30  # bytes of forward_backward()'s saved activations: shipped size 24 x 172,096 B per token, 4 sequences of 1024 per chunk
 MAX_DEPTH = 8           # enh_rq_embed_seq, enh_short_causal_attention_forward: the stage-1 residual quantizer's cap on num_quantizers
 CODE_SUMS = ("depth", "channels")
+SLOT0_LNS = ("once", "twice")     # RQTransformer.sample: how often ln_depth is applied to depth slot 0
 
 
 class MultiHeadSelfAttention(nn.Module):
@@ -266,13 +269,7 @@ class GPT(Prior):
         else:
             _C.gpt_embed(self.tok_emb_code.weight.detach(), ids, self.pos_emb_code.detach()[0, t - 1], x)
         for blk, W, (kc, vc) in zip(self.blocks, st["ops"]["layers"], st["caches"]):
-            _C.row_ln_scale(x, blk.ln1.weight, blk.ln1.bias, a, colscale=W["time_mix"], eps=blk.ln1.eps)
-            linear(a, W["wqkv"], qkv, bias=W["bqkv"])
-            _C.decode_attention(qkv, kc, vc, t, att)
-            linear(att, W["wproj"], x2, bias=blk.attn.proj.bias, res=x)
-            _C.row_ln_scale(x2, blk.ln2.weight, blk.ln2.bias, a, eps=blk.ln2.eps)
-            linear(a, W["w0"], hid, bias=blk.mlp.p0.bias, relu_sq=True)
-            linear(hid, W["w1"], x, bias=blk.mlp.p1.bias, res=x2)
+            _block_step(blk, W, linear, lambda q, o: _C.decode_attention(q, kc, vc, t, o), x, x2, a, qkv, att, hid)
         _C.row_ln_scale(x, self.layer_norm.weight, self.layer_norm.bias, a, eps=self.layer_norm.eps)
         linear(a, st["ops"]["head"], st["logits"])
 
@@ -281,7 +278,7 @@ class RQTransformer(Prior):
     """reference layers.py:306-395: a spatial transformer over the T positions of an image, whose input at a position is built from the D residual
     codes of the position before it, and a depth transformer over the D slots of every position: slot 0 is ln_spatial of the spatial output, slot
     d >= 1 is built from codes 0 .. d - 1 of the position; logits [B T, D, V].  The reference's constructor arguments, parameter names, shapes and
-    init.  Built here: the teacher-forced forward, the validation loss and forward_backward (training: engine/optim.py GPTAdam).  Not built: sampling.
+    init.  Built here: the teacher-forced forward, the validation loss, forward_backward (training: engine/optim.py GPTAdam) and sample.
 
     The code-sum quirk.  The reference's forward computes `codes.cumsum(-1)` on the [B, T, D, C] embeddings: a running sum along the embedding
     CHANNELS, not along depth.  Its own sampler (sample_spatial_step / sample_depth_step: `codes.sum(1)`) and the RQ-VAE formulation sum over
@@ -525,3 +522,124 @@ class RQTransformer(Prior):
                                      self.tok_emb_code.weight.grad, self.pos_emb_code.grad.view(-1, C), self.pos_emb_depth.grad.view(-1, C), accumulate)
         else:
             self._embed_channels_backward(codes, conds, gs, g, accumulate)
+
+    # ---- sampling -------------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
+               use_fp16: bool = True, *, seed: Optional[int] = None, forced_codes: Optional[torch.Tensor] = None, return_logits: bool = True,
+               call: int = 0, row_offset: int = 0, slot0_ln: str = "once") -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+        """reference layers.py:397-547 (sample, sample_spatial_step, sample_depth_step) with one condition token: returns (logits [B T, D, V] f32
+        after the temperature and the top-k mask, codes [B, T, D] int64).  GPT.sample's contract: the loop is restated per
+        step, one row per batch element.  Per position t the spatial Blocks run under a cache of T slots on the input row
+        tok_emb_cond[cond] + pos_emb_cond[0] (t == 0) or sum_j tok_emb_code[code[b, t - 1, j]] + pos_emb_code[t - 1], and ln_spatial gives the hidden
+        row; then D depth steps under a cache of D slots whose slot d is overwritten at every position: the input row is the hidden row (d == 0)
+        or sum_{j < d} tok_emb_code[code[b, t, j]] + pos_emb_depth[d - 1]; ln_depth, the head, the filter and the draw of code[b, t, d].
+
+        Two contracts.  Under the cache every Block of BOTH transformers sees one row, where `time_shift(x)` is all zeros and the mix is
+        ln1(x) * time_mix.  That is NOT what the teacher-forced `forward` computes on the same codes (there the shifted term is the previous row's
+        ln1): the sampler's logits differ from forward's, as GPT's do, and each has its golden (tests/golden/rq_sample_<case>.npz, rq_fwd_<case>.npz).
+
+        The slot-0 quirk.  The reference's sample_depth_step applies ln_depth inside its `codes is None` branch and again in the common line behind
+        it: depth slot 0 is normalised twice, slots d >= 1 once; the teacher-forced forward (so training) normalises every slot once.  Keyword
+        `slot0_ln` selects "once" (default: what the trained model computes) or "twice" (the reference's sampler line for line: a parity instrument
+        whose golden is the reference's own sample loop; one more enh_row_ln_scale launch at d == 0, nothing else differs).
+
+        The sampler sums the code embeddings over depth: a module built with code_sum="channels" is refused (the reference's sampler has no such form).
+
+        use_fp16=True runs the 16-bit operand format of ENH_PRECISION with f32 accumulation; False the exact mode (f32 caches, enh_skinny_gemm_f32,
+        f32 row kernels).  The draw is GPT.sample's: one uniform per (seed, call, step = t D + d, row_offset + row); seed=None draws one from torch's
+        generator.  forced_codes [B, T, D] are fed forward instead of the draws (codes are still drawn and returned).  Batches above 64 rows run in
+        chunks of 64 rows; a chunk equals a separate call with its `row_offset`.  Nothing in the loop reads a device value on the host.  The depth
+        transformer's attention is enh_short_decode_attention; ENH_RQ_DEPTH_DECODE=cache runs enh_decode_attention at Tmax = D instead (A/B only).
+        Device tensors only.  Side effect: a module whose parameters are not on the device of `conds` is moved there."""
+        if not (torch.is_tensor(conds) and conds.is_cuda):
+            raise NotImplementedError("RQTransformer.sample: sampling runs on a ROCm device only: conds must be a device tensor (the spatial / depth "
+                                      "decode loop is HIP kernels: there is no CPU path)")
+        if slot0_ln not in SLOT0_LNS:
+            raise ValueError(f"RQTransformer.sample: slot0_ln must be one of {SLOT0_LNS}, got {slot0_ln!r}")
+        if self.code_sum != "depth":
+            raise ValueError(f"RQTransformer.sample: this module was built with code_sum={self.code_sum!r}, but the sampler sums the code embeddings over "
+                             "depth (the reference's sample_spatial_step / sample_depth_step have no other form): build it with code_sum=\"depth\"")
+        depth_decode = os.environ.get("ENH_RQ_DEPTH_DECODE", "short")
+        if depth_decode not in ("short", "cache"):
+            raise ValueError(f"RQTransformer.sample: ENH_RQ_DEPTH_DECODE must be 'short' or 'cache', got {depth_decode!r}")
+        dev = conds.device
+        conds = self._on_device_conds(conds, conds.shape[0], "RQTransformer.sample")
+        B, T, D, V = conds.shape[0], self.img_num_tokens, self.depth_num_tokens, self.vocab_img_size
+        if top_k is not None and not 1 <= int(top_k) <= V:
+            raise ValueError(f"RQTransformer.sample: top_k must be in [1, {V}], got {top_k}")
+        if forced_codes is not None:
+            if forced_codes.numel() != B * T * D:
+                raise ValueError(f"RQTransformer.sample: forced_codes must be [B = {B}, img_num_tokens = {T}, depth_num_tokens = {D}], got "
+                                 f"{tuple(forced_codes.shape)}")
+            forced_codes = forced_codes.to(device=dev, dtype=torch.int64).reshape(B, T, D).contiguous()
+            if int(forced_codes.min()) < 0 or int(forced_codes.max()) >= V:
+                raise ValueError(f"RQTransformer.sample: forced_codes outside [0, {V})")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        dt = self._operand_dtype(use_fp16, "RQTransformer.sample")
+        codes = torch.empty(B, T, D, dtype=torch.int64, device=dev)
+        logits = torch.empty(B * T, D, V, dtype=torch.float32, device=dev) if return_logits else None
+        for s in range(0, B, MAX_BATCH):
+            e = min(s + MAX_BATCH, B)
+            self._sample_rows(conds[s:e], codes[s:e], None if logits is None else logits.view(B, T, D, V)[s:e],
+                              None if forced_codes is None else forced_codes[s:e], dt, top_k, top_p, float(softmax_temperature), seed, call,
+                              row_offset + s, slot0_ln == "twice", depth_decode == "cache")
+        return logits, codes
+
+    def _decode_state(self, b: int, dt: torch.dtype, dev) -> dict:
+        """the buffers of one chunk of b <= 64 rows: the spatial and the depth residual stream, activations, the step's logits, every spatial
+        layer's k / v cache [b, Hs, T, C / Hs] and every depth layer's [b, Hd, D, C / Hd]"""
+        f32, C, T, D = torch.float32, self.embed_dim, self.img_num_tokens, self.depth_num_tokens
+        Hs, Hd = self.spatial_n_heads, self.depth_n_heads
+        e = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=dev)
+        return dict(dt=dt, b=b, xs=e(b, C, dtype=f32), xd=e(b, C, dtype=f32), x2=e(b, C, dtype=f32), a=e(b, C), qkv=e(b, 3 * C), att=e(b, C),
+                    hid=e(b, 4 * C), logits=e(b, self.vocab_img_size, dtype=f32),
+                    spatial=[(e(b, Hs, T, C // Hs), e(b, Hs, T, C // Hs)) for _ in self.spatial_transformer],
+                    depth=[(e(b, Hd, D, C // Hd), e(b, Hd, D, C // Hd)) for _ in self.depth_transformer], ops=self._operand_copies(dt))
+
+    def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0, ln_twice: bool, depth_cache: bool):
+        """one chunk of b <= 64 rows: codes [b, T, D] (a view the draws are written into), logits [b, T, D, V] (a view) or None"""
+        from ... import _C
+        T, D = self.img_num_tokens, self.depth_num_tokens
+        st = self._decode_state(conds.shape[0], dt, conds.device)
+        feed = codes if forced is None else forced
+        for t in range(T):
+            self._spatial_step(st, t, conds if t == 0 else feed[:, t - 1, :])
+            for d in range(D):
+                self._depth_step(st, t, d, None if d == 0 else feed[:, t, :d], ln_twice, depth_cache)
+                _C.sample_logits(st["logits"], codes[:, t, d], temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, call=call, step=t * D + d,
+                                 row0=row0, logits_out=None if logits is None else logits[:, t, d, :])
+
+    def _spatial_step(self, st: dict, t: int, ids: torch.Tensor) -> None:
+        """position t of the spatial transformer, one row per batch element: ids (int64, on the device: the condition [b] at t == 0, else the D
+        codes [b, D] of position t - 1) -> ln_spatial of the stack's output in st["xd"] [b, C] f32, the input row of depth slot 0"""
+        from ... import _C
+        x, x2, a, qkv, att, hid = st["xs"], st["x2"], st["a"], st["qkv"], st["att"], st["hid"]
+        linear = _C.skinny_gemm_f32 if st["dt"] == torch.float32 else _C.skinny_gemm
+        if t == 0:
+            _C.gpt_embed(self.tok_emb_cond.weight.detach(), ids, self.pos_emb_cond.detach()[0, 0], x)
+        else:
+            _C.rq_embed_step(self.tok_emb_code.weight.detach(), ids, self.pos_emb_code.detach()[0, t - 1], x)
+        for blk, W, (kc, vc) in zip(self.spatial_transformer, st["ops"]["spatial"], st["spatial"]):
+            _block_step(blk, W, linear, lambda q, o: _C.decode_attention(q, kc, vc, t, o), x, x2, a, qkv, att, hid)
+        _C.row_ln_scale(x, self.ln_spatial.weight, self.ln_spatial.bias, st["xd"], eps=self.ln_spatial.eps)
+
+    def _depth_step(self, st: dict, t: int, d: int, ids: Optional[torch.Tensor], ln_twice: bool, depth_cache: bool) -> None:
+        """slot d of position t of the depth transformer: the input row is st["xd"] as _spatial_step left it (d == 0), else built from ids
+        (int64 [b, d] on the device: codes 0 .. d - 1 of the position) -> st["logits"] [b, V] f32.  Slot d of the depth caches is overwritten
+        and slots > d are never read: the caches need no reset between positions."""
+        from ... import _C
+        x, x2, a, qkv, att, hid = st["xd"], st["x2"], st["a"], st["qkv"], st["att"], st["hid"]
+        linear = _C.skinny_gemm_f32 if st["dt"] == torch.float32 else _C.skinny_gemm
+        attend = _C.decode_attention if depth_cache else _C.short_decode_attention
+        if d > 0:
+            _C.rq_embed_step(self.tok_emb_code.weight.detach(), ids, self.pos_emb_depth.detach()[0, d - 1], x)
+        for blk, W, (kc, vc) in zip(self.depth_transformer, st["ops"]["depth"], st["depth"]):
+            _block_step(blk, W, linear, lambda q, o: attend(q, kc, vc, d, o), x, x2, a, qkv, att, hid)
+        ln = self.ln_depth
+        if d == 0 and ln_twice:      # the reference's sampler: ln_depth in the `codes is None` branch, then the common line
+            _C.row_ln_scale(x, ln.weight, ln.bias, x2, eps=ln.eps)
+            x = x2
+        _C.row_ln_scale(x, ln.weight, ln.bias, a, eps=ln.eps)
+        linear(a, st["ops"]["head"], st["logits"])

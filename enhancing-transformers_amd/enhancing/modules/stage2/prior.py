@@ -1,6 +1,6 @@
 """What the stage-2 priors of layers.py (GPT, RQTransformer) and their optimizer (engine/optim.py GPTAdam) share, each stated once: the limits of
 the kernels, the launches of one Block over whole sequences forward (`_block_rows`) and backward (`_block_rows_backward`) with the products between
-them (`_row_linear`, `_grad_linears`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`), the flat parameter layout
+them (`_row_linear`, `_grad_linears`), the launches of one Block in a cached sampling step (`_block_step`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`), the flat parameter layout
 (`flat_layout`), a layer's slice of the optimizer's operand arena (`ARENA_LAYER`), and `Prior`, the base class: init, input checks, the
 version-keyed operand cache, the one-chunk-at-a-time buffer cache and the two teacher-forced drivers (forward: chunks, cross-entropy rows, mean; forward_backward: chunks under the
 saved-activation cap, the loss scale, gradients set in the first chunk and added to in the later ones)."""
@@ -122,6 +122,20 @@ def _block_rows(blk, W, linear, dt, S: int, attention, x, x_out, a, a2, qkv, att
         linear(a2, W["w0"], hid32, bias=blk.mlp.p0.bias)
         _C.relu_sq(hid, hid32)
         linear(hid, W["w1"], x_out, bias=blk.mlp.p1.bias, res=x2)
+
+
+def _block_step(blk, W, linear, attention, x, x2, a, qkv, att, hid) -> None:
+    """the launches of one Block in a cached sampling step, one row per batch element: x -> x (f32, in place).  The Block sees T == 1, so
+    time_shift is all zeros and the mix is ln1(x) * time_mix (DESIGN.md §3.5).  linear is enh_skinny_gemm_h16 or, in the exact mode, its f32 form;
+    attention(qkv, att) appends the step's k / v to the layer's cache and attends over it."""
+    from ... import _C
+    _C.row_ln_scale(x, blk.ln1.weight, blk.ln1.bias, a, colscale=W["time_mix"], eps=blk.ln1.eps)
+    linear(a, W["wqkv"], qkv, bias=W["bqkv"])
+    attention(qkv, att)
+    linear(att, W["wproj"], x2, bias=blk.attn.proj.bias, res=x)
+    _C.row_ln_scale(x2, blk.ln2.weight, blk.ln2.bias, a, eps=blk.ln2.eps)
+    linear(a, W["w0"], hid, bias=blk.mlp.p0.bias, relu_sq=True)
+    linear(hid, W["w1"], x, bias=blk.mlp.p1.bias, res=x2)
 
 
 def _block_rows_backward(blk, W, wgrad, dgrad, accumulate: bool, S: int, attention_backward, sv, st, g, g2, d32, g16, dh16, dqkv, datt, hid32) -> None:

@@ -4,8 +4,8 @@ RQTransformer over a residual stage 1's codes [B, N, D]); `sample` draws codes o
 gradient of every parameter of the prior on the device (forward_backward); `configure_optimizers` returns the reference's Adam as one device launch
 (engine/optim.py GPTAdam) and `training_step` runs the loss-scaled forward + backward against it (Trainer.fit drives both, on one GPU).
 
-With an `RQTransformer`, `sample` raises NotImplementedError (RQ sampling is not built), and training exists on a ROCm device only: a prior that
-is elsewhere is refused before the tokenizer runs."""
+With an `RQTransformer`, sampling and training exist on a ROCm device only: `sample` with conditions that are not on the device raises
+NotImplementedError, and a prior that is elsewhere is refused by the training entries before the tokenizer runs."""
 from typing import List, Optional, Tuple
 
 import torch
@@ -56,8 +56,9 @@ class CondTransformer(nn.Module):
     @torch.no_grad()
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
                use_fp16: bool = True, **kw) -> torch.Tensor:
-        """reference transformer.py:78-95.  **kw goes to GPT.sample (seed, forced_codes, ...).  The drawn codes are kept in `last_codes`."""
-        self._gpt_only("sample", "RQ sampling (the spatial / depth decode loop)")
+        """reference transformer.py:78-95, for both priors: GPT draws codes [B, T], RQTransformer [B, T, D] (for a residual tokenizer), and
+        `code_shape` is applied to them as the reference does (e.g. [32, 32] or [32, 32, 4]).  **kw goes to the prior's sample (seed, forced_codes,
+        slot0_ln, ...).  The drawn codes are kept in `last_codes`.  An RQ prior that is off the device refuses (sampling runs on a ROCm device only)."""
         conds = conds.view(conds.shape[0], -1)
         kw.setdefault("return_logits", False)
         _, codes = self.transformer.sample(conds=conds, top_k=top_k, top_p=top_p, softmax_temperature=softmax_temperature, use_fp16=use_fp16, **kw)
@@ -74,11 +75,6 @@ class CondTransformer(nn.Module):
         if x.dtype == torch.double:
             x = x.float()
         return x.contiguous()
-
-    def _gpt_only(self, what: str, missing: str) -> None:
-        if isinstance(getattr(self, "transformer", None), RQTransformer):
-            raise NotImplementedError(f"CondTransformer.{what} with an RQTransformer: {missing} is not built (the teacher-forced forward, the "
-                                      "validation loss and training are)")
 
     def _rq_on_device(self, what: str) -> None:
         """with an RQTransformer: refuses a prior that is not on a ROCm device, before anything is tokenized (the batch itself may come from the

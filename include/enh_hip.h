@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 28  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 29  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -668,6 +668,20 @@ int enh_ln_rows_strided(const float* x, const float* w, const float* b, int64_t 
  * D a multiple of 64 up to 384 (anything else: ENH_E_SHAPE).  The arithmetic contract of enh_causal_attention_forward (f32 scores, exp(s - max)
  * rounded to the format before P V, one rounding of out); eight lanes own a (sequence, head) pair and a workgroup 32 pairs, nothing staged in LDS. */
 int enh_short_causal_attention_forward(const enh_h16* qkv, int NSEQ, int L, int H, int D, float scale, enh_h16* out, float* lse, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 RQTransformer, sampling (csrc/rq_decode.hip; layers.py:397-547 with one condition token): what the spatial / depth decode loop needs
+ * beyond the GPT's decode kernels above.  No float atomics.
+ * ------------------------------------------------------------------------------------------------ */
+/* out[b] = (((e_0 + e_1) + ...) + e_{n-1}) + pos_row with e_j = table[ids[b * id_stride + j]], b < B, 1 <= n <= 8 (else ENH_E_SHAPE); table [V, C]
+ * f32, pos_row [C] f32, C % 4 == 0.  ids: int64 on the device (a strided view of the sampler's [B, T, D] codes: id_stride >= n).  Sums in ascending
+ * depth, one rounding per addition: the bits of enh_rq_embed_seq's row for the same codes (layers.py:502,535).  Ids outside the table are clamped. */
+int enh_rq_embed_step(const float* table, const int64_t* ids, int64_t id_stride, int n, const float* pos_row, int B, int C, int V, float* out,
+                      void* stream);
+/* enh_decode_attention (its arguments, its arithmetic contract: f32 scores, f32 softmax numerators, slot t taken from qkv and appended, slots > t
+ * neither read nor written) for a cache of Tmax <= 8 slots (else ENH_E_SHAPE): eight lanes own a (row, head) pair and a workgroup 32 pairs,
+ * nothing staged in LDS, no workspace.  dtype ENH_DT_BF16 | ENH_DT_F16 | ENH_DT_F32; hs a multiple of 64 up to 384. */
+int enh_short_decode_attention(const void* qkv, void* k_cache, void* v_cache, int B, int H, int hs, int Tmax, int t, void* out, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stage-2 GPT, backward of the teacher-forced forward (csrc/gpt_attn_bwd.hip: the attention, csrc/gpt_rows.hip: the row kernels).  The gradient

@@ -1,0 +1,193 @@
+"""Times the stage-2 RQTransformer's sampling loop at the shipped size (the transformer block of configs/imagenet_rqtransformer_rqvae_base.yaml:
+C = 1536, 24 spatial and 4 depth layers, 12 heads of 128 in both, T = 1024, D = 4, V = 8192; random weights) and writes profiles/rq_sample.txt:
+python tools/rq_sample_bench.py [--out FILE] [--spatial_layers N]
+
+1. The depth transformer's decode attention alone at the shipped shape (batch x 12 heads of 128, a cache of D = 4 slots, the steps d = 0 .. 3 in
+   turn), batch 1 and 4, fp16: enh_short_decode_attention against enh_decode_attention at Tmax = D in the same run, the outputs compared.
+2. One position of the loop (fp16 operands), batch 1 and 4, at several fills of the spatial cache: the spatial step, the D depth steps with their
+   draws (with either depth attention), and the same cached position in plain fp16 torch (torch.addmm, F.layer_norm, softmax, torch.multinomial)
+   on the model's own operand copies; launches per position, the GEMM weight bytes a position must read over its time against the rate of a plain
+   copy, and the seconds per image extrapolated from the fills.
+Timing: HIP events around a window of back-to-back calls; median, minimum and maximum of 7 windows that alternate between the paths, after a warm-up
+of every path.  Not 1024 positions: a few positions per fill."""
+import argparse
+import math
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "enhancing-transformers_amd"))
+from enhancing import _C  # noqa: E402
+from enhancing.modules.stage2.layers import RQTransformer  # noqa: E402
+from enhancing.utils.general import get_config_from_file  # noqa: E402
+
+COPY_TBS = 6.29
+
+
+def timed(fn, inner):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for i in range(inner):
+        fn(i)
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / inner
+
+
+def alternate(fns, inner, reps=7):
+    """[(min, median, max) ms per call] of every function of `fns`: `reps` rounds of one window of `inner` back-to-back calls per function, after
+    a warm-up of each"""
+    for fn in fns:
+        fn(0)
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for v, fn in zip(ts, fns):
+            v.append(timed(fn, inner))
+    return [(min(v), statistics.median(v), max(v)) for v in ts]
+
+
+class TorchPosition:
+    """the yardstick: the same cached position (one spatial step, D depth steps, D draws) in plain fp16 torch on the operand copies of the model"""
+
+    def __init__(self, m, b):
+        self.m, self.b = m, b
+        C, T, D = m.embed_dim, m.img_num_tokens, m.depth_num_tokens
+        self.ops = m._operand_copies(torch.float16)
+        h = lambda p: None if p is None else p.detach().half()
+        self.small = {id(k): (h(k.ln1.weight), h(k.ln1.bias), h(k.ln2.weight), h(k.ln2.bias), h(k.attn.proj.bias), h(k.mlp.p0.bias), h(k.mlp.p1.bias))
+                      for k in list(m.spatial_transformer) + list(m.depth_transformer)}
+        self.lns, self.lnd = (h(m.ln_spatial.weight), h(m.ln_spatial.bias)), (h(m.ln_depth.weight), h(m.ln_depth.bias))
+        self.emb, self.pos, self.pos_d = h(m.tok_emb_code.weight), h(m.pos_emb_code)[0], h(m.pos_emb_depth)[0]
+        z = lambda H, n: torch.zeros(b * H, n, C // H, dtype=torch.float16, device="cuda")
+        self.sp = [(z(m.spatial_n_heads, T), z(m.spatial_n_heads, T)) for _ in m.spatial_transformer]
+        self.dp = [(z(m.depth_n_heads, D), z(m.depth_n_heads, D)) for _ in m.depth_transformer]
+
+    def blocks(self, x, stack, ops, H, caches, t):
+        b, C = x.shape
+        hs = C // H
+        for blk, W, (kc, vc) in zip(stack, ops, caches):
+            w1, b1, w2, b2, bp, b0, bq = self.small[id(blk)]
+            a = F.layer_norm(x, (C,), w1, b1) * W["time_mix"].half()
+            qkv = torch.addmm(W["bqkv"].half(), a, W["wqkv"].t())
+            q, k, v = (z.reshape(b * H, 1, hs) for z in qkv.split(C, dim=1))
+            kc[:, t:t + 1], vc[:, t:t + 1] = k, v
+            att = torch.softmax(torch.bmm(q, kc[:, :t + 1].transpose(1, 2)) * (1.0 / math.sqrt(hs)), dim=-1)
+            x = x + torch.addmm(bp, torch.bmm(att, vc[:, :t + 1]).reshape(b, C), W["wproj"].t())
+            hdn = torch.square(torch.relu(torch.addmm(b0, F.layer_norm(x, (C,), w2, b2), W["w0"].t())))
+            x = x + torch.addmm(bq, hdn, W["w1"].t())
+        return x
+
+    @torch.no_grad()
+    def __call__(self, t, codes):
+        """position t >= 1 given codes [b, T, D]: draws its D codes"""
+        m = self.m
+        C, D = m.embed_dim, m.depth_num_tokens
+        x = self.emb[codes[:, t - 1]].sum(1) + self.pos[t - 1]
+        hidden = F.layer_norm(self.blocks(x, m.spatial_transformer, self.ops["spatial"], m.spatial_n_heads, self.sp, t), (C,), *self.lns)
+        out = []
+        for d in range(D):
+            x = hidden if d == 0 else self.emb[codes[:, t, :d]].sum(1) + self.pos_d[d - 1]
+            x = self.blocks(x, m.depth_transformer, self.ops["depth"], m.depth_n_heads, self.dp, d)
+            logits = torch.matmul(F.layer_norm(x, (C,), *self.lnd), self.ops["head"].t()).float()
+            out.append(torch.multinomial(torch.softmax(logits, -1), 1))
+        return out
+
+
+def launches_per_position(b, C, V, D, Ls, Ld, t):
+    """kernel launches of one position at spatial slot t, from the code: a Block step is 7 library calls (2 LayerNorms, 4 products, the attention);
+    a product whose plan splits K adds its slab pass, the spatial attention its merge once the cache is cut into pieces (past 64 slots)"""
+    L = _C.lib()
+    split = lambda N, K: 1 + int(L.enh_skinny_gemm_workspace_bytes(b, N, K) > 0)
+    block = 2 + split(3 * C, C) + split(C, C) + split(4 * C, C) + split(C, 4 * C) + 1
+    spatial = 1 + Ls * (block + int(t + 1 > 64)) + 1
+    depth = (D - 1) + D * (Ld * block + 1 + split(V, C) + 1)
+    return spatial, depth
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rq_sample.txt"))
+    ap.add_argument("--spatial_layers", type=int, default=None)
+    args = ap.parse_args()
+    kw = dict(get_config_from_file(os.path.join(ROOT, "configs", "imagenet_rqtransformer_rqvae_base.yaml")).model.params.transformer.params)
+    if args.spatial_layers is not None:
+        kw["spatial_n_layers"] = args.spatial_layers
+    C, V, T, D = kw["embed_dim"], kw["vocab_img_size"], kw["img_num_tokens"], kw["depth_num_tokens"]
+    Hs, Hd, Ls, Ld = kw["spatial_n_heads"], kw["depth_n_heads"], kw["spatial_n_layers"], kw["depth_n_layers"]
+    dt = torch.float16
+    f3 = lambda v, k=1.0: f"{v[1] * k:.3f} [{v[0] * k:.3f} .. {v[2] * k:.3f}]"
+    f1 = lambda v: f"{v[1] * 1e3:.1f} [{v[0] * 1e3:.1f} .. {v[2] * 1e3:.1f}]"
+    lines = [f"stage-2 RQTransformer sampling on {torch.cuda.get_device_name(0)}: C={C} spatial layers={Ls} depth layers={Ld} heads={Hs} x {C // Hs} | "
+             f"{Hd} x {C // Hd} T={T} D={D} V={V}, fp16 operands",
+             "times: median [min .. max] of 7 alternating windows of back-to-back calls, after a warm-up of every path",
+             f"depth decode attention alone, batch x {Hd} heads of {C // Hd}, cache of {D} slots, steps d = 0 .. {D - 1} in turn: windows of 200 launches",
+             f"{'batch':>5} {'short us [min .. max]':>28} {'general us [min .. max]':>28} {'general/short':>13} {'spread-free':>11} {'max |diff|':>10}"]
+    all_faster = True
+    for b in (1, 4):
+        hs = C // Hd
+        qkv = torch.randn(b, 3 * C, device="cuda").to(dt)
+        ks, vs, kg, vg = (torch.zeros(b, Hd, D, hs, device="cuda", dtype=dt) for _ in range(4))
+        o_s, o_g = torch.empty(b, C, device="cuda", dtype=dt), torch.empty(b, C, device="cuda", dtype=dt)
+        s, g = alternate([lambda i: _C.short_decode_attention(qkv, ks, vs, i % D, o_s), lambda i: _C.decode_attention(qkv, kg, vg, i % D, o_g)], inner=200)
+        _C.short_decode_attention(qkv, ks, vs, D - 1, o_s)
+        _C.decode_attention(qkv, kg, vg, D - 1, o_g)
+        faster = s[2] < g[0]      # the slowest window of the new kernel against the fastest of the old one: beyond the spread of both
+        all_faster &= faster
+        lines.append(f"{b:>5} {f1(s):>28} {f1(g):>28} {g[1] / s[1]:>13.2f} {'yes' if faster else 'NO':>11} {(o_s.float() - o_g.float()).abs().max().item():>10.1e}")
+    lines.append(f"short kernel faster than the general kernel beyond the run-to-run spread at every point: {'yes' if all_faster else 'NO'}")
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        m = RQTransformer(**kw)
+        with torch.no_grad():
+            for p in (m.pos_emb_cond, m.pos_emb_code, m.pos_emb_depth):
+                p.normal_(0, 0.02)
+    wb_spatial, wb_depth = 12 * C * C * Ls * 2, D * (12 * C * C * Ld + V * C) * 2
+    lines += [f"one position, fp16 operands: windows of 10 positions; GEMM weights read per position {wb_spatial / 1e9:.3f} GB (spatial) + {wb_depth / 1e9:.3f} GB "
+              f"({D} depth steps with the head) = {(wb_spatial + wb_depth) / 1e9:.3f} GB; a plain copy reaches {COPY_TBS} TB/s",
+              f"(the depth stack and the head, {wb_depth / D / 1e6:.0f} MB, are re-read {D} times per position and fit the 256 MiB last-level cache: their rate can pass the HBM rate)",
+              f"{'batch':>5} {'slot':>5} {'spatial ms [min .. max]':>28} {'depth ms, short [min .. max]':>30} {'depth ms, general [min .. max]':>31} {'position ms':>11} "
+              f"{'torch ms [min .. max]':>28} {'torch/dev':>9} {'launches':>9} {'weights TB/s':>12} {'of copy':>8}"]
+    per_image = {}
+    for b in (1, 4):
+        st = m._decode_state(b, dt, "cuda")
+        codes = torch.randint(0, V, (b, T, D), device="cuda")
+        tp = TorchPosition(m, b)
+        pos_ms = []
+        for t in (1, 256, 512, T - 1):
+            def spatial(i):
+                m._spatial_step(st, t, codes[:, t - 1, :])
+
+            def depth(cache):
+                def run(i):
+                    for d in range(D):
+                        m._depth_step(st, t, d, None if d == 0 else codes[:, t, :d], False, cache)
+                        _C.sample_logits(st["logits"], codes[:, t, d], top_k=None, top_p=None, seed=1, step=t * D + d)
+                return run
+            sp, ds, dg, tr = alternate([spatial, depth(False), depth(True), lambda i: tp(t, codes)], inner=10)
+            n_sp, n_dp = launches_per_position(b, C, V, D, Ls, Ld, t)
+            pos = sp[1] + ds[1]
+            pos_ms.append(pos)
+            tbs = (wb_spatial + wb_depth) / (pos * 1e-3) / 1e12
+            lines.append(f"{b:>5} {t:>5} {f3(sp):>28} {f3(ds):>30} {f3(dg):>31} {pos:>11.3f} {f3(tr):>28} {tr[1] / pos:>9.2f} {n_sp + n_dp:>9} {tbs:>12.2f} "
+                         f"{100 * tbs / COPY_TBS:>7.1f}%")
+        per_image[b] = statistics.mean(pos_ms) * T / 1e3
+        del st, tp
+        torch.cuda.empty_cache()
+    n_sp, n_dp = launches_per_position(4, C, V, D, Ls, Ld, T - 1)
+    lines.append(f"launches per position at batch 4, slot {T - 1}: {n_sp} (spatial step) + {n_dp} ({D} depth steps with their draws) = {n_sp + n_dp}")
+    for b, s in per_image.items():
+        lines.append(f"extrapolated whole image, batch {b}: mean position time of the four fills x {T} positions = {s:.2f} s ({s / b:.2f} s per image)")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()

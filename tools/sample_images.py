@@ -1,8 +1,9 @@
 """Class-conditional image sampling with a stage-2 config:  python tools/sample_images.py -c configs/imagenet_gpt_vitvq_base.yaml --ckpt last.ckpt
 --classes 207 360 --top_k 100 --top_p 0.95 --temperature 1.0 --seed 0 --out samples.png
 
-Builds the config's CondTransformer (condition model, stage-1 tokenizer, GPT prior), loads `--ckpt` (a {"state_dict": ...} file; without it the
-config's own `path` entries or the random init are used), samples one image per class id on the device and writes them as one PNG grid."""
+Builds the config's CondTransformer (condition model, stage-1 tokenizer, and the prior: GPT, or RQTransformer over a residual tokenizer as in
+configs/imagenet_rqtransformer_rqvae_base.yaml), loads `--ckpt` (a {"state_dict": ...} file; without it the config's own `path` entries or the
+random init are used), samples one image per class id on the device and writes them as one PNG grid."""
 import argparse
 import os
 import sys
