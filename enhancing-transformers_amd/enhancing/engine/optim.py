@@ -24,53 +24,42 @@ class _GradClip:
         clip_norm = float(val) if by_norm else (float("inf") if self.track_grad_norm else None)
         return clip_norm, (float(val) if val is not None and not by_norm else None)
 
+    _clip_out = None      # (total_norm, clip coefficient) on the device, allocated by the first step that wants the norm
 
-class FusedAdamW(_GradClip):
-    def __init__(self, engine, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 1e-4) -> None:
-        self.engine = engine
-        self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
-        self.grad_scale = 1.0  # 1 / accumulate_grad_batches
+    def _clip_buf(self, clip, device):
+        if clip[0] is not None and self._clip_out is None:
+            import torch
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=device)
+        return self._clip_out
 
     @property
     def grad_norm(self):
-        """2-norm of the gradient the last step applied, before clipping (device f32 [1]; meaningful once a step ran with clipping by norm or tracking on)"""
-        return self.engine.grad_norm
-
-    def zero_grad(self, set_to_none: bool = False) -> None:
-        self.engine.store.zero_grad()
-
-    def step(self) -> None:
-        g = self.param_groups[0]
-        clip_norm, clip_value = self._clip_args()
-        self.engine.optimizer_step(g["lr"], g["betas"], g["eps"], g["weight_decay"], self.grad_scale, clip_norm=clip_norm, clip_value=clip_value)
-
-    def state_dict(self) -> dict:
-        s = self.engine.store
-        return dict(step=s.step_count, m=s.m.detach().cpu(), v=s.v.detach().cpu(), param_groups=self.param_groups)
-
-    def load_state_dict(self, sd: dict) -> None:
-        s = self.engine.store
-        s.step_count = int(sd["step"])
-        s.m.copy_(sd["m"]); s.v.copy_(sd["v"])
-        self.param_groups = sd["param_groups"]
+        """2-norm of the gradient the last step applied, before clipping (device f32 [1]; None until a step ran with clipping by norm or tracking on)"""
+        return None if self._clip_out is None else self._clip_out[:1]
 
 
 class LossScaler:
-    """torch.cuda.amp.GradScaler's state machine with every quantity on the device (the same three launches the fp16 engine uses: enh_nonfinite_flag,
-    enh_adamw_step's skip / unscale operands, enh_loss_scale_update), for a ParamStore whose backward runs through plain autograd — the discriminator's.
-    `enabled` is decided by the forward that builds the graph (fp16 operands in the loss networks: gradients of ~1e-5 would sit in fp16's subnormal range);
-    disabled it is the identity everywhere.  Initial scale ENH_LOSS_NET_SCALE (default 2^12: a gradient of 1 per logit, times the scale, has to fit fp16
-    itself — GradScaler's 2^16 would spend its first steps backing off), growth x2 after `interval` clean steps, x0.5 on an inf / nan (that step is skipped)."""
+    """torch.cuda.amp.GradScaler's state machine with every quantity on the device: the one scaler under the three optimizers (the fp16 engine's, the
+    discriminator's ParamStore, GPTAdam's), stepped by `scaled_step` below.  `enabled` False is the identity everywhere; the discriminator's is switched
+    by the forward that builds the graph (fp16 operands in the loss networks: gradients of ~1e-5 would sit in fp16's subnormal range).
+    Initial scale: the environment variable `env` names.  ENH_LOSS_SCALE (2^16, GradScaler's) for the engine and GPTAdam; ENH_LOSS_NET_SCALE (2^12) for
+    the loss networks: a gradient of 1 per logit, times the scale, has to fit fp16 itself, and 2^16 would spend its first steps backing off.  Growth x2
+    after ENH_LOSS_SCALE_INTERVAL (2000, GradScaler's; 0 = never) clean steps, x0.5 on an inf / nan (that step is skipped).
+    check=False scales but does not check (the engine's ENH_NONFINITE_CHECK=0): found_inf is None, no step is dropped and the scale never moves.
+    count_skipped: keep `skipped_steps`, a device count of the dropped steps (the engine's; read it with .item() outside the step)."""
+    DEFAULT_SCALE = dict(ENH_LOSS_SCALE=65536.0, ENH_LOSS_NET_SCALE=4096.0)
 
-    def __init__(self, device, init_scale: float = None, growth_interval: int = None) -> None:
+    def __init__(self, device, init_scale: float = None, growth_interval: int = None, env: str = "ENH_LOSS_NET_SCALE", enabled: bool = False,
+                 check: bool = True, count_skipped: bool = False) -> None:
         import os
         import torch
-        init_scale = float(os.environ.get("ENH_LOSS_NET_SCALE", 4096.0)) if init_scale is None else float(init_scale)
+        init_scale = float(os.environ.get(env, self.DEFAULT_SCALE[env])) if init_scale is None else float(init_scale)
         self.growth_interval = int(os.environ.get("ENH_LOSS_SCALE_INTERVAL", 2000)) if growth_interval is None else int(growth_interval)
         self.scale_t = torch.full((1,), init_scale, dtype=torch.float32, device=device)
         self.tracker = torch.zeros(1, dtype=torch.int32, device=device)
-        self.found_inf = torch.zeros(1, dtype=torch.float32, device=device)
-        self.enabled = False
+        self.found_inf = torch.zeros(1, dtype=torch.float32, device=device) if check else None      # written by the flag / norm pass, read by the Adam launch
+        self.skipped_steps = torch.zeros(1, dtype=torch.float32, device=device) if check and count_skipped else None
+        self.enabled = enabled
 
     def scale(self, t):
         return t * self.scale_t.view(()) if self.enabled else t
@@ -83,7 +72,81 @@ class LossScaler:
         return float(self.scale_t.item()) if self.enabled else 1.0
 
 
-class FlatAdamW(_GradClip):
+def scaled_step(g, grad_scale: float, clip, clip_out, scaler, adam, grads_unscaled: bool = False) -> None:
+    """The clipped, loss-scaled optimizer step all three optimizers take: GradScaler.step + GradScaler.update around the caller's Adam launch, with no
+    host read and no allocation, so a HIP graph can capture it.
+    g: the flat f32 gradient, already reduced; grad_scale: what the launch multiplies it by (1 / accumulation window / world size).
+    clip: _GradClip._clip_args()'s (clip_norm, clip_value): clip_norm = inf measures the norm and clips nothing, clip_value None / 0 is off.
+    clip_out: the caller's (total_norm, coefficient) f32 [2]; touched only when clip_norm is not None.
+    scaler: a LossScaler; None or a disabled one: no scale, no check.  grads_unscaled: the scale was already divided out of g (Stage1Engine.unscale_grads):
+    neither launch gets the loss_scale operand, the flag and the update still run.
+    adam: the caller's Adam launch; called once, with exactly those of skip_flag / loss_scale / clip_coef / clip_value that apply (none: the plain call).
+    Under a scaler that checks: one pass over g sets found_inf (the norm pass when there is one: the sum of squares and the flag ride on the same loads),
+    the Adam launch reads it and writes nothing when it is set, enh_loss_scale_update halves / doubles the scale on the device."""
+    from .. import _C
+    clip_norm, clip_value = clip
+    sc = scaler if scaler is not None and scaler.enabled else None
+    norm_kw, kw = {}, {}      # the scaler's operands of the norm pass; the scaler's and the clip operands of the Adam launch
+    flag = sc.found_inf if sc is not None else None
+    if flag is not None:
+        flag.zero_()
+        norm_kw["found_inf"] = kw["skip_flag"] = flag
+    if sc is not None and not grads_unscaled:
+        norm_kw["loss_scale"] = kw["loss_scale"] = sc.scale_t
+    if clip_norm is not None:
+        _C.grad_clip_coef(g, clip_norm, grad_scale, clip_out, **norm_kw)
+        if clip_norm != float("inf"):
+            kw["clip_coef"] = clip_out[1:]
+    elif flag is not None:
+        _C.nonfinite_flag(g, flag)
+    if clip_value:
+        kw["clip_value"] = float(clip_value)
+    adam(**kw)
+    if flag is not None:
+        _C.loss_scale_update(sc.scale_t, flag, sc.tracker, 2.0, 0.5, sc.growth_interval)
+        if sc.skipped_steps is not None:      # (the update and the Adam kernels only read the flag)
+            sc.skipped_steps.add_(flag)
+
+
+class _StoreAdamW(_GradClip):
+    """what FusedAdamW and FlatAdamW share: AdamW's state lives in `self.store` (a ParamStore: step_count, m, v)"""
+
+    def zero_grad(self, set_to_none: bool = False) -> None:
+        self.store.zero_grad()
+
+    def state_dict(self) -> dict:
+        s = self.store
+        return dict(step=s.step_count, m=s.m.detach().cpu(), v=s.v.detach().cpu(), param_groups=self.param_groups)
+
+    def load_state_dict(self, sd: dict) -> None:
+        s = self.store
+        s.step_count = int(sd["step"])
+        s.m.copy_(sd["m"]); s.v.copy_(sd["v"])
+        self.param_groups = sd["param_groups"]
+
+
+class FusedAdamW(_StoreAdamW):
+    def __init__(self, engine, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 1e-4) -> None:
+        self.engine = engine
+        self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
+        self.grad_scale = 1.0  # 1 / accumulate_grad_batches
+
+    @property
+    def store(self):
+        return self.engine.store
+
+    @property
+    def grad_norm(self):
+        """2-norm of the gradient the last step applied, before clipping (device f32 [1]; meaningful once a step ran with clipping by norm or tracking on)"""
+        return self.engine.grad_norm
+
+    def step(self) -> None:
+        g = self.param_groups[0]
+        clip_norm, clip_value = self._clip_args()
+        self.engine.optimizer_step(g["lr"], g["betas"], g["eps"], g["weight_decay"], self.grad_scale, clip_norm=clip_norm, clip_value=clip_value)
+
+
+class FlatAdamW(_StoreAdamW):
     """The same fused AdamW launch over any ``ParamStore`` (here: the discriminator's, the second optimizer of reference
     vitvqgan.py:163-164).  Under DDP the gradient buckets are all-reduced behind the discriminator's own backward (``attach_sync``: an
     ``AutogradGradSync`` whose hooks fire as autograd finishes each bucket; ``step`` only waits for what is still in flight) — a process group
@@ -94,12 +157,6 @@ class FlatAdamW(_GradClip):
         self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
         self.grad_scale = 1.0
         self.comm = None
-        self._clip_out = None      # (total_norm, clip coefficient) on the device, allocated by the first step that wants the norm
-
-    @property
-    def grad_norm(self):
-        """2-norm of the gradient the last step applied, before clipping (device f32 [1]; None until a step ran with clipping by norm or tracking on)"""
-        return None if self._clip_out is None else self._clip_out[:1]
 
     def attach_sync(self, module, **kw):
         """bucketed asynchronous gradient all-reduce for this store, driven by autograd hooks on `module`'s parameters (engine/ddp.py)"""
@@ -123,9 +180,6 @@ class FlatAdamW(_GradClip):
             self.comm = None
             self.store._grad_sync = None
 
-    def zero_grad(self, set_to_none: bool = False) -> None:
-        self.store.zero_grad()
-
     def step(self) -> None:
         import torch.distributed as dist
         from .. import _C
@@ -138,43 +192,11 @@ class FlatAdamW(_GradClip):
             dist.all_reduce(s.g)
             scale /= dist.get_world_size()
         s.step_count += 1
-        sc = getattr(s, "loss_scaler", None)
-        scaled = sc is not None and sc.enabled
-        clip_norm, clip_value = self._clip_args()
-        kw = {}      # the clip operands of the AdamW launch; empty = the call as it was before they existed
-        if clip_norm is not None:
-            if self._clip_out is None:
-                import torch
-                self._clip_out = torch.zeros(2, dtype=torch.float32, device=s.g.device)
-            if clip_norm != float("inf"):
-                kw["clip_coef"] = self._clip_out[1:]
-        if clip_value is not None:
-            kw["clip_value"] = clip_value
-        if scaled:        # the backward ran on scale_t x the loss: inf / nan check, unscale inside the update, GradScaler.update — no host sync
-            sc.found_inf.zero_()
-            if clip_norm is not None:      # one pass over the gradient: the sum of squares and the flag
-                _C.grad_clip_coef(s.g, clip_norm, scale, self._clip_out, loss_scale=sc.scale_t, found_inf=sc.found_inf)
-            else:
-                _C.nonfinite_flag(s.g, sc.found_inf)
-            _C.adamw_step(s.p, s.g, s.m, s.v, None, s.step_count, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], scale,
-                          skip_flag=sc.found_inf, loss_scale=sc.scale_t, **kw)
-            _C.loss_scale_update(sc.scale_t, sc.found_inf, sc.tracker, 2.0, 0.5, sc.growth_interval)
-        else:
-            if clip_norm is not None:
-                _C.grad_clip_coef(s.g, clip_norm, scale, self._clip_out)
-            _C.adamw_step(s.p, s.g, s.m, s.v, None, s.step_count, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], scale, **kw)
+        clip = self._clip_args()
+        scaled_step(s.g, scale, clip, self._clip_buf(clip, s.g.device), getattr(s, "loss_scaler", None), lambda **kw: _C.adamw_step(
+            s.p, s.g, s.m, s.v, None, s.step_count, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], scale, **kw))
         from ..losses.op.conv_nhwc import invalidate_packed_weights
         invalidate_packed_weights()          # the kernel wrote the weights through raw pointers: cached operand images are stale
-
-    def state_dict(self) -> dict:
-        s = self.store
-        return dict(step=s.step_count, m=s.m.detach().cpu(), v=s.v.detach().cpu(), param_groups=self.param_groups)
-
-    def load_state_dict(self, sd: dict) -> None:
-        s = self.store
-        s.step_count = int(sd["step"])
-        s.m.copy_(sd["m"]); s.v.copy_(sd["v"])
-        self.param_groups = sd["param_groups"]
 
 
 def gpt_param_groups(gpt):
@@ -213,14 +235,13 @@ class GPTAdam(_GradClip):
         copies that are no view of a master (the q | k | v bias concatenation) are rebuilt with torch after every step.
     Moving or replacing the parameters afterwards, or changing ENH_PRECISION, is refused with an error by the GPT and by step().
 
-    With the fp16 operand format step() is GradScaler's step on the device: found-inf (or the norm pass, which also finds it), the update with
-    skip / unscale, enh_loss_scale_update; initial scale ENH_LOSS_SCALE (65536), growth interval ENH_LOSS_SCALE_INTERVAL (2000): torch's defaults.
+    With the fp16 operand format step() is GradScaler's step on the device (`scaled_step` above: found-inf, or the norm pass, which also finds it, the
+    update with skip / unscale, enh_loss_scale_update); initial scale ENH_LOSS_SCALE (65536), growth interval ENH_LOSS_SCALE_INTERVAL (2000): torch's defaults.
     Under bf16 there is no scale and no skip.  The step count lives on the device (a dropped step does not advance it, and the host cannot know of
     a drop); only state_dict() reads it.  state_dict() copies m and v to the host: 88 GB at the shipped size (10.98 G parameters)."""
 
     def __init__(self, gpt, lr: float, betas=(0.9, 0.96), eps: float = 1e-8, weight_decay: float = 0.01, init_scale: float = None,
                  growth_interval: int = None) -> None:
-        import os
         import torch
         from .. import _C
         from ..modules.stage2.prior import ARENA_LAYER, ARENA_LAYER_SIZE, flat_layout, qkv_bias
@@ -239,7 +260,6 @@ class GPTAdam(_GradClip):
         self.param_groups = [dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, names=decay),
                              dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=0.0, names=no_decay)]
         self.grad_scale = 1.0
-        self._clip_out = None
         # ---- flat masters: the gradients' layout ----
         layout, total = flat_layout(gpt)
         self.p = torch.zeros(total, dtype=torch.float32, device=dev)
@@ -278,21 +298,12 @@ class GPTAdam(_GradClip):
         self.refresh_operands()
         gpt._flat_grads(dev)
         # ---- GradScaler on the device (fp16 operands only) ----
-        self.scaler = None
-        if self.dt == torch.float16:
-            self.scaler = LossScaler(dev, init_scale=float(os.environ.get("ENH_LOSS_SCALE", 65536.0)) if init_scale is None else init_scale,
-                                     growth_interval=growth_interval)
-            self.scaler.enabled = True
+        self.scaler = LossScaler(dev, init_scale, growth_interval, env="ENH_LOSS_SCALE", enabled=True) if self.dt == torch.float16 else None
 
     @property
     def loss_scale(self):
         """device f32 [1]: what forward_backward(loss_scale=...) takes; None under bf16"""
         return None if self.scaler is None else self.scaler.scale_t
-
-    @property
-    def grad_norm(self):
-        """2-norm of the gradient the last step applied, before clipping (device f32 [1]; None until a step ran with clipping by norm or tracking on)"""
-        return None if self._clip_out is None else self._clip_out[:1]
 
     def refresh_operands(self) -> None:
         """the arena and the q | k | v bias copies rebuilt from the masters with torch (one rounding from f32, as the copies the arena replaces).
@@ -325,35 +336,15 @@ class GPTAdam(_GradClip):
             raise RuntimeError(f"GPTAdam.step: the operand arena holds {self.dt} but the engine's operand format (ENH_PRECISION) changed; build a new GPTAdam")
 
     def step(self) -> None:
-        import torch
         from .. import _C
         self._check_home()
         gpt, g, h = self.gpt, self.gpt.flat_grad, self.param_groups[0]
         if g is None or g.numel() != self.p.numel():
             raise RuntimeError("GPTAdam.step: no gradients (run GPT.forward_backward / CondTransformer.training_step first)")
-        scale = self.grad_scale
-        clip_norm, clip_value = self._clip_args()
-        kw = dict(lr=h["lr"], beta1=h["betas"][0], beta2=h["betas"][1], eps=h["eps"], grad_scale=scale)
-        if clip_norm is not None:
-            if self._clip_out is None:
-                self._clip_out = torch.zeros(2, dtype=torch.float32, device=g.device)
-            if clip_norm != float("inf"):
-                kw["clip_coef"] = self._clip_out[1:]
-        if clip_value is not None:
-            kw["clip_value"] = clip_value
-        sc = self.scaler
-        if sc is not None:        # the backward ran on scale_t x the loss: inf / nan check, unscale inside the update, GradScaler.update — no host sync
-            sc.found_inf.zero_()
-            if clip_norm is not None:
-                _C.grad_clip_coef(g, clip_norm, scale, self._clip_out, loss_scale=sc.scale_t, found_inf=sc.found_inf)
-            else:
-                _C.nonfinite_flag(g, sc.found_inf)
-            _C.adam_step_segments(self.p, g, self.m, self.v, self.arena, self.table, self.state, skip_flag=sc.found_inf, loss_scale=sc.scale_t, **kw)
-            _C.loss_scale_update(sc.scale_t, sc.found_inf, sc.tracker, 2.0, 0.5, sc.growth_interval)
-        else:
-            if clip_norm is not None:
-                _C.grad_clip_coef(g, clip_norm, scale, self._clip_out)
-            _C.adam_step_segments(self.p, g, self.m, self.v, self.arena, self.table, self.state, **kw)
+        clip = self._clip_args()
+        scaled_step(g, self.grad_scale, clip, self._clip_buf(clip, g.device), self.scaler, lambda **kw: _C.adam_step_segments(
+            self.p, g, self.m, self.v, self.arena, self.table, self.state, lr=h["lr"], beta1=h["betas"][0], beta2=h["betas"][1], eps=h["eps"],
+            grad_scale=self.grad_scale, **kw))
         # the kernel wrote the masters through raw pointers: the f32 copies that are no view of a master are rebuilt (3C elements per layer), and
         # operand copies of any other format (the exact mode's f32 q | k | v) are dropped so that their next use rebuilds them
         self._refresh_bias_copies()

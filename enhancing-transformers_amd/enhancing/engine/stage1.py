@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import _C
+from .optim import LossScaler, scaled_step
 
 F32, BF16, F16 = torch.float32, torch.bfloat16, torch.float16
 # precision modes of the engine: the two product paths ("bf16" / "fp16": 16-bit MFMA operands of that format, fp32 accumulation / residual stream /
@@ -422,7 +423,7 @@ class Stage1Engine:
         single-pass mode that meets the 1e-3 parity clause; "bf16" is the round-1..5 default, ~3 % faster, ~5e-3).
         "fp16" is the reference's --use_amp dtype (main.py:25,52: Lightning precision=16): 11-bit significands bring the single-pass forward within 1e-3
         of the fp32 reference (bf16: ~5e-3) at the same MFMA rate; the backward runs on fp16 operands too, with the loss gradient multiplied by a
-        power-of-two loss scale that lives ON THE DEVICE (`scale_t`; initial value ENH_LOSS_SCALE, default 2^16 — GradScaler's initial scale): the
+        power-of-two loss scale that lives ON THE DEVICE (`scaler`, engine/optim.py's LossScaler; initial value ENH_LOSS_SCALE, default 2^16): the
         AdamW launch divides it out again, an inf / nan check of the flat gradient makes that launch a no-op (GradScaler.step's skip), and
         enh_loss_scale_update applies GradScaler.update (x 0.5 after an overflow, x 2 after ENH_LOSS_SCALE_INTERVAL = 2000 clean steps) — all without a
         host round trip, so the step stays HIP-graph capturable.  ENH_LOSS_SCALE_INTERVAL=0 keeps the scale from growing.
@@ -459,11 +460,7 @@ class Stage1Engine:
         if precision != "bf16" and "x3" in (self.encoder_precision, self.decoder_precision):
             raise ValueError("x3 towers in the TRAINING forward save bf16 hi planes for a bf16 backward: they need precision='bf16' (fp16 meets the tolerance in one pass)")
         self.adt = OPERAND_DTYPE[precision]
-        # loss scale of the fp16 backward (1 elsewhere): a power of two, so scaling and unscaling are exact
         self.scaled = precision == "fp16"                       # the backward runs under a loss scale
-        self._init_scale = float(os.environ.get("ENH_LOSS_SCALE", 65536.0)) if self.scaled else 1.0
-        self.scale_growth_interval = int(os.environ.get("ENH_LOSS_SCALE_INTERVAL", 2000))      # torch.cuda.amp.GradScaler's default
-        self.check_nonfinite = self.scaled and os.environ.get("ENH_NONFINITE_CHECK", "1") != "0"
         if not torch.cuda.is_available():
             raise RuntimeError("Stage1Engine needs a ROCm device (MI355X); the HIP path has no CPU fallback")
         _C.lib()
@@ -494,13 +491,13 @@ class Stage1Engine:
         self.use_graphs = os.environ.get("ENH_GRAPHS", "0") == "1"
         self._graphs: Dict[tuple, tuple] = {}
         self.store.operand_hooks.append(self._refresh_x3_operands)
-        self.found_inf = torch.zeros(1, dtype=F32, device=self.device) if self.check_nonfinite else None      # written by nonfinite_flag, read by the AdamW launch
-        self.skipped_steps = None      # device counter of dropped steps (fp16): accumulated without a host sync
-        if self.check_nonfinite:
-            self.skipped_steps = torch.zeros(1, dtype=F32, device=self.device)
-        # the loss scale and GradScaler's growth tracker, on the device (None for bf16 / fp32 engines: no scaling anywhere)
-        self.scale_t = torch.full((1,), self._init_scale, dtype=F32, device=self.device) if self.scaled else None
-        self._growth_tracker = torch.zeros(1, dtype=torch.int32, device=self.device) if self.scaled else None
+        # the loss scale of the fp16 backward with GradScaler's state, on the device (None for bf16 / fp32 engines: no scaling anywhere); a power of two,
+        # so scaling and unscaling are exact.  ENH_NONFINITE_CHECK=0 scales without the inf / nan check: no step is dropped, the scale never moves.
+        # scale_t, found_inf (None without the check) and skipped_steps (the dropped steps, counted on the device) are the scaler's own tensors.
+        self.scaler = LossScaler(self.device, env="ENH_LOSS_SCALE", enabled=True, check=os.environ.get("ENH_NONFINITE_CHECK", "1") != "0",
+                                 count_skipped=True) if self.scaled else None
+        sc = self.scaler
+        self.scale_t, self.found_inf, self.skipped_steps = (sc.scale_t, sc.found_inf, sc.skipped_steps) if self.scaled else (None, None, None)
         # (total_norm, clip coefficient) of the last optimizer_step that asked for the gradient norm: written by enh_grad_clip_coef, the coefficient is
         # read by the AdamW launch — neither ever visits the host inside the step
         self._clip_out = torch.zeros(2, dtype=F32, device=self.device)
@@ -509,7 +506,7 @@ class Stage1Engine:
     @property
     def loss_scale(self) -> float:
         """current loss scale as a host number (reads the device scalar: synchronises; for tests and logging — the step itself never needs it)"""
-        return float(self.scale_t.item()) if self.scaled else 1.0
+        return self.scaler.value if self.scaled else 1.0
 
     # ---- helpers -----------------------------------------------------------------------------
     def _invalidate_saved(self) -> None:
@@ -895,31 +892,11 @@ class Stage1Engine:
             s.comm_done = False
             grad_scale = grad_scale / self.comm.world
         s.step_count += 1
-        skip = None
-        loss_scale = self.scale_t if (self.scaled and not s.grads_unscaled) else None
-        if self.check_nonfinite:
-            # GradScaler.step's found-inf skip + GradScaler.update (reference main.py:25,52 --use_amp), without a host round trip: one pass over the flat
-            # gradient sets the flag, the AdamW launch reads it and writes nothing when it is set, and the scale is halved / doubled on the device.
-            # skipped_steps counts the drops on the device (read it with .item() outside the step if wanted).  The host step count advances either way:
-            # a dropped step then only shifts the bias correction by one step.
-            skip = self.found_inf
-            skip.zero_()
-        clip = {}      # the clip operands of the AdamW launch; empty = the call as it was before they existed
-        if clip_norm is not None:
-            # the same single pass over the flat gradient gives the sum of squares AND the flag: the norm costs the fp16 step no extra read
-            _C.grad_clip_coef(s.g, clip_norm, grad_scale, self._clip_out, loss_scale=loss_scale, found_inf=skip)
-            if clip_norm != float("inf"):
-                clip["clip_coef"] = self._clip_out[1:]
-        elif skip is not None:
-            _C.nonfinite_flag(s.g, skip)
-        if clip_value:
-            clip["clip_value"] = float(clip_value)
-        if skip is not None:
-            self.skipped_steps.add_(skip)
-        _C.adamw_step(s.p, s.g, s.m, s.v, s.p16 if self.half else None, s.step_count, lr, betas[0], betas[1], eps, weight_decay,
-                      grad_scale, skip_flag=skip, loss_scale=loss_scale, **clip)
-        if self.check_nonfinite:
-            _C.loss_scale_update(self.scale_t, skip, self._growth_tracker, 2.0, 0.5, self.scale_growth_interval)
+        # under fp16 this is GradScaler.step + GradScaler.update (reference main.py:25,52 --use_amp) on the device.  The host step count advances
+        # either way: a dropped step then only shifts the bias correction by one step.
+        scaled_step(s.g, grad_scale, (clip_norm, clip_value), self._clip_out, self.scaler, lambda **kw: _C.adamw_step(
+            s.p, s.g, s.m, s.v, s.p16 if self.half else None, s.step_count, lr, betas[0], betas[1], eps, weight_decay, grad_scale, **kw),
+            grads_unscaled=s.grads_unscaled)
         s.refresh_operands()      # operands derived from the masters (the towers' pre-scaled q | k | v weights, the x3 images: _refresh_x3_operands)
 
     def _refresh_x3_operands(self) -> None:

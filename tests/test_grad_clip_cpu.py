@@ -99,6 +99,114 @@ def test_flat_adamw_launch_sequence(monkeypatch, calls):
         opt.step()
 
 
+_INF = float("inf")
+# The launch table of the shared step (engine/optim.py scaled_step), written down from the three optimizers' steps as they were before they shared it.
+# scaler: None | "disabled" | "on" | "nocheck" (the engine's ENH_NONFINITE_CHECK=0); clip = (clip_norm, clip_value); then the launches in order and
+# the exact keyword set of the Adam launch.  The flag pass and the norm pass under a scaler that checks must find the flag zeroed.
+_STEP_ROWS = [
+    # id                 scaler      clip           unscaled  launches                                                  Adam keywords
+    ("plain",            None,       (None, None),  False,    ["adam"],                                                 set()),
+    ("disabled",         "disabled", (None, None),  False,    ["adam"],                                                 set()),
+    ("norm",             None,       (2.0, None),   False,    ["grad_clip_coef", "adam"],                               {"clip_coef"}),
+    ("disabled-norm",    "disabled", (2.0, None),   False,    ["grad_clip_coef", "adam"],                               {"clip_coef"}),
+    ("track",            None,       (_INF, None),  False,    ["grad_clip_coef", "adam"],                               set()),
+    ("value",            None,       (None, 0.25),  False,    ["adam"],                                                 {"clip_value"}),
+    ("value-0",          None,       (None, 0),     False,    ["adam"],                                                 set()),
+    ("scaled",           "on",       (None, None),  False,    ["nonfinite_flag", "adam", "loss_scale_update"],          {"skip_flag", "loss_scale"}),
+    ("scaled-norm",      "on",       (2.0, None),   False,    ["grad_clip_coef", "adam", "loss_scale_update"],          {"skip_flag", "loss_scale", "clip_coef"}),
+    ("scaled-track",     "on",       (_INF, None),  False,    ["grad_clip_coef", "adam", "loss_scale_update"],          {"skip_flag", "loss_scale"}),
+    ("scaled-value",     "on",       (None, 0.25),  False,    ["nonfinite_flag", "adam", "loss_scale_update"],          {"skip_flag", "loss_scale", "clip_value"}),
+    ("unscaled",         "on",       (None, None),  True,     ["nonfinite_flag", "adam", "loss_scale_update"],          {"skip_flag"}),
+    ("unscaled-norm",    "on",       (2.0, None),   True,     ["grad_clip_coef", "adam", "loss_scale_update"],          {"skip_flag", "clip_coef"}),
+    ("nocheck",          "nocheck",  (None, None),  False,    ["adam"],                                                 {"loss_scale"}),
+    ("nocheck-norm",     "nocheck",  (2.0, None),   False,    ["grad_clip_coef", "adam"],                               {"loss_scale", "clip_coef"}),
+]
+
+
+@pytest.mark.parametrize("scaler,clip,unscaled,launches,adam_kw", [r[1:] for r in _STEP_ROWS], ids=[r[0] for r in _STEP_ROWS])
+def test_shared_step_issues_the_rows_of_the_launch_table(monkeypatch, scaler, clip, unscaled, launches, adam_kw):
+    from enhancing import _C
+    from enhancing.engine.optim import LossScaler, scaled_step
+    cpu = torch.device("cpu")
+    sc = None if scaler is None else LossScaler(cpu, init_scale=8.0, growth_interval=7, enabled=scaler != "disabled", check=scaler != "nocheck",
+                                                count_skipped=True)
+    on = scaler == "on"
+    if scaler in ("on", "disabled"):
+        sc.found_inf.fill_(1.0)      # left over from an earlier step: a scaler that checks has to clear it before the pass that sets it
+    g, out, rec = torch.ones(64), torch.zeros(2), []
+
+    def flag_pass(x, flag):
+        rec.append(("nonfinite_flag", x, flag, float(flag)))
+        flag.fill_(1.0)              # "an inf was found": the dropped-step counter below must see it
+
+    def norm_pass(x, max_norm, grad_scale, o, **kw):
+        rec.append(("grad_clip_coef", x, max_norm, grad_scale, o, kw, None if kw.get("found_inf") is None else float(kw["found_inf"])))
+
+    monkeypatch.setattr(_C, "nonfinite_flag", flag_pass)
+    monkeypatch.setattr(_C, "grad_clip_coef", norm_pass)
+    monkeypatch.setattr(_C, "loss_scale_update", lambda *a: rec.append(("loss_scale_update",) + a))
+    scaled_step(g, 0.5, clip, out, sc, lambda **kw: rec.append(("adam", kw)), **(dict(grads_unscaled=True) if unscaled else {}))
+    assert [r[0] for r in rec] == launches
+    by_name = {r[0]: r for r in rec}
+    scale_operand = on and not unscaled or scaler == "nocheck"      # the table: loss_scale reaches both launches or neither
+    if "nonfinite_flag" in by_name:
+        _, x, flag, seen = by_name["nonfinite_flag"]
+        assert x is g and flag is sc.found_inf and seen == 0.0
+    if "grad_clip_coef" in by_name:
+        _, x, max_norm, grad_scale, o, kw, seen = by_name["grad_clip_coef"]
+        assert x is g and max_norm == clip[0] and grad_scale == 0.5 and o is out
+        assert set(kw) == ({"found_inf"} if on else set()) | ({"loss_scale"} if scale_operand else set())
+        assert kw.get("found_inf") is (sc.found_inf if on else None) and kw.get("loss_scale") is (sc.scale_t if scale_operand else None)
+        assert seen == (0.0 if on else None)
+    kw = by_name["adam"][1]
+    assert set(kw) == adam_kw and all(v is not None for v in kw.values())
+    if "skip_flag" in kw:
+        assert kw["skip_flag"] is sc.found_inf
+    if "loss_scale" in kw:
+        assert kw["loss_scale"] is sc.scale_t
+    if "clip_coef" in kw:
+        assert kw["clip_coef"].data_ptr() == out.data_ptr() + 4 and kw["clip_coef"].numel() == 1
+    if "clip_value" in kw:
+        assert kw["clip_value"] == clip[1]
+    if on:
+        upd = by_name["loss_scale_update"]
+        assert upd[1] is sc.scale_t and upd[2] is sc.found_inf and upd[3] is sc.tracker and upd[4:] == (2.0, 0.5, 7)
+        assert float(sc.skipped_steps) == (1.0 if "nonfinite_flag" in by_name else 0.0)      # counts what the flag pass left, after the update read it
+    elif scaler == "disabled":
+        assert float(sc.found_inf) == 1.0 and float(sc.skipped_steps) == 0.0                  # a disabled scaler is not touched
+    elif scaler == "nocheck":
+        assert sc.found_inf is None and sc.skipped_steps is None
+
+
+def test_loss_scaler_reads_each_default_from_its_own_variable(monkeypatch):
+    from enhancing.engine.optim import LossScaler
+    cpu = torch.device("cpu")
+    for v in ("ENH_LOSS_SCALE", "ENH_LOSS_NET_SCALE", "ENH_LOSS_SCALE_INTERVAL"):
+        monkeypatch.delenv(v, raising=False)
+    net, eng = LossScaler(cpu), LossScaler(cpu, env="ENH_LOSS_SCALE", enabled=True)
+    assert (net.scale_t.item(), net.growth_interval, net.enabled, net.value) == (4096.0, 2000, False, 1.0) and net.skipped_steps is None
+    assert (eng.scale_t.item(), eng.growth_interval, eng.enabled, eng.value) == (65536.0, 2000, True, 65536.0)
+    monkeypatch.setenv("ENH_LOSS_SCALE", "1024")
+    monkeypatch.setenv("ENH_LOSS_NET_SCALE", "256")
+    monkeypatch.setenv("ENH_LOSS_SCALE_INTERVAL", "5")
+    assert LossScaler(cpu).scale_t.item() == 256.0 and LossScaler(cpu, env="ENH_LOSS_SCALE").scale_t.item() == 1024.0
+    assert LossScaler(cpu).growth_interval == 5 and LossScaler(cpu, init_scale=2.0, growth_interval=3).scale_t.item() == 2.0
+
+
+def test_fused_and_flat_adamw_save_the_same_keys():
+    from enhancing.engine.optim import FlatAdamW, FusedAdamW
+    st = _Store()
+    st.step_count, eng = 3, type("E", (), {})()
+    eng.store = st
+    for opt in (FlatAdamW(st, lr=1e-3), FusedAdamW(eng, lr=1e-3)):
+        sd = opt.state_dict()
+        assert sorted(sd) == ["m", "param_groups", "step", "v"] and sd["step"] == 3 and sd["param_groups"] is opt.param_groups
+        st.m.fill_(0.0)
+        opt.load_state_dict(dict(sd, step=5, m=torch.full_like(st.m, 2.0)))
+        assert st.step_count == 5 and float(st.m[0]) == 2.0
+        st.step_count = 3
+
+
 def test_trainer_hands_the_switches_to_every_optimizer_and_logs_the_norms(monkeypatch, tmp_path):
     from enhancing.engine import trainer as T
 
