@@ -15,7 +15,12 @@
 //   enh_skinny_gemm_f32   the exact mode's form of the product: f32 operands, vector ALU, tree-ordered sums.
 // The step's LayerNorm and embedding are row kernels and stand beside the teacher-forced forward's: gpt_rows.hip (enh_row_ln_scale, enh_gpt_embed).
 // Every result is the same bits on every run: all sums run in a fixed order.
+//
+// The cursor forms (enh_cursor_advance, enh_decode_attention_at, enh_embed_step_at, enh_sample_logits_at) take the loop's position from one int32 in
+// device memory instead of from their arguments, so the launches of one position, captured into a HIP graph, can be replayed for the next one.
+// Each is a kernel of its own name around the __device__ body of its by-value sibling: the same arithmetic, the same bits.
 #include "common.h"
+#include "embed_row.h"
 #include <type_traits>
 
 #define GD_MAX_M 64
@@ -181,10 +186,10 @@ __device__ __forceinline__ void gd_load8(const void* p, float (&f)[8]) {
   }
 }
 
+// one piece (blockIdx.y) of one (batch, head) pair (blockIdx.x): the body of gpt_decode_attn_kernel and of its cursor form gpt_decode_attn_at_kernel
 template <typename OT, bool F32>
-__global__ __launch_bounds__(256) void gpt_decode_attn_kernel(const void* __restrict__ qkv_, void* __restrict__ Kc_, void* __restrict__ Vc_, int H, int hs,
-                                                              int Tmax, int t, int nsplit, int split_len, float scale, void* __restrict__ out_,
-                                                              float* __restrict__ part) {
+__device__ __forceinline__ void gd_attn_piece(const void* __restrict__ qkv_, void* __restrict__ Kc_, void* __restrict__ Vc_, int H, int hs, int Tmax, int t,
+                                              int nsplit, int split_len, float scale, void* __restrict__ out_, float* __restrict__ part) {
   typedef typename std::conditional<F32, float, uint16_t>::type CT;
   __shared__ float s_p[GD_ATT_PIECE];
   __shared__ float s_mx[4], s_sm[4];
@@ -288,9 +293,16 @@ __global__ __launch_bounds__(256) void gpt_decode_attn_kernel(const void* __rest
   }
 }
 
-// pieces in ascending order under the common maximum
 template <typename OT, bool F32>
-__global__ __launch_bounds__(128) void gpt_decode_attn_merge_kernel(const float* __restrict__ part, int H, int hs, int nsplit, void* __restrict__ out_) {
+__global__ __launch_bounds__(256) void gpt_decode_attn_kernel(const void* __restrict__ qkv_, void* __restrict__ Kc_, void* __restrict__ Vc_, int H, int hs,
+                                                              int Tmax, int t, int nsplit, int split_len, float scale, void* __restrict__ out_,
+                                                              float* __restrict__ part) {
+  gd_attn_piece<OT, F32>(qkv_, Kc_, Vc_, H, hs, Tmax, t, nsplit, split_len, scale, out_, part);
+}
+
+// pieces in ascending order under the common maximum: the body of gpt_decode_attn_merge_kernel and of its cursor form
+template <typename OT, bool F32>
+__device__ __forceinline__ void gd_attn_merge(const float* __restrict__ part, int H, int hs, int nsplit, void* __restrict__ out_) {
   typedef typename std::conditional<F32, float, uint16_t>::type CT;
   const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
   const float* pp = part + (size_t)bh * nsplit * (hs + 2);
@@ -308,8 +320,14 @@ __global__ __launch_bounds__(128) void gpt_decode_attn_merge_kernel(const float*
   }
 }
 
-// pieces of a cache of `len` slots: at most GD_ATT_PIECE slots each, and more, down to 64 slots, while B * H workgroups leave the chip idle
-static inline void gd_att_plan(int64_t BH, int len, int* nsplit, int* split_len) {
+template <typename OT, bool F32>
+__global__ __launch_bounds__(128) void gpt_decode_attn_merge_kernel(const float* __restrict__ part, int H, int hs, int nsplit, void* __restrict__ out_) {
+  gd_attn_merge<OT, F32>(part, H, hs, nsplit, out_);
+}
+
+// pieces of a cache of `len` slots: at most GD_ATT_PIECE slots each, and more, down to 64 slots, while B * H workgroups leave the chip idle.
+// Host and device: the cursor kernels below plan on the device from the position they read there, with the integers of the host's plan.
+__host__ __device__ static inline void gd_att_plan(int64_t BH, int len, int* nsplit, int* split_len) {
   int64_t by_len = (len + GD_ATT_PIECE - 1) / GD_ATT_PIECE;
   int64_t want = (512 + BH - 1) / BH;
   const int64_t most = (len + 63) / 64;
@@ -357,6 +375,107 @@ extern "C" int enh_decode_attention(const void* qkv, void* k_cache, void* v_cach
     if (nsplit > 1) ENH_DT_DISPATCH(dtype, (gpt_decode_attn_merge_kernel<OT, false><<<(unsigned)(B * H), 128, 0, s>>>(part, H, hs, nsplit, out)));
   }
   return enh_check_launch("enh_decode_attention");
+}
+
+// ---------------------------------------------------------------------------------------------
+// the cursor forms: the position t of the sampling loop is one int32 in device memory, so a captured launch sequence can be replayed for the
+// next position.  Nothing that depends on t is a kernel argument: the slot, the split plan and the grid's live part are worked out on the device.
+// ---------------------------------------------------------------------------------------------
+__global__ void gpt_cursor_advance_kernel(int* __restrict__ cursor) { *cursor += 1; }
+
+extern "C" int enh_cursor_advance(int* cursor, void* stream) {
+  ENH_REQUIRE(cursor, ENH_E_BADARG, "enh_cursor_advance: null pointer");
+  enh_note_kernel_plain("gpt_cursor_advance_kernel");
+  gpt_cursor_advance_kernel<<<1, 1, 0, (hipStream_t)stream>>>(cursor);
+  return enh_check_launch("enh_cursor_advance");
+}
+
+// the step t = *cursor + t_offset, or -1 when it lies outside the cache: then no workgroup reads or writes anything
+__device__ __forceinline__ int gd_cursor_step(const int* __restrict__ cursor, int t_offset, int Tmax) {
+  const int64_t t = (int64_t)*cursor + t_offset;
+  return t >= 0 && t < Tmax ? (int)t : -1;
+}
+
+// gpt_decode_attn_kernel under a grid sized for the whole cache (gridDim.y = (Tmax + 63) / 64 >= every plan's nsplit): the pieces past the plan return
+template <typename OT, bool F32>
+__global__ __launch_bounds__(256) void gpt_decode_attn_at_kernel(const void* __restrict__ qkv_, void* __restrict__ Kc_, void* __restrict__ Vc_, int H, int hs,
+                                                                 int Tmax, const int* __restrict__ cursor, int t_offset, float scale,
+                                                                 void* __restrict__ out_, float* __restrict__ part) {
+  const int t = gd_cursor_step(cursor, t_offset, Tmax);
+  if (t < 0) return;
+  int nsplit, split_len;
+  gd_att_plan((int64_t)gridDim.x, t + 1, &nsplit, &split_len);
+  if ((int)blockIdx.y >= nsplit) return;
+  gd_attn_piece<OT, F32>(qkv_, Kc_, Vc_, H, hs, Tmax, t, nsplit, split_len, scale, out_, part);
+}
+
+// always launched: under a plan of one piece the main kernel has written out itself
+template <typename OT, bool F32>
+__global__ __launch_bounds__(128) void gpt_decode_attn_merge_at_kernel(const float* __restrict__ part, int H, int hs, int Tmax,
+                                                                       const int* __restrict__ cursor, int t_offset, void* __restrict__ out_) {
+  const int t = gd_cursor_step(cursor, t_offset, Tmax);
+  if (t < 0) return;
+  int nsplit, split_len;
+  gd_att_plan((int64_t)gridDim.x, t + 1, &nsplit, &split_len);
+  if (nsplit == 1) return;
+  gd_attn_merge<OT, F32>(part, H, hs, nsplit, out_);
+}
+
+extern "C" int enh_decode_attention_at(const void* qkv, void* k_cache, void* v_cache, int B, int H, int hs, int Tmax, const int* cursor, int t_offset,
+                                       void* out, void* workspace, size_t workspace_bytes, int dtype, void* stream) {
+  ENH_REQUIRE(qkv && k_cache && v_cache && out && cursor, ENH_E_BADARG, "enh_decode_attention_at: null pointer");
+  ENH_REQUIRE(dtype == ENH_DT_BF16 || dtype == ENH_DT_F16 || dtype == ENH_DT_F32, ENH_E_BADARG, "enh_decode_attention_at: dtype must be 0, 1 or 2, got %d", dtype);
+  ENH_REQUIRE(B >= 1 && H >= 1 && (int64_t)B * H <= 2147483647LL, ENH_E_BADARG, "enh_decode_attention_at: B=%d H=%d", B, H);
+  ENH_REQUIRE(hs >= 64 && hs <= 384 && hs % 64 == 0, ENH_E_SHAPE, "enh_decode_attention_at: head size must be a multiple of 64 up to 384, got %d", hs);
+  ENH_REQUIRE(Tmax >= 1 && Tmax <= GD_ATT_MAX_T, ENH_E_SHAPE, "enh_decode_attention_at: cache length must be in [1, %d], got %d", GD_ATT_MAX_T, Tmax);
+  // the plan is not known here: the workspace holds the most pieces any position of the cache can have
+  ENH_REQUIRE(workspace && workspace_bytes >= enh_decode_attention_workspace_bytes(B, H, hs, Tmax), ENH_E_WORKSPACE,
+              "enh_decode_attention_at: workspace too small");
+  float* part = reinterpret_cast<float*>(workspace);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)(B * H), (unsigned)((Tmax + 63) / 64));
+  const float scale = 1.0f / sqrtf((float)hs);
+  if (dtype == ENH_DT_F32) {
+    enh_note_kernel_plain("gpt_decode_attn_at_kernel<BF16, true>");
+    gpt_decode_attn_at_kernel<BF16, true><<<grid, 256, 0, s>>>(qkv, k_cache, v_cache, H, hs, Tmax, cursor, t_offset, scale, out, part);
+    gpt_decode_attn_merge_at_kernel<BF16, true><<<(unsigned)(B * H), 128, 0, s>>>(part, H, hs, Tmax, cursor, t_offset, out);
+  } else {
+    enh_note_kernel_plain(dtype == ENH_DT_F16 ? "gpt_decode_attn_at_kernel<F16, false>" : "gpt_decode_attn_at_kernel<BF16, false>");
+    ENH_DT_DISPATCH(dtype, (gpt_decode_attn_at_kernel<OT, false><<<grid, 256, 0, s>>>(qkv, k_cache, v_cache, H, hs, Tmax, cursor, t_offset, scale, out, part)));
+    ENH_DT_DISPATCH(dtype, (gpt_decode_attn_merge_at_kernel<OT, false><<<(unsigned)(B * H), 128, 0, s>>>(part, H, hs, Tmax, cursor, t_offset, out)));
+  }
+  return enh_check_launch("enh_decode_attention_at");
+}
+
+// The step's input row at t = *cursor: row b sums the n ids at ids_base[b id_row_stride + t id_t_stride + id_offset ..] in ascending order and adds
+// the position row at pos_base + t pos_t_stride + pos_offset (embed_row.h: rq_embed_step_kernel's body; at n == 1 the row is table[id] + pos, the
+// bits of gpt_embed_kernel).  A position outside [t_lo, t_hi) reads and writes nothing.
+__global__ __launch_bounds__(256) void gpt_embed_at_kernel(const float* __restrict__ table, const int64_t* __restrict__ ids_base, int64_t id_row_stride,
+                                                           int64_t id_t_stride, int64_t id_offset, int n, const float* __restrict__ pos_base,
+                                                           int64_t pos_t_stride, int64_t pos_offset, const int* __restrict__ cursor, int t_lo, int t_hi,
+                                                           int C, int V, float* __restrict__ out) {
+  const int64_t t = *cursor;
+  if (t < t_lo || t >= t_hi) return;
+  const int64_t b = blockIdx.x;
+  rq_embed_row(table, ids_base + b * id_row_stride + t * id_t_stride + id_offset, n, pos_base + t * pos_t_stride + pos_offset, C, V, out + b * C);
+}
+
+extern "C" int enh_embed_step_at(const float* table, const int64_t* ids_base, int64_t id_row_stride, int64_t id_t_stride, int64_t id_offset, int n,
+                                 const float* pos_base, int64_t pos_t_stride, int64_t pos_offset, const int* cursor, int t_lo, int t_hi, int B, int C,
+                                 int V, float* out, void* stream) {
+  ENH_REQUIRE(n >= 1 && n <= RQ_MAX_DEPTH, ENH_E_SHAPE, "enh_embed_step_at: the number of summed codes must be in [1, %d], got %d", RQ_MAX_DEPTH, n);
+  ENH_REQUIRE(table && ids_base && pos_base && cursor && out, ENH_E_BADARG, "enh_embed_step_at: null pointer");
+  ENH_REQUIRE(B >= 1 && V >= 1 && t_lo >= 0 && t_hi > t_lo, ENH_E_BADARG, "enh_embed_step_at: B=%d V=%d positions [%d, %d)", B, V, t_lo, t_hi);
+  // the first and the last position's ids and position row must lie at or behind the bases (the caller owns what follows them)
+  ENH_REQUIRE(t_lo * id_t_stride + id_offset >= 0 && (t_hi - 1) * id_t_stride + id_offset >= 0 && t_lo * pos_t_stride + pos_offset >= 0 &&
+                  (t_hi - 1) * pos_t_stride + pos_offset >= 0 && id_row_stride >= 0 && pos_offset % 4 == 0 && pos_t_stride % 4 == 0,
+              ENH_E_BADARG, "enh_embed_step_at: strides %lld %lld %lld / %lld %lld reach in front of a base or break the 16-byte alignment",
+              (long long)id_row_stride, (long long)id_t_stride, (long long)id_offset, (long long)pos_t_stride, (long long)pos_offset);
+  ENH_REQUIRE(C >= 4 && C % 4 == 0, ENH_E_SHAPE, "enh_embed_step_at: C must be a positive multiple of 4, got %d", C);
+  enh_note_kernel_plain("gpt_embed_at_kernel");
+  gpt_embed_at_kernel<<<(unsigned)B, 256, 0, (hipStream_t)stream>>>(table, ids_base, id_row_stride, id_t_stride, id_offset, n, pos_base, pos_t_stride,
+                                                                    pos_offset, cursor, t_lo, t_hi, C, V, out);
+  return enh_check_launch("enh_embed_step_at");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -418,11 +537,11 @@ __device__ __forceinline__ uint32_t gd_key(float x) {   // a < b  <=>  key(a) < 
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__global__ __launch_bounds__(1024) void gpt_sample_kernel(const float* __restrict__ logits, int V, float temperature, int top_k, float top_p,
-                                                          const float* __restrict__ uniforms, uint64_t seed, uint32_t call, uint32_t step,
-                                                          int64_t row0, int64_t* __restrict__ codes, int64_t code_stride,
-                                                          float* __restrict__ logits_out, int64_t logits_out_stride, uint8_t* __restrict__ mask_out,
-                                                          float* __restrict__ probs_out) {
+// one row (blockIdx.x): the body of gpt_sample_kernel and of its cursor form gpt_sample_at_kernel
+__device__ __forceinline__ void gd_sample_row(const float* __restrict__ logits, int V, float temperature, int top_k, float top_p,
+                                              const float* __restrict__ uniforms, uint64_t seed, uint32_t call, uint32_t step, int64_t row0,
+                                              int64_t* __restrict__ codes, int64_t code_stride, float* __restrict__ logits_out,
+                                              int64_t logits_out_stride, uint8_t* __restrict__ mask_out, float* __restrict__ probs_out) {
   __shared__ float s_f[16];
   __shared__ int s_i[16];
   __shared__ int s_pick, s_last;
@@ -556,6 +675,15 @@ __global__ __launch_bounds__(1024) void gpt_sample_kernel(const float* __restric
   }
 }
 
+__global__ __launch_bounds__(1024) void gpt_sample_kernel(const float* __restrict__ logits, int V, float temperature, int top_k, float top_p,
+                                                          const float* __restrict__ uniforms, uint64_t seed, uint32_t call, uint32_t step,
+                                                          int64_t row0, int64_t* __restrict__ codes, int64_t code_stride,
+                                                          float* __restrict__ logits_out, int64_t logits_out_stride, uint8_t* __restrict__ mask_out,
+                                                          float* __restrict__ probs_out) {
+  gd_sample_row(logits, V, temperature, top_k, top_p, uniforms, seed, call, step, row0, codes, code_stride, logits_out, logits_out_stride, mask_out,
+                probs_out);
+}
+
 extern "C" int enh_sample_logits(const float* logits, int B, int V, float temperature, int top_k, float top_p, const float* uniforms, uint64_t seed,
                                  uint32_t call, uint32_t step, int64_t row0, int64_t* codes, int64_t code_stride, float* logits_out,
                                  int64_t logits_out_stride, uint8_t* mask_out, float* probs_out, void* stream) {
@@ -568,4 +696,30 @@ extern "C" int enh_sample_logits(const float* logits, int B, int V, float temper
   gpt_sample_kernel<<<(unsigned)B, 1024, 0, (hipStream_t)stream>>>(logits, V, temperature, top_k, top_p, uniforms, seed, call, step, row0, codes,
                                                                    code_stride, logits_out, logits_out_stride, mask_out, probs_out);
   return enh_check_launch("enh_sample_logits");
+}
+
+// the cursor form: step = *cursor * step_mul + step_add selects the draw's uniform, the column of the codes and the row of logits_out.  A step
+// outside [0, n_steps) (a replay too many) writes nothing.
+__global__ __launch_bounds__(1024) void gpt_sample_at_kernel(const float* __restrict__ logits, int V, float temperature, int top_k, float top_p,
+                                                             uint64_t seed, uint32_t call, const int* __restrict__ cursor, int step_mul, int step_add,
+                                                             int n_steps, int64_t row0, int64_t* __restrict__ codes_base, int64_t code_row_stride,
+                                                             float* __restrict__ logits_base, int64_t logits_row_stride) {
+  const int64_t step = (int64_t)*cursor * step_mul + step_add;
+  if (step < 0 || step >= n_steps) return;
+  gd_sample_row(logits, V, temperature, top_k, top_p, nullptr, seed, call, (uint32_t)step, row0, codes_base + step, code_row_stride,
+                logits_base ? logits_base + step * V : nullptr, logits_row_stride, nullptr, nullptr);
+}
+
+extern "C" int enh_sample_logits_at(const float* logits, int B, int V, float temperature, int top_k, float top_p, uint64_t seed, uint32_t call,
+                                    const int* cursor, int step_mul, int step_add, int n_steps, int64_t row0, int64_t* codes_base,
+                                    int64_t code_row_stride, float* logits_base, int64_t logits_row_stride, void* stream) {
+  ENH_REQUIRE(logits && codes_base && cursor, ENH_E_BADARG, "enh_sample_logits_at: null pointer");
+  ENH_REQUIRE(B >= 1 && n_steps >= 1 && row0 >= 0 && code_row_stride >= n_steps && (!logits_base || logits_row_stride >= (int64_t)n_steps * V), ENH_E_BADARG,
+              "enh_sample_logits_at: B=%d n_steps=%d strides %lld %lld", B, n_steps, (long long)code_row_stride, (long long)logits_row_stride);
+  ENH_REQUIRE(V >= 1 && V <= GD_SAMPLE_MAX_V, ENH_E_SHAPE, "enh_sample_logits_at: V must be in [1, %d], got %d", GD_SAMPLE_MAX_V, V);
+  ENH_REQUIRE(temperature > 0.f, ENH_E_BADARG, "enh_sample_logits_at: temperature must be positive, got %g", (double)temperature);
+  enh_note_kernel_plain("gpt_sample_at_kernel");
+  gpt_sample_at_kernel<<<(unsigned)B, 1024, 0, (hipStream_t)stream>>>(logits, V, temperature, top_k, top_p, seed, call, cursor, step_mul, step_add, n_steps,
+                                                                      row0, codes_base, code_row_stride, logits_base, logits_row_stride);
+  return enh_check_launch("enh_sample_logits_at");
 }

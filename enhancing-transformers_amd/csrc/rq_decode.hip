@@ -9,34 +9,19 @@
 //                                 32 pairs per workgroup, nothing staged in LDS
 // No float atomics; every sum runs in a fixed order: the same bits on every run.
 #include "common.h"
+#include "embed_row.h"
 #include <type_traits>
-
-#define RQ_MAX_DEPTH 8
 
 // ---------------------------------------------------------------------------------------------
 // embedding of one step
 // ---------------------------------------------------------------------------------------------
-// One workgroup per row b; a thread owns float4 columns c, c + 1024, ...  The row's n ids are read from device memory (ids + b id_stride: a strided view
-// of the [B, T, D] codes the sampler writes, so the step follows the draws without a host read) and their embedding rows are added in ascending depth,
-// one rounding per addition, then the position row: the bits of rq_embed_seq_kernel's row for the same codes.  An id outside the table is clamped,
-// never followed.
+// One workgroup per row b.  The row's n ids are read from device memory (ids + b id_stride: a strided view of the [B, T, D] codes the sampler writes, so
+// the step follows the draws without a host read) and their embedding rows are added in ascending depth, one rounding per addition, then the position
+// row (embed_row.h): the bits of rq_embed_seq_kernel's row for the same codes.  An id outside the table is clamped, never followed.
 __global__ __launch_bounds__(256) void rq_embed_step_kernel(const float* __restrict__ table, const int64_t* __restrict__ ids, int64_t id_stride, int n,
                                                             const float* __restrict__ pos_row, int C, int V, float* __restrict__ out) {
   const int64_t b = blockIdx.x;
-  const float* rows[RQ_MAX_DEPTH];
-#pragma unroll
-  for (int j = 0; j < RQ_MAX_DEPTH; ++j) {
-    int64_t id = j < n ? ids[b * id_stride + j] : 0;
-    id = id < 0 ? 0 : (id >= V ? V - 1 : id);
-    rows[j] = table + id * C;
-  }
-  for (int c = threadIdx.x * 4; c < C; c += 1024) {
-    f32x4 run = *reinterpret_cast<const f32x4*>(rows[0] + c);
-#pragma unroll
-    for (int j = 1; j < RQ_MAX_DEPTH; ++j)
-      if (j < n) run = run + *reinterpret_cast<const f32x4*>(rows[j] + c);
-    *reinterpret_cast<f32x4*>(out + b * C + c) = run + *reinterpret_cast<const f32x4*>(pos_row + c);
-  }
+  rq_embed_row(table, ids + b * id_stride, n, pos_row, C, V, out + b * C);
 }
 
 extern "C" int enh_rq_embed_step(const float* table, const int64_t* ids, int64_t id_stride, int n, const float* pos_row, int B, int C, int V, float* out,

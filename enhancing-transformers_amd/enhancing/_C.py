@@ -161,10 +161,14 @@ SIGNATURES = {
     "enh_rq_embed_seq_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "enh_rq_embed_step": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp]),
     "enh_short_decode_attention": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    "enh_cursor_advance": (_i32, [_vp, _vp]),
+    "enh_decode_attention_at": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _i32, _vp]),
+    "enh_embed_step_at": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "enh_sample_logits_at": (_i32, [_vp, _i32, _i32, _f32, _i32, _f32, _u64, _u32, _vp, _i32, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp]),
 }
 
 _LIB = None
-ABI_VERSION = 29  # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 30 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -1391,3 +1395,79 @@ def short_decode_attention(qkv, k_cache, v_cache, t: int, out):
     _timed(None, 2.0 * qkv.element_size() * B * H * (int(t) + 1) * hs,
            lambda: _check(lib().enh_short_decode_attention(_p(qkv, dt, "qkv"), _p(k_cache, dt, "k_cache"), _p(v_cache, dt, "v_cache"), B, H, hs, Tmax, int(t),
                                                            _p(out, dt, "out"), _DT_OF[dt], _stream()), "enh_short_decode_attention"), unit="byte")
+
+
+# ------------------------------------------------------------------------------------------------
+# stage-2 sampling, the cursor forms (csrc/gpt_decode.hip): the loop's position t is a device int32 [1], so the launches of
+# one position can be captured into a HIP graph and replayed for the next.  No argument below depends on t.  Not timed per kernel: the graphed
+# sampler falls back to the eager loop while TIMER is set.
+# ------------------------------------------------------------------------------------------------
+def _cursor_ptr(cursor, who: str):
+    if not (torch.is_tensor(cursor) and cursor.is_cuda and cursor.dtype == torch.int32 and cursor.numel() == 1):
+        raise RuntimeError(f"{who}: cursor must be a device int32 tensor of one element")
+    return ctypes.c_void_p(cursor.data_ptr())
+
+
+def cursor_advance(cursor) -> None:
+    """cursor += 1 on the device (enh_cursor_advance)"""
+    _check(lib().enh_cursor_advance(_cursor_ptr(cursor, "cursor_advance"), _stream()), "enh_cursor_advance")
+
+
+def decode_attention_at(qkv, k_cache, v_cache, cursor, out, t_offset: int = 0) -> None:
+    """decode_attention at t = cursor + t_offset, read on the device (enh_decode_attention_at): its bits at the same t; t outside the cache:
+    nothing is read or written"""
+    B, H, Tmax, hs = k_cache.shape
+    if tuple(v_cache.shape) != (B, H, Tmax, hs) or tuple(qkv.shape) != (B, 3 * H * hs) or tuple(out.shape) != (B, H * hs):
+        raise RuntimeError(f"decode_attention_at: qkv {tuple(qkv.shape)} caches {tuple(k_cache.shape)} {tuple(v_cache.shape)} out {tuple(out.shape)} do not fit")
+    dt = qkv.dtype
+    if dt not in _DT_OF:
+        raise RuntimeError(f"decode_attention_at: dtype must be bf16, fp16 or f32, got {dt}")
+    L = lib()
+    ws = _workspace(L.enh_decode_attention_workspace_bytes(B, H, hs, Tmax), qkv.device)
+    _check(L.enh_decode_attention_at(_p(qkv, dt, "qkv"), _p(k_cache, dt, "k_cache"), _p(v_cache, dt, "v_cache"), B, H, hs, Tmax,
+                                     _cursor_ptr(cursor, "decode_attention_at"), int(t_offset), _p(out, dt, "out"), _p(ws), ws.numel(), _DT_OF[dt],
+                                     _stream()), "enh_decode_attention_at")
+
+
+def embed_step_at(table, ids, n: int, id_t_stride: int, id_offset: int, pos, pos_t_stride: int, pos_offset: int, cursor, t_lo: int, t_hi: int, out) -> None:
+    """the input row of a step at t = cursor (enh_embed_step_at): out[b] = sum_{j < n} table[ids[b].flat[t id_t_stride + id_offset + j]] (ascending j)
+    + pos.flat[t pos_t_stride + pos_offset .. + C).  ids: an int64 device view with one row per output row whose rows are contiguous (e.g. the
+    sampler's codes [B, T] or [B, T, D], or a chunk of their rows); pos: f32, contiguous (e.g. pos_emb_code[0]).  Every position of [t_lo, t_hi) must
+    stay inside a row of ids and inside pos (checked here); outside that range of positions the kernel does nothing."""
+    B, C = out.shape
+    if not (ids.is_cuda and ids.dtype == I64 and ids.dim() >= 2 and ids.shape[0] == B and ids[0].is_contiguous()):
+        raise RuntimeError("embed_step_at: ids must be an int64 device view with one contiguous row per output row")
+    if table.shape[1] != C or not 0 <= t_lo < t_hi:
+        raise RuntimeError(f"embed_step_at: table {tuple(table.shape)} does not fit out {tuple(out.shape)}, or no position in [{t_lo}, {t_hi})")
+    row = ids[0].numel()
+    for t in (t_lo, t_hi - 1):
+        if not (0 <= t * id_t_stride + id_offset and t * id_t_stride + id_offset + n <= row):
+            raise RuntimeError(f"embed_step_at: position {t} reads ids outside a row of {row}")
+        if not (0 <= t * pos_t_stride + pos_offset and t * pos_t_stride + pos_offset + C <= pos.numel()):
+            raise RuntimeError(f"embed_step_at: position {t} reads outside the {pos.numel()} position values")
+    _check(lib().enh_embed_step_at(_p(table, F32, "table"), ctypes.c_void_p(ids.data_ptr()), int(ids.stride(0)) if B > 1 else row, int(id_t_stride),
+                                   int(id_offset), int(n), _p(pos, F32, "pos"), int(pos_t_stride), int(pos_offset), _cursor_ptr(cursor, "embed_step_at"),
+                                   int(t_lo), int(t_hi), B, C, table.shape[0], _p(out, F32, "out"), _stream()), "enh_embed_step_at")
+
+
+def sample_logits_at(logits, codes, cursor, step_mul: int = 1, step_add: int = 0, temperature: float = 1.0, top_k=None, top_p=None, seed: int = 0,
+                     call: int = 0, row0: int = 0, logits_out=None) -> None:
+    """sample_logits at step = cursor * step_mul + step_add (enh_sample_logits_at): the code of row b goes to codes[b].flat[step], the filtered
+    logits to logits_out[b].flat[step V .. + V).  codes: an int64 device view with one contiguous row of n_steps codes per row of logits (the
+    sampler's [B, T] or [B, T, D]); logits_out: None or an f32 view with one contiguous row of n_steps V values per row.  A step outside
+    [0, n_steps) writes nothing."""
+    B, V = logits.shape
+    if not (codes.is_cuda and codes.dtype == I64 and codes.dim() >= 2 and codes.shape[0] == B and codes[0].is_contiguous()):
+        raise RuntimeError("sample_logits_at: codes must be an int64 device view with one contiguous row per row of logits")
+    n_steps = codes[0].numel()
+    lo_ptr, lo_stride = None, 0
+    if logits_out is not None:
+        if not (logits_out.is_cuda and logits_out.dtype == F32 and logits_out.dim() >= 2 and logits_out.shape[0] == B and logits_out[0].is_contiguous()
+                and logits_out[0].numel() == n_steps * V):
+            raise RuntimeError("sample_logits_at: logits_out must be an f32 device view with one contiguous row of n_steps * V values per row")
+        lo_ptr, lo_stride = ctypes.c_void_p(logits_out.data_ptr()), (int(logits_out.stride(0)) if B > 1 else n_steps * V)
+    _check(lib().enh_sample_logits_at(_p(logits, F32, "logits"), B, V, float(temperature), int(top_k) if top_k is not None else 0,
+                                      float(top_p) if top_p is not None else -1.0, int(seed) & (2 ** 64 - 1), int(call),
+                                      _cursor_ptr(cursor, "sample_logits_at"), int(step_mul), int(step_add), n_steps, int(row0),
+                                      ctypes.c_void_p(codes.data_ptr()), int(codes.stride(0)) if B > 1 else n_steps, lo_ptr, lo_stride, _stream()),
+           "enh_sample_logits_at")

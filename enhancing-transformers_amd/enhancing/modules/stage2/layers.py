@@ -18,8 +18,13 @@ depth sequences and the attention over B T sequences of D <= 8 slots are csrc/rq
 spatial / depth decode loop: both stacks run GPT's decode launches (prior.py `_block_step`), the spatial one under a cache of T slots, the depth
 one under a cache of D slots; a step's input row and the attention over the short cache are csrc/rq_decode.hip.
 
-Left out: an exact-f32 backward, more than one condition token, HIP-graph capture, relu^2 /
-LayerNorm fused into GEMM epilogues."""
+Both `sample` entries take `graph=` (None: ENH_GRAPHS == "1"): position 0 runs as above, then ONE position is captured into a
+HIP graph per chunk and replayed T - 1 times (prior.py `_sample_graphed`).  The captured launches take the position from a device int32, the
+cursor: the attention over the long cache, the step's input row and the draw have cursor forms (enh_decode_attention_at, enh_embed_step_at,
+enh_sample_logits_at) that run the bodies of their by-value siblings, and enh_cursor_advance ends the position.  The same bits as the loop.
+
+Left out: an exact-f32 backward, more than one condition token, HIP-graph capture of position 0 and of the teacher-forced entries, graphs kept
+from call to call, relu^2 / LayerNorm fused into GEMM epilogues."""
 import os
 from typing import Optional, Tuple
 
@@ -208,8 +213,12 @@ class GPT(Prior):
     @torch.no_grad()
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
                use_fp16: bool = True, *, seed: Optional[int] = None, forced_codes: Optional[torch.Tensor] = None, return_logits: bool = True,
-               call: int = 0, row_offset: int = 0) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+               call: int = 0, row_offset: int = 0, graph: Optional[bool] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """reference layers.py:213-266: returns (logits [B, T*V] after the temperature and the top-k mask, codes [B, T]).
+
+        graph=True replays every position after the first from ONE captured HIP graph per chunk: the launches of a position
+        in their cursor forms, which read the position from device memory; the same bits as the loop.  None reads ENH_GRAPHS == "1", False is the
+        loop.  Captured per call, nothing is cached between calls; while per-kernel timing is on (_C.TIMER) the loop runs.
 
         use_fp16=True runs the 16-bit operand format of ENH_PRECISION (default fp16) with f32 accumulation; False the exact mode (f32 operands on the vector ALU, f32 cache and
         row kernels).  The draw is an inverse-CDF walk in index order with one uniform per (seed, call, step, row_offset + row): the distribution of
@@ -234,6 +243,11 @@ class GPT(Prior):
         dt = self._operand_dtype(use_fp16, "GPT.sample")
         codes = torch.empty(B, T, dtype=torch.int64, device=dev)
         logits = torch.empty(B, T * V, dtype=torch.float32, device=dev) if return_logits else None
+        if self._use_graph(graph):
+            self._sample_graphed(B, dev, lambda b: self._decode_state(b, dt, dev), lambda st, s, e, positions: self._sample_rows_graphed(
+                st, positions, conds[s:e], codes[s:e], None if logits is None else logits[s:e], None if forced_codes is None else forced_codes[s:e],
+                top_k, top_p, float(softmax_temperature), seed, call, row_offset + s))
+            return logits, codes
         for s in range(0, B, MAX_BATCH):
             e = min(s + MAX_BATCH, B)
             self._sample_rows(conds[s:e], codes[s:e], None if logits is None else logits[s:e], None if forced_codes is None else forced_codes[s:e],
@@ -250,6 +264,23 @@ class GPT(Prior):
             _C.sample_logits(st["logits"], codes[:, t], temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, call=call, step=t, row0=row0,
                              logits_out=None if logits is None else logits[:, t * V:(t + 1) * V])
 
+    def _sample_rows_graphed(self, st, positions, conds, codes, logits, forced, top_k, top_p, temperature, seed, call, row0):
+        """_sample_rows for Prior._sample_graphed: position 0 as there, every later one the same launches in their cursor forms"""
+        from ... import _C
+        V = self.vocab_img_size
+        feed = codes if forced is None else forced
+        draw = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, call=call, row0=row0)
+
+        def first():
+            self._decode_step(st, 0, conds)
+            _C.sample_logits(st["logits"], codes[:, 0], step=0, logits_out=None if logits is None else logits[:, :V], **draw)
+
+        def later(cursor):
+            self._decode_step(st, None, feed, cursor=cursor)
+            _C.sample_logits_at(st["logits"], codes, cursor, logits_out=logits, **draw)
+
+        positions(self.img_num_tokens, first, later)
+
     def _decode_state(self, b: int, dt: torch.dtype, dev, cache_len: Optional[int] = None) -> dict:
         """the buffers of one chunk of b <= 64 rows: residual stream, activations, the step's logits and every layer's k / v cache [b, H, T, hs]"""
         f32, C, H = torch.float32, self.embed_dim, self.n_heads
@@ -259,17 +290,25 @@ class GPT(Prior):
                     logits=e(b, self.vocab_img_size, dtype=f32), caches=[(e(b, H, T, C // H), e(b, H, T, C // H)) for _ in self.blocks],
                     ops=self._operand_copies(dt))
 
-    def _decode_step(self, st: dict, t: int, ids: torch.Tensor) -> None:
-        """one token per row: ids (int64, on the device: the condition at t == 0, else the previous step's codes) -> st["logits"] [b, V] f32"""
+    def _decode_step(self, st: dict, t: Optional[int], ids: torch.Tensor, cursor: Optional[torch.Tensor] = None) -> None:
+        """one token per row: ids (int64, on the device: the condition at t == 0, else the previous step's codes) -> st["logits"] [b, V] f32.
+        The cursor form (cursor: device int32 [1], t is None): the step t >= 1 the cursor holds; ids is then the whole [b, T] tensor of the codes
+        that are fed forward, whose column t - 1 the embedding reads on the device."""
         from ... import _C
         x, x2, a, qkv, att, hid = st["x"], st["x2"], st["a"], st["qkv"], st["att"], st["hid"]
         linear = _C.skinny_gemm_f32 if st["dt"] == torch.float32 else _C.skinny_gemm
-        if t == 0:
-            _C.gpt_embed(self.tok_emb_cond.weight.detach(), ids, self.pos_emb_cond.detach()[0, 0], x)
+        if cursor is not None:
+            C = self.embed_dim
+            _C.embed_step_at(self.tok_emb_code.weight.detach(), ids, 1, 1, -1, self.pos_emb_code.detach()[0], C, -C, cursor, 1, self.img_num_tokens, x)
+            attend = lambda q, kc, vc, o: _C.decode_attention_at(q, kc, vc, cursor, o)
         else:
-            _C.gpt_embed(self.tok_emb_code.weight.detach(), ids, self.pos_emb_code.detach()[0, t - 1], x)
+            if t == 0:
+                _C.gpt_embed(self.tok_emb_cond.weight.detach(), ids, self.pos_emb_cond.detach()[0, 0], x)
+            else:
+                _C.gpt_embed(self.tok_emb_code.weight.detach(), ids, self.pos_emb_code.detach()[0, t - 1], x)
+            attend = lambda q, kc, vc, o: _C.decode_attention(q, kc, vc, t, o)
         for blk, W, (kc, vc) in zip(self.blocks, st["ops"]["layers"], st["caches"]):
-            _block_step(blk, W, linear, lambda q, o: _C.decode_attention(q, kc, vc, t, o), x, x2, a, qkv, att, hid)
+            _block_step(blk, W, linear, lambda q, o: attend(q, kc, vc, o), x, x2, a, qkv, att, hid)
         _C.row_ln_scale(x, self.layer_norm.weight, self.layer_norm.bias, a, eps=self.layer_norm.eps)
         linear(a, st["ops"]["head"], st["logits"])
 
@@ -527,7 +566,7 @@ class RQTransformer(Prior):
     @torch.no_grad()
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
                use_fp16: bool = True, *, seed: Optional[int] = None, forced_codes: Optional[torch.Tensor] = None, return_logits: bool = True,
-               call: int = 0, row_offset: int = 0, slot0_ln: str = "once") -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+               call: int = 0, row_offset: int = 0, slot0_ln: str = "once", graph: Optional[bool] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """reference layers.py:397-547 (sample, sample_spatial_step, sample_depth_step) with one condition token: returns (logits [B T, D, V] f32
         after the temperature and the top-k mask, codes [B, T, D] int64).  GPT.sample's contract: the loop is restated per
         step, one row per batch element.  Per position t the spatial Blocks run under a cache of T slots on the input row
@@ -551,7 +590,12 @@ class RQTransformer(Prior):
         generator.  forced_codes [B, T, D] are fed forward instead of the draws (codes are still drawn and returned).  Batches above 64 rows run in
         chunks of 64 rows; a chunk equals a separate call with its `row_offset`.  Nothing in the loop reads a device value on the host.  The depth
         transformer's attention is enh_short_decode_attention; ENH_RQ_DEPTH_DECODE=cache runs enh_decode_attention at Tmax = D instead (A/B only).
-        Device tensors only.  Side effect: a module whose parameters are not on the device of `conds` is moved there."""
+        Device tensors only.  Side effect: a module whose parameters are not on the device of `conds` is moved there.
+
+        graph=True replays every position after the first from ONE captured HIP graph per chunk: the spatial step, the D depth
+        steps and their draws, with the spatial attention, the input rows and the draws in their cursor forms (the depth attention keeps its
+        constant slot d); the same bits as the loop.  None reads ENH_GRAPHS == "1", False is the loop.  Captured per call, nothing is cached between
+        calls; while per-kernel timing is on (_C.TIMER) the loop runs."""
         if not (torch.is_tensor(conds) and conds.is_cuda):
             raise NotImplementedError("RQTransformer.sample: sampling runs on a ROCm device only: conds must be a device tensor (the spatial / depth "
                                       "decode loop is HIP kernels: there is no CPU path)")
@@ -580,6 +624,12 @@ class RQTransformer(Prior):
         dt = self._operand_dtype(use_fp16, "RQTransformer.sample")
         codes = torch.empty(B, T, D, dtype=torch.int64, device=dev)
         logits = torch.empty(B * T, D, V, dtype=torch.float32, device=dev) if return_logits else None
+        if self._use_graph(graph):
+            self._sample_graphed(B, dev, lambda b: self._decode_state(b, dt, dev), lambda st, s, e, positions: self._sample_rows_graphed(
+                st, positions, conds[s:e], codes[s:e], None if logits is None else logits.view(B, T, D, V)[s:e],
+                None if forced_codes is None else forced_codes[s:e], top_k, top_p, float(softmax_temperature), seed, call, row_offset + s,
+                slot0_ln == "twice", depth_decode == "cache"))
+            return logits, codes
         for s in range(0, B, MAX_BATCH):
             e = min(s + MAX_BATCH, B)
             self._sample_rows(conds[s:e], codes[s:e], None if logits is None else logits.view(B, T, D, V)[s:e],
@@ -611,29 +661,66 @@ class RQTransformer(Prior):
                 _C.sample_logits(st["logits"], codes[:, t, d], temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, call=call, step=t * D + d,
                                  row0=row0, logits_out=None if logits is None else logits[:, t, d, :])
 
-    def _spatial_step(self, st: dict, t: int, ids: torch.Tensor) -> None:
+    def _sample_rows_graphed(self, st, positions, conds, codes, logits, forced, top_k, top_p, temperature, seed, call, row0, ln_twice: bool,
+                             depth_cache: bool):
+        """_sample_rows for Prior._sample_graphed: position 0 as there, every later one the same launches with the spatial attention, the input
+        rows and the draws in their cursor forms"""
+        from ... import _C
+        D = self.depth_num_tokens
+        feed = codes if forced is None else forced
+        draw = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, call=call, row0=row0)
+
+        def first():
+            self._spatial_step(st, 0, conds)
+            for d in range(D):
+                self._depth_step(st, 0, d, None if d == 0 else feed[:, 0, :d], ln_twice, depth_cache)
+                _C.sample_logits(st["logits"], codes[:, 0, d], step=d, logits_out=None if logits is None else logits[:, 0, d, :], **draw)
+
+        def later(cursor):
+            self._spatial_step(st, None, feed, cursor=cursor)
+            for d in range(D):
+                self._depth_step(st, None, d, None if d == 0 else feed, ln_twice, depth_cache, cursor=cursor)
+                _C.sample_logits_at(st["logits"], codes, cursor, step_mul=D, step_add=d, logits_out=logits, **draw)
+
+        positions(self.img_num_tokens, first, later)
+
+    def _spatial_step(self, st: dict, t: Optional[int], ids: torch.Tensor, cursor: Optional[torch.Tensor] = None) -> None:
         """position t of the spatial transformer, one row per batch element: ids (int64, on the device: the condition [b] at t == 0, else the D
-        codes [b, D] of position t - 1) -> ln_spatial of the stack's output in st["xd"] [b, C] f32, the input row of depth slot 0"""
+        codes [b, D] of position t - 1) -> ln_spatial of the stack's output in st["xd"] [b, C] f32, the input row of depth slot 0.
+        The cursor form (cursor: device int32 [1], t is None): the position t >= 1 the cursor holds; ids is then the whole [b, T, D] tensor of the
+        codes that are fed forward, whose row t - 1 the embedding reads on the device."""
         from ... import _C
         x, x2, a, qkv, att, hid = st["xs"], st["x2"], st["a"], st["qkv"], st["att"], st["hid"]
         linear = _C.skinny_gemm_f32 if st["dt"] == torch.float32 else _C.skinny_gemm
-        if t == 0:
-            _C.gpt_embed(self.tok_emb_cond.weight.detach(), ids, self.pos_emb_cond.detach()[0, 0], x)
+        if cursor is not None:
+            C, D = self.embed_dim, self.depth_num_tokens
+            _C.embed_step_at(self.tok_emb_code.weight.detach(), ids, D, D, -D, self.pos_emb_code.detach()[0], C, -C, cursor, 1, self.img_num_tokens, x)
+            attend = lambda q, kc, vc, o: _C.decode_attention_at(q, kc, vc, cursor, o)
         else:
-            _C.rq_embed_step(self.tok_emb_code.weight.detach(), ids, self.pos_emb_code.detach()[0, t - 1], x)
+            if t == 0:
+                _C.gpt_embed(self.tok_emb_cond.weight.detach(), ids, self.pos_emb_cond.detach()[0, 0], x)
+            else:
+                _C.rq_embed_step(self.tok_emb_code.weight.detach(), ids, self.pos_emb_code.detach()[0, t - 1], x)
+            attend = lambda q, kc, vc, o: _C.decode_attention(q, kc, vc, t, o)
         for blk, W, (kc, vc) in zip(self.spatial_transformer, st["ops"]["spatial"], st["spatial"]):
-            _block_step(blk, W, linear, lambda q, o: _C.decode_attention(q, kc, vc, t, o), x, x2, a, qkv, att, hid)
+            _block_step(blk, W, linear, lambda q, o: attend(q, kc, vc, o), x, x2, a, qkv, att, hid)
         _C.row_ln_scale(x, self.ln_spatial.weight, self.ln_spatial.bias, st["xd"], eps=self.ln_spatial.eps)
 
-    def _depth_step(self, st: dict, t: int, d: int, ids: Optional[torch.Tensor], ln_twice: bool, depth_cache: bool) -> None:
+    def _depth_step(self, st: dict, t: Optional[int], d: int, ids: Optional[torch.Tensor], ln_twice: bool, depth_cache: bool,
+                    cursor: Optional[torch.Tensor] = None) -> None:
         """slot d of position t of the depth transformer: the input row is st["xd"] as _spatial_step left it (d == 0), else built from ids
         (int64 [b, d] on the device: codes 0 .. d - 1 of the position) -> st["logits"] [b, V] f32.  Slot d of the depth caches is overwritten
-        and slots > d are never read: the caches need no reset between positions."""
+        and slots > d are never read: the caches need no reset between positions.  The cursor form (cursor: device int32 [1], t is None): ids is
+        the whole [b, T, D] tensor of the codes that are fed forward, whose row t the embedding reads on the device; the attention's slot d is a
+        constant of the launch either way."""
         from ... import _C
         x, x2, a, qkv, att, hid = st["xd"], st["x2"], st["a"], st["qkv"], st["att"], st["hid"]
         linear = _C.skinny_gemm_f32 if st["dt"] == torch.float32 else _C.skinny_gemm
         attend = _C.decode_attention if depth_cache else _C.short_decode_attention
-        if d > 0:
+        if d > 0 and cursor is not None:
+            D = self.depth_num_tokens
+            _C.embed_step_at(self.tok_emb_code.weight.detach(), ids, d, D, 0, self.pos_emb_depth.detach()[0, d - 1], 0, 0, cursor, 0, self.img_num_tokens, x)
+        elif d > 0:
             _C.rq_embed_step(self.tok_emb_code.weight.detach(), ids, self.pos_emb_depth.detach()[0, d - 1], x)
         for blk, W, (kc, vc) in zip(self.depth_transformer, st["ops"]["depth"], st["depth"]):
             _block_step(blk, W, linear, lambda q, o: attend(q, kc, vc, d, o), x, x2, a, qkv, att, hid)

@@ -197,6 +197,8 @@ class Prior(nn.Module):
         self._arena = None        # set by engine/optim.py GPTAdam: dict(dt, ptrs, ops, versions, refresh) — the operand arena its step kernel keeps current
         self._grad_key = None     # the parameters whose .grad are views into flat_grad
         self.flat_grad = None
+        self._sample_stream = None    # sample(graph=True): the side stream its chunks are captured and replayed on
+        self._sample_keep = None      # ... and what the last call's graphs point at (_sample_graphed)
 
     def _init_weights(self, module: nn.Module) -> None:
         if isinstance(module, (nn.Linear, nn.Embedding)):
@@ -301,6 +303,53 @@ class Prior(nn.Module):
                 p.grad = self.flat_grad[o:o + n].view(p.shape)
             self._grad_key = key
         return self.flat_grad
+
+    # ---- sampling: one captured position, replayed ------------------------------------------------------
+    @staticmethod
+    def _use_graph(graph) -> bool:
+        """sample(graph=): None reads ENH_GRAPHS == "1" (the stage-1 engine's switch), anything else is the caller's choice.  While per-kernel
+        timing is on (_C.TIMER) the answer is False: a replay runs no host code to time (as engine/stage1.py forward_backward_graphed)."""
+        from ... import _C
+        use = os.environ.get("ENH_GRAPHS", "0") == "1" if graph is None else bool(graph)
+        return use and _C.TIMER is None
+
+    def _sample_graphed(self, B: int, dev, make_state, run_chunk) -> None:
+        """sample(graph=True): the chunks of <= MAX_BATCH rows, each as position 0 and one captured position.  run_chunk(st, s, e, positions) runs
+        rows s .. e - 1 in the buffers st = make_state(e - s) by calling positions(T, first, later): first() runs eagerly (it embeds the condition,
+        and it warms the launches and their workspaces), the cursor (device int32) is set to 1, later(cursor), the launches of one position in
+        their cursor forms, is captured once with enh_cursor_advance behind it, and the graph is replayed T - 1 times.  Everything runs on one
+        side stream, so the graph is a chain; the current stream waits for it at the end.  Nothing is kept from call to call but what a replay
+        that may still be running points at: the graphs, their cursors, the chunk buffers and the workspaces of the launches (`_sample_keep`),
+        until the next call replaces them."""
+        from ... import _C
+        cur = torch.cuda.current_stream(dev)
+        side = self._sample_stream
+        if side is None or side.device != dev:
+            side = self._sample_stream = torch.cuda.Stream(dev)
+        keep, states = [], {}
+
+        def positions(T, first, later):
+            first()
+            if T == 1:
+                return
+            cursor = torch.ones(1, dtype=torch.int32, device=dev)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                later(cursor)
+                _C.cursor_advance(cursor)
+            for _ in range(T - 1):
+                g.replay()
+            keep.append((g, cursor))
+
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            for s in range(0, B, MAX_BATCH):
+                e = min(s + MAX_BATCH, B)
+                if e - s not in states:       # chunks of one size share their buffers: the stream orders them
+                    states[e - s] = make_state(e - s)
+                run_chunk(states[e - s], s, e, positions)
+        cur.wait_stream(side)
+        self._sample_keep = (keep, states, list(_C._WS.values()), list(_C._GEMM_WS.values()))
 
     # ---- the teacher-forced driver ------------------------------------------------------------------
     def _teacher_forced(self, who: str, codes, conds, use_fp16: bool, return_loss: bool, why: str):

@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 29  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 30  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -682,6 +682,35 @@ int enh_rq_embed_step(const float* table, const int64_t* ids, int64_t id_stride,
  * neither read nor written) for a cache of Tmax <= 8 slots (else ENH_E_SHAPE): eight lanes own a (row, head) pair and a workgroup 32 pairs,
  * nothing staged in LDS, no workspace.  dtype ENH_DT_BF16 | ENH_DT_F16 | ENH_DT_F32; hs a multiple of 64 up to 384. */
 int enh_short_decode_attention(const void* qkv, void* k_cache, void* v_cache, int B, int H, int hs, int Tmax, int t, void* out, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 sampling, the cursor forms (csrc/gpt_decode.hip; the input row's body: csrc/embed_row.h).  The position t of the sampling loop is one int32 in device memory,
+ * the cursor, and no argument of these entries depends on t: the launches of one position, captured once into a HIP graph, are replayed for every
+ * later position.  Each entry runs the body of its by-value sibling above and gives its bits at the same t.  The cursor is read, never checked on
+ * the host: a position outside an entry's range makes every workgroup return without reading or writing anything.
+ * ------------------------------------------------------------------------------------------------ */
+/* *cursor += 1 (one thread) */
+int enh_cursor_advance(int* cursor, void* stream);
+/* enh_decode_attention at t = *cursor + t_offset.  The split plan is worked out on the device from t + 1 by the host's function, the grid covers the
+ * (Tmax + 63) / 64 pieces the longest plan can have (workgroups past the plan return), and the merge kernel is always launched (it returns under a
+ * plan of one piece).  workspace: at least enh_decode_attention_workspace_bytes(B, H, hs, Tmax), always required.  t outside [0, Tmax): nothing is
+ * read or written. */
+int enh_decode_attention_at(const void* qkv, void* k_cache, void* v_cache, int B, int H, int hs, int Tmax, const int* cursor, int t_offset, void* out,
+                            void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* The input row of a step at t = *cursor: out[b] = (((e_0 + e_1) + ...) + e_{n-1}) + pos_base[t pos_t_stride + pos_offset .. + C) with
+ * e_j = table[ids_base[b id_row_stride + t id_t_stride + id_offset + j]], b < B, 1 <= n <= 8: enh_rq_embed_step's bits, and at n == 1 enh_gpt_embed's.
+ * Strides and offsets count elements; offsets may be negative (the codes of position t - 1) as long as positions t_lo and t_hi - 1 stay at or
+ * behind the bases; pos_t_stride and pos_offset are multiples of 4.  t outside [t_lo, t_hi): nothing is read or written.  Ids outside the table
+ * are clamped. */
+int enh_embed_step_at(const float* table, const int64_t* ids_base, int64_t id_row_stride, int64_t id_t_stride, int64_t id_offset, int n,
+                      const float* pos_base, int64_t pos_t_stride, int64_t pos_offset, const int* cursor, int t_lo, int t_hi, int B, int C, int V,
+                      float* out, void* stream);
+/* enh_sample_logits at step = *cursor * step_mul + step_add, with the Philox uniform of (seed, call, step, row0 + row): the code of row b goes to
+ * codes_base[b code_row_stride + step] and, when logits_base is given, the filtered logits to logits_base[b logits_row_stride + step V .. + V).
+ * step outside [0, n_steps): nothing is read or written (code_row_stride >= n_steps, logits_row_stride >= n_steps V). */
+int enh_sample_logits_at(const float* logits, int B, int V, float temperature, int top_k, float top_p, uint64_t seed, uint32_t call, const int* cursor,
+                         int step_mul, int step_add, int n_steps, int64_t row0, int64_t* codes_base, int64_t code_row_stride, float* logits_base,
+                         int64_t logits_row_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stage-2 GPT, backward of the teacher-forced forward (csrc/gpt_attn_bwd.hip: the attention, csrc/gpt_rows.hip: the row kernels).  The gradient

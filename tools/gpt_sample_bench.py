@@ -6,7 +6,10 @@ fp16 restatement of the same step (torch.matmul / F.layer_norm / softmax on a pr
 step must move (every GEMM weight once + the cache up to t + the activations) over the time, as a share of the 6.29 TB/s that a plain copy reaches on
 MI355X.  The same share for the skinny GEMM and the decode attention alone, and the time of a whole 1024-step sample at batch 4.
 Timing: HIP events around a window of back-to-back calls (10 steps; 100 kernel launches over rotating operand buffers larger than the last-level
-cache), median, minimum and maximum of 7 windows that alternate between the two paths, after a warm-up."""
+cache), median, minimum and maximum of 7 windows that alternate between the two paths, after a warm-up.
+
+--graph writes profiles/gpt_sample_graph.txt instead: the eager loop against replays of one captured position (sample(graph=True)) at batch 1 and 4
+(tools/sample_graph_bench.py)."""
 import argparse
 import math
 import os
@@ -81,18 +84,80 @@ class TorchStep:
         return torch.multinomial(torch.softmax(logits, -1), 1)
 
 
+def graph_mode(m, L, out):
+    """--graph: the eager loop against replays of one captured position (sample(graph=True)) at batch 1 and 4 and the cache fills
+    of the table above; writes profiles/gpt_sample_graph.txt"""
+    import sample_graph_bench as SG
+    C, V, T = m.embed_dim, m.vocab_img_size, m.img_num_tokens
+    dt, count = torch.float16, 10
+    lines = [f"stage-2 GPT sampling, eager loop against replays of one captured position, on {torch.cuda.get_device_name(0)}: C={C} layers={L} "
+             f"heads={m.n_heads} V={V} T={T}, fp16 operands, top_k 100, logits returned",
+             f"ms per position: mean [min .. max] of 5 windows of {count} consecutive positions per path, the paths alternating, after a warm-up window of "
+             "both; host clock around work that ends in a device synchronise",
+             f"{'batch':>5} {'cache':>5} {'eager ms [min .. max]':>28} {'graph ms [min .. max]':>28} {'eager/graph':>11} {'beyond spread':>13} {'capture ms':>10} "
+             f"{'nodes':>6} {'bit-equal':>9}"]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for b in (1, 4):
+            st = m._decode_state(b, dt, "cuda")
+            for kc, vc in st["caches"]:
+                kc.normal_(0, 0.5)
+                vc.normal_(0, 0.5)
+            forced = torch.randint(0, V, (b, T), device="cuda")
+            outs = {k: (torch.zeros(b, T, dtype=torch.int64, device="cuda"), torch.zeros(b, T * V, device="cuda")) for k in ("eager", "graph")}
+            draw = dict(temperature=1.0, top_k=100, top_p=None, seed=1, call=0, row0=0)
+
+            def eager(t):
+                codes, logits = outs["eager"]
+                m._decode_step(st, t, forced[:, t - 1])
+                _C.sample_logits(st["logits"], codes[:, t], step=t, logits_out=logits[:, t * V:(t + 1) * V], **draw)
+
+            def later(cursor):
+                codes, logits = outs["graph"]
+                m._decode_step(st, None, forced, cursor=cursor)
+                _C.sample_logits_at(st["logits"], codes, cursor, logits_out=logits, **draw)
+
+            eager(1)      # warms the launches and their workspaces on this stream, as position 0 does in sample()
+            g, cursor, cap_s, nodes = SG.capture_position(later, "cuda")
+            for n in (1, 512, 1024):
+                first = max(1, min(n - 1, T - count))
+                e, r = SG.eager_against_graph(eager, g, cursor, first, count)
+                sl = slice(first, first + count)
+                same = all(SG.same_bits(a.view(b, T, -1)[:, sl], c.view(b, T, -1)[:, sl]) for a, c in zip(outs["eager"], outs["graph"]))
+                assert same, f"graph and eager differ at batch {b}, positions {first} .. {first + count - 1}"
+                assert int(cursor.item()) == first + count
+                lines.append(f"{b:>5} {n:>5} {SG.fmt(e):>28} {SG.fmt(r):>28} {e[0] / r[0]:>11.3f} {'yes' if r[2] < e[1] else 'no':>13} {cap_s * 1e3:>10.1f} "
+                             f"{'n/a' if nodes is None else nodes:>6} {'yes':>9}")
+            del st, g, outs
+            torch.cuda.empty_cache()
+    torch.cuda.current_stream().wait_stream(side)
+    lines.append("beyond spread: the slowest graph window is faster than the fastest eager window of the same point")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gpt_sample.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--layers", type=int, default=24)
     ap.add_argument("--whole", type=int, default=1, help="also time a whole 1024-step sample at batch 4")
+    ap.add_argument("--graph", action="store_true", help="instead of the tables: the eager loop against replays of one captured position "
+                    "(profiles/gpt_sample_graph.txt)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "gpt_sample_graph.txt" if args.graph else "gpt_sample.txt")
     C, H, V, T, L = 6144, 16, 8192, 1024, args.layers
     torch.manual_seed(0)
     with torch.device("cuda"):
         m = GPT(vocab_cond_size=1000, vocab_img_size=V, embed_dim=C, cond_num_tokens=1, img_num_tokens=T, n_heads=H, n_layers=L)
         with torch.no_grad():
             m.pos_emb_code.normal_(0, 0.02)
+    if args.graph:
+        return graph_mode(m, L, args.out)
     dt = torch.float16
     wbytes = (12 * C * C * L + V * C) * 2
     lines = [f"stage-2 sampling step on {torch.cuda.get_device_name(0)}: C={C} layers={L} heads={H} V={V}, fp16 operands; weights {wbytes / 1e9:.2f} GB per step",

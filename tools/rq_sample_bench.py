@@ -9,7 +9,10 @@ python tools/rq_sample_bench.py [--out FILE] [--spatial_layers N]
    on the model's own operand copies; launches per position, the GEMM weight bytes a position must read over its time against the rate of a plain
    copy, and the seconds per image extrapolated from the fills.
 Timing: HIP events around a window of back-to-back calls; median, minimum and maximum of 7 windows that alternate between the paths, after a warm-up
-of every path.  Not 1024 positions: a few positions per fill."""
+of every path.  Not 1024 positions: a few positions per fill.
+
+--graph writes profiles/rq_sample_graph.txt instead: the eager loop against replays of one captured position (sample(graph=True)) at batch 1 and 4 and
+the same fills (tools/sample_graph_bench.py), then one whole image through sample() both ways."""
 import argparse
 import math
 import os
@@ -109,14 +112,104 @@ def launches_per_position(b, C, V, D, Ls, Ld, t):
     return spatial, depth
 
 
+def graph_mode(kw, out, whole: bool):
+    """--graph: the eager loop against replays of one captured position (sample(graph=True)) at batch 1 and 4 and the cache fills
+    of the table above, then one whole image through the public entry both ways; writes profiles/rq_sample_graph.txt"""
+    import time
+    import sample_graph_bench as SG
+    C, V, T, D = kw["embed_dim"], kw["vocab_img_size"], kw["img_num_tokens"], kw["depth_num_tokens"]
+    Ls, Ld = kw["spatial_n_layers"], kw["depth_n_layers"]
+    dt, count = torch.float16, 10
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        m = RQTransformer(**kw)
+        with torch.no_grad():
+            for p in (m.pos_emb_cond, m.pos_emb_code, m.pos_emb_depth):
+                p.normal_(0, 0.02)
+    wb = (12 * C * C * Ls + D * (12 * C * C * Ld + V * C)) * 2
+    lines = [f"stage-2 RQTransformer sampling, eager loop against replays of one captured position, on {torch.cuda.get_device_name(0)}: C={C} "
+             f"spatial layers={Ls} depth layers={Ld} T={T} D={D} V={V}, fp16 operands, top_k 100, logits returned",
+             f"ms per position: mean [min .. max] of 5 windows of {count} consecutive positions per path, the paths alternating, after a warm-up window of "
+             "both; host clock around work that ends in a device synchronise",
+             f"GEMM weights read per position {wb / 1e9:.3f} GB: {wb / COPY_TBS / 1e9:.3f} ms at the {COPY_TBS} TB/s of a plain copy",
+             f"{'batch':>5} {'slot':>5} {'eager ms [min .. max]':>28} {'graph ms [min .. max]':>28} {'eager/graph':>11} {'beyond spread':>13} {'capture ms':>10} "
+             f"{'nodes':>6} {'launches':>8} {'bit-equal':>9}"]
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for b in (1, 4):
+            st = m._decode_state(b, dt, "cuda")
+            for kc, vc in st["spatial"] + st["depth"]:
+                kc.normal_(0, 0.5)
+                vc.normal_(0, 0.5)
+            forced = torch.randint(0, V, (b, T, D), device="cuda")
+            outs = {k: (torch.zeros(b, T, D, dtype=torch.int64, device="cuda"), torch.zeros(b, T, D, V, device="cuda")) for k in ("eager", "graph")}
+            draw = dict(temperature=1.0, top_k=100, top_p=None, seed=1, call=0, row0=0)
+
+            def eager(t):
+                codes, logits = outs["eager"]
+                m._spatial_step(st, t, forced[:, t - 1, :])
+                for d in range(D):
+                    m._depth_step(st, t, d, None if d == 0 else forced[:, t, :d], False, False)
+                    _C.sample_logits(st["logits"], codes[:, t, d], step=t * D + d, logits_out=logits[:, t, d, :], **draw)
+
+            def later(cursor):
+                codes, logits = outs["graph"]
+                m._spatial_step(st, None, forced, cursor=cursor)
+                for d in range(D):
+                    m._depth_step(st, None, d, None if d == 0 else forced, False, False, cursor=cursor)
+                    _C.sample_logits_at(st["logits"], codes, cursor, step_mul=D, step_add=d, logits_out=logits, **draw)
+
+            eager(1)      # warms the launches and their workspaces on this stream, as position 0 does in sample()
+            g, cursor, cap_s, nodes = SG.capture_position(later, "cuda")
+            for slot in (1, 256, 512, T - 1):
+                first = min(slot, T - count)
+                e, r = SG.eager_against_graph(eager, g, cursor, first, count)
+                same = all(SG.same_bits(a[:, first:first + count], c[:, first:first + count]) for a, c in zip(outs["eager"], outs["graph"]))
+                assert same, f"graph and eager differ at batch {b}, positions {first} .. {first + count - 1}"
+                assert int(cursor.item()) == first + count
+                n_sp, n_dp = launches_per_position(b, C, V, D, Ls, Ld, first + count - 1)
+                lines.append(f"{b:>5} {slot:>5} {SG.fmt(e):>28} {SG.fmt(r):>28} {e[0] / r[0]:>11.3f} {'yes' if r[2] < e[1] else 'no':>13} {cap_s * 1e3:>10.1f} "
+                             f"{'n/a' if nodes is None else nodes:>6} {n_sp + n_dp:>8} {'yes':>9}")
+            del st, g, outs
+            torch.cuda.empty_cache()
+    torch.cuda.current_stream().wait_stream(side)
+    lines += ["beyond spread: the slowest graph window is faster than the fastest eager window of the same point",
+              "launches: the eager loop's kernel launches of a position at the window's last slot (the graph always holds the attention's merge node)"]
+    if whole:
+        conds = torch.randint(0, kw["vocab_cond_size"], (1, 1), device="cuda")
+        res, secs = {}, {}
+        for graph in (False, True, False, True):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res[graph] = m.sample(conds, top_k=100, seed=1, graph=graph)
+            torch.cuda.synchronize()
+            secs.setdefault(graph, []).append(time.perf_counter() - t0)
+        assert SG.same_bits(res[False][1], res[True][1]) and SG.same_bits(res[False][0], res[True][0]), "whole image: graph and eager differ"
+        lines.append(f"whole image through sample(), batch 1, {T} positions x {D} codes, top_k 100, two calls each, alternating: eager "
+                     f"{secs[False][0]:.2f} s, {secs[False][1]:.2f} s; graph (with its capture) {secs[True][0]:.2f} s, {secs[True][1]:.2f} s; codes and logits bit-equal: yes")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rq_sample.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--spatial_layers", type=int, default=None)
+    ap.add_argument("--graph", action="store_true", help="instead of the tables: the eager loop against replays of one captured position "
+                    "(profiles/rq_sample_graph.txt)")
+    ap.add_argument("--whole", type=int, default=1, help="--graph: also draw one whole image through sample() both ways")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "rq_sample_graph.txt" if args.graph else "rq_sample.txt")
     kw = dict(get_config_from_file(os.path.join(ROOT, "configs", "imagenet_rqtransformer_rqvae_base.yaml")).model.params.transformer.params)
     if args.spatial_layers is not None:
         kw["spatial_n_layers"] = args.spatial_layers
+    if args.graph:
+        return graph_mode(kw, args.out, bool(args.whole))
     C, V, T, D = kw["embed_dim"], kw["vocab_img_size"], kw["img_num_tokens"], kw["depth_num_tokens"]
     Hs, Hd, Ls, Ld = kw["spatial_n_heads"], kw["depth_n_heads"], kw["spatial_n_layers"], kw["depth_n_layers"]
     dt = torch.float16

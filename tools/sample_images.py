@@ -27,6 +27,8 @@ def main(argv=None):
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp32", action="store_true", help="the exact mode (use_fp16=False)")
+    ap.add_argument("--graph", action="store_true", help="replay every position after the first from one captured HIP graph (sample(graph=True): "
+                    "the same codes); without it ENH_GRAPHS=1 decides")
     ap.add_argument("--nrow", type=int, default=4)
     ap.add_argument("--out", default="samples.png")
     args = ap.parse_args(argv)
@@ -37,7 +39,8 @@ def main(argv=None):
     if args.ckpt:
         model.init_from_ckpt(args.ckpt)
     conds = torch.tensor(args.classes, dtype=torch.int64, device="cuda")
-    img = model.sample(conds, top_k=args.top_k, top_p=args.top_p, softmax_temperature=args.temperature, use_fp16=not args.fp32, seed=args.seed)
+    img = model.sample(conds, top_k=args.top_k, top_p=args.top_p, softmax_temperature=args.temperature, use_fp16=not args.fp32, seed=args.seed,
+                       graph=True if args.graph else None)
     from PIL import Image
     grid = make_grid(img.float().cpu(), nrow=args.nrow)
     Image.fromarray((grid.permute(1, 2, 0).numpy() * 255).astype(np.uint8)).save(args.out)
