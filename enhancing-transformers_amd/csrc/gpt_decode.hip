@@ -21,10 +21,9 @@
 // Each is a kernel of its own name around the __device__ body of its by-value sibling: the same arithmetic, the same bits.
 #include "common.h"
 #include "embed_row.h"
+#include "skinny_gemm.h"
 #include <type_traits>
 
-#define GD_MAX_M 64
-#define GD_MAX_SPLITS 32
 #define GD_ATT_PIECE 256      // cache slots per workgroup of the decode attention (its scores live in LDS)
 #define GD_ATT_MAX_T 8192
 #define GD_SAMPLE_MAX_V 16384
@@ -33,18 +32,6 @@
 // ---------------------------------------------------------------------------------------------
 // skinny GEMM
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float gd_epilogue(float v, int64_t m, int64_t n, int64_t N, const float* __restrict__ bias, int act, const float* __restrict__ res) {
-  if (bias) v += bias[n];
-  if (act) { v = fmaxf(v, 0.f); v = v * v; }
-  if (res) v += res[m * N + n];
-  return v;
-}
-template <typename OT>
-__device__ __forceinline__ void gd_store(float v, int64_t i, float* __restrict__ out_f32, uint16_t* __restrict__ out_h16) {
-  if (out_f32) out_f32[i] = v;
-  if (out_h16) out_h16[i] = pack1<OT>(v);
-}
-
 // One workgroup = 16 rows of W; wave w takes the 128-wide K chunks w, w + 4, ... of the workgroup's K slice.  v_mfma_f32_16x16x32: lane (r = lane % 16,
 // q = lane / 16) supplies row r, k = 8 q .. 8 q + 7 of a 32-wide step, so ONE load instruction reads 64 contiguous bytes of each of the 16 rows
 // (whole 64-byte sectors: a 32-row fragment of the 32x32x16 form reads 32 bytes per row and instruction and measured 2 TB/s), four are in flight
@@ -111,25 +98,7 @@ template <typename OT>
 __global__ __launch_bounds__(256) void gpt_skinny_reduce_kernel(const float* __restrict__ part, int splits, int M, int N, const float* __restrict__ bias,
                                                                 int act, const float* __restrict__ res, float* __restrict__ out_f32,
                                                                 uint16_t* __restrict__ out_h16) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t MN = (int64_t)M * N;
-  if (i >= MN) return;
-  float v = part[i];
-  for (int s = 1; s < splits; ++s) v += part[(int64_t)s * MN + i];
-  const int64_t m = i / N, n = i - m * N;
-  gd_store<OT>(gd_epilogue(v, m, n, N, bias, act, res), i, out_f32, out_h16);
-}
-
-// K chunks per slab and the slab count: a function of (N, K) alone
-static inline void gd_gemm_plan(int64_t N, int64_t K, int* chunks_per_split, int* splits) {
-  const int64_t tiles = (N + 15) / 16, nchunks = (K + 127) / 128;
-  int64_t s = 768 / tiles;                // about three 4-wave workgroups per CU
-  if (s > nchunks / 4) s = nchunks / 4;   // a wave keeps at least one chunk
-  if (s > GD_MAX_SPLITS) s = GD_MAX_SPLITS;
-  if (s < 1) s = 1;
-  const int64_t cps = (nchunks + s - 1) / s;
-  *chunks_per_split = (int)cps;
-  *splits = (int)((nchunks + cps - 1) / cps);
+  gd_reduce_slabs<OT>(part, splits, M, N, bias, act, res, out_f32, out_h16);
 }
 
 extern "C" size_t enh_skinny_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {

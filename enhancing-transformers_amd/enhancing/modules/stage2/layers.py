@@ -23,8 +23,13 @@ HIP graph per chunk and replayed T - 1 times (prior.py `_sample_graphed`).  The 
 cursor: the attention over the long cache, the step's input row and the draw have cursor forms (enh_decode_attention_at, enh_embed_step_at,
 enh_sample_logits_at) that run the bodies of their by-value siblings, and enh_cursor_advance ends the position.  The same bits as the loop.
 
+Both also take `weights=` (None: ENH_SAMPLE_WEIGHTS, default "h16"): "fp8" streams every Linear of every Block as an MXFP8
+operand (e4m3fn codes, one E8M0 scale per 32 k; prior.py `_sample_operands`) through enh_skinny_gemm_w8 (csrc/gpt_decode_w8.hip); the head,
+the activations and the caches stay 16-bit.  The three step methods choose their product through prior.py `_step_linear`.
+
 Left out: an exact-f32 backward, more than one condition token, HIP-graph capture of position 0 and of the teacher-forced entries, graphs kept
-from call to call, relu^2 / LayerNorm fused into GEMM epilogues."""
+from call to call, relu^2 / LayerNorm fused into GEMM epilogues, 8-bit activations or caches (W8A8), MXFP6 / MXFP4, a quantized head, MXFP8 in
+the teacher-forced entries, quantized checkpoints on disk."""
 import os
 from typing import Optional, Tuple
 
@@ -32,7 +37,7 @@ import torch
 import torch.nn as nn
 
 from .prior import (FORWARD_HIDDEN_CAP, MAX_BATCH, MAX_EMBED, MAX_HEAD, MAX_TOKENS, MAX_VOCAB, OPERAND_DTYPE, Prior,  # noqa: F401  (re-exported)
-                    _block_rows, _block_rows_backward, _block_step, _grad_linears, _row_linear)
+                    _block_rows, _block_rows_backward, _block_step, _grad_linears, _row_linear, _step_linear)
 
 BACKWARD_SAVED_CAP = 16 << 30  # bytes of forward_backward()'s saved activations: shipped size 24 x 172,096 B per token, 4 sequences of 1024 per chunk
 MAX_DEPTH = 8           # enh_rq_embed_seq, enh_short_causal_attention_forward: the stage-1 residual quantizer's cap on num_quantizers
@@ -213,12 +218,17 @@ class GPT(Prior):
     @torch.no_grad()
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
                use_fp16: bool = True, *, seed: Optional[int] = None, forced_codes: Optional[torch.Tensor] = None, return_logits: bool = True,
-               call: int = 0, row_offset: int = 0, graph: Optional[bool] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+               call: int = 0, row_offset: int = 0, graph: Optional[bool] = None, weights: Optional[str] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """reference layers.py:213-266: returns (logits [B, T*V] after the temperature and the top-k mask, codes [B, T]).
 
         graph=True replays every position after the first from ONE captured HIP graph per chunk: the launches of a position
         in their cursor forms, which read the position from device memory; the same bits as the loop.  None reads ENH_GRAPHS == "1", False is the
         loop.  Captured per call, nothing is cached between calls; while per-kernel timing is on (_C.TIMER) the loop runs.
+
+        weights="fp8" streams every Linear of every Block (q|k|v, proj, p0, p1) as its MXFP8 operand (e4m3fn codes and one
+        E8M0 scale per 32 k, quantized once from the f32 masters) through enh_skinny_gemm_w8: half the weight bytes of a step and of the operand
+        copies; the head, activations and caches stay in the 16-bit format.  "h16" is the 16-bit weights; None reads ENH_SAMPLE_WEIGHTS (default
+        "h16").  It needs use_fp16=True and composes with graph=True (a different launch in the captured position).
 
         use_fp16=True runs the 16-bit operand format of ENH_PRECISION (default fp16) with f32 accumulation; False the exact mode (f32 operands on the vector ALU, f32 cache and
         row kernels).  The draw is an inverse-CDF walk in index order with one uniform per (seed, call, step, row_offset + row): the distribution of
@@ -241,23 +251,24 @@ class GPT(Prior):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         dt = self._operand_dtype(use_fp16, "GPT.sample")
+        weights = self._sample_weights(weights, use_fp16, "GPT.sample")
         codes = torch.empty(B, T, dtype=torch.int64, device=dev)
         logits = torch.empty(B, T * V, dtype=torch.float32, device=dev) if return_logits else None
         if self._use_graph(graph):
-            self._sample_graphed(B, dev, lambda b: self._decode_state(b, dt, dev), lambda st, s, e, positions: self._sample_rows_graphed(
+            self._sample_graphed(B, dev, lambda b: self._decode_state(b, dt, dev, weights=weights), lambda st, s, e, positions: self._sample_rows_graphed(
                 st, positions, conds[s:e], codes[s:e], None if logits is None else logits[s:e], None if forced_codes is None else forced_codes[s:e],
                 top_k, top_p, float(softmax_temperature), seed, call, row_offset + s))
             return logits, codes
         for s in range(0, B, MAX_BATCH):
             e = min(s + MAX_BATCH, B)
             self._sample_rows(conds[s:e], codes[s:e], None if logits is None else logits[s:e], None if forced_codes is None else forced_codes[s:e],
-                              dt, top_k, top_p, float(softmax_temperature), seed, call, row_offset + s)
+                              dt, top_k, top_p, float(softmax_temperature), seed, call, row_offset + s, weights)
         return logits, codes
 
-    def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0):
+    def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0, weights: str = "h16"):
         from ... import _C
         T, V = self.img_num_tokens, self.vocab_img_size
-        st = self._decode_state(conds.shape[0], dt, conds.device)
+        st = self._decode_state(conds.shape[0], dt, conds.device, weights=weights)
         feed = codes if forced is None else forced
         for t in range(T):
             self._decode_step(st, t, conds if t == 0 else feed[:, t - 1])
@@ -281,14 +292,15 @@ class GPT(Prior):
 
         positions(self.img_num_tokens, first, later)
 
-    def _decode_state(self, b: int, dt: torch.dtype, dev, cache_len: Optional[int] = None) -> dict:
-        """the buffers of one chunk of b <= 64 rows: residual stream, activations, the step's logits and every layer's k / v cache [b, H, T, hs]"""
+    def _decode_state(self, b: int, dt: torch.dtype, dev, cache_len: Optional[int] = None, weights: str = "h16") -> dict:
+        """the buffers of one chunk of b <= 64 rows: residual stream, activations, the step's logits and every layer's k / v cache [b, H, T, hs];
+        ops: the operands of `weights` (prior.py `_sample_operands`)"""
         f32, C, H = torch.float32, self.embed_dim, self.n_heads
         T = cache_len or self.img_num_tokens
         e = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=dev)
         return dict(dt=dt, b=b, x=e(b, C, dtype=f32), x2=e(b, C, dtype=f32), a=e(b, C), qkv=e(b, 3 * C), att=e(b, C), hid=e(b, 4 * C),
                     logits=e(b, self.vocab_img_size, dtype=f32), caches=[(e(b, H, T, C // H), e(b, H, T, C // H)) for _ in self.blocks],
-                    ops=self._operand_copies(dt))
+                    ops=self._sample_operands(dt, weights))
 
     def _decode_step(self, st: dict, t: Optional[int], ids: torch.Tensor, cursor: Optional[torch.Tensor] = None) -> None:
         """one token per row: ids (int64, on the device: the condition at t == 0, else the previous step's codes) -> st["logits"] [b, V] f32.
@@ -296,7 +308,7 @@ class GPT(Prior):
         that are fed forward, whose column t - 1 the embedding reads on the device."""
         from ... import _C
         x, x2, a, qkv, att, hid = st["x"], st["x2"], st["a"], st["qkv"], st["att"], st["hid"]
-        linear = _C.skinny_gemm_f32 if st["dt"] == torch.float32 else _C.skinny_gemm
+        linear = _step_linear(st["dt"])
         if cursor is not None:
             C = self.embed_dim
             _C.embed_step_at(self.tok_emb_code.weight.detach(), ids, 1, 1, -1, self.pos_emb_code.detach()[0], C, -C, cursor, 1, self.img_num_tokens, x)
@@ -566,7 +578,8 @@ class RQTransformer(Prior):
     @torch.no_grad()
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
                use_fp16: bool = True, *, seed: Optional[int] = None, forced_codes: Optional[torch.Tensor] = None, return_logits: bool = True,
-               call: int = 0, row_offset: int = 0, slot0_ln: str = "once", graph: Optional[bool] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+               call: int = 0, row_offset: int = 0, slot0_ln: str = "once", graph: Optional[bool] = None,
+               weights: Optional[str] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """reference layers.py:397-547 (sample, sample_spatial_step, sample_depth_step) with one condition token: returns (logits [B T, D, V] f32
         after the temperature and the top-k mask, codes [B, T, D] int64).  GPT.sample's contract: the loop is restated per
         step, one row per batch element.  Per position t the spatial Blocks run under a cache of T slots on the input row
@@ -595,7 +608,10 @@ class RQTransformer(Prior):
         graph=True replays every position after the first from ONE captured HIP graph per chunk: the spatial step, the D depth
         steps and their draws, with the spatial attention, the input rows and the draws in their cursor forms (the depth attention keeps its
         constant slot d); the same bits as the loop.  None reads ENH_GRAPHS == "1", False is the loop.  Captured per call, nothing is cached between
-        calls; while per-kernel timing is on (_C.TIMER) the loop runs."""
+        calls; while per-kernel timing is on (_C.TIMER) the loop runs.
+
+        weights="fp8" is GPT.sample's: every Linear of every Block of BOTH stacks as its MXFP8 operand through enh_skinny_gemm_w8, the head in the
+        16-bit format; None reads ENH_SAMPLE_WEIGHTS (default "h16"); it needs use_fp16=True."""
         if not (torch.is_tensor(conds) and conds.is_cuda):
             raise NotImplementedError("RQTransformer.sample: sampling runs on a ROCm device only: conds must be a device tensor (the spatial / depth "
                                       "decode loop is HIP kernels: there is no CPU path)")
@@ -622,10 +638,11 @@ class RQTransformer(Prior):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         dt = self._operand_dtype(use_fp16, "RQTransformer.sample")
+        weights = self._sample_weights(weights, use_fp16, "RQTransformer.sample")
         codes = torch.empty(B, T, D, dtype=torch.int64, device=dev)
         logits = torch.empty(B * T, D, V, dtype=torch.float32, device=dev) if return_logits else None
         if self._use_graph(graph):
-            self._sample_graphed(B, dev, lambda b: self._decode_state(b, dt, dev), lambda st, s, e, positions: self._sample_rows_graphed(
+            self._sample_graphed(B, dev, lambda b: self._decode_state(b, dt, dev, weights), lambda st, s, e, positions: self._sample_rows_graphed(
                 st, positions, conds[s:e], codes[s:e], None if logits is None else logits.view(B, T, D, V)[s:e],
                 None if forced_codes is None else forced_codes[s:e], top_k, top_p, float(softmax_temperature), seed, call, row_offset + s,
                 slot0_ln == "twice", depth_decode == "cache"))
@@ -634,25 +651,27 @@ class RQTransformer(Prior):
             e = min(s + MAX_BATCH, B)
             self._sample_rows(conds[s:e], codes[s:e], None if logits is None else logits.view(B, T, D, V)[s:e],
                               None if forced_codes is None else forced_codes[s:e], dt, top_k, top_p, float(softmax_temperature), seed, call,
-                              row_offset + s, slot0_ln == "twice", depth_decode == "cache")
+                              row_offset + s, slot0_ln == "twice", depth_decode == "cache", weights)
         return logits, codes
 
-    def _decode_state(self, b: int, dt: torch.dtype, dev) -> dict:
+    def _decode_state(self, b: int, dt: torch.dtype, dev, weights: str = "h16") -> dict:
         """the buffers of one chunk of b <= 64 rows: the spatial and the depth residual stream, activations, the step's logits, every spatial
-        layer's k / v cache [b, Hs, T, C / Hs] and every depth layer's [b, Hd, D, C / Hd]"""
+        layer's k / v cache [b, Hs, T, C / Hs] and every depth layer's [b, Hd, D, C / Hd]; ops: the operands of `weights` (prior.py
+        `_sample_operands`)"""
         f32, C, T, D = torch.float32, self.embed_dim, self.img_num_tokens, self.depth_num_tokens
         Hs, Hd = self.spatial_n_heads, self.depth_n_heads
         e = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=dev)
         return dict(dt=dt, b=b, xs=e(b, C, dtype=f32), xd=e(b, C, dtype=f32), x2=e(b, C, dtype=f32), a=e(b, C), qkv=e(b, 3 * C), att=e(b, C),
                     hid=e(b, 4 * C), logits=e(b, self.vocab_img_size, dtype=f32),
                     spatial=[(e(b, Hs, T, C // Hs), e(b, Hs, T, C // Hs)) for _ in self.spatial_transformer],
-                    depth=[(e(b, Hd, D, C // Hd), e(b, Hd, D, C // Hd)) for _ in self.depth_transformer], ops=self._operand_copies(dt))
+                    depth=[(e(b, Hd, D, C // Hd), e(b, Hd, D, C // Hd)) for _ in self.depth_transformer], ops=self._sample_operands(dt, weights))
 
-    def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0, ln_twice: bool, depth_cache: bool):
+    def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0, ln_twice: bool, depth_cache: bool,
+                     weights: str = "h16"):
         """one chunk of b <= 64 rows: codes [b, T, D] (a view the draws are written into), logits [b, T, D, V] (a view) or None"""
         from ... import _C
         T, D = self.img_num_tokens, self.depth_num_tokens
-        st = self._decode_state(conds.shape[0], dt, conds.device)
+        st = self._decode_state(conds.shape[0], dt, conds.device, weights)
         feed = codes if forced is None else forced
         for t in range(T):
             self._spatial_step(st, t, conds if t == 0 else feed[:, t - 1, :])
@@ -691,7 +710,7 @@ class RQTransformer(Prior):
         codes that are fed forward, whose row t - 1 the embedding reads on the device."""
         from ... import _C
         x, x2, a, qkv, att, hid = st["xs"], st["x2"], st["a"], st["qkv"], st["att"], st["hid"]
-        linear = _C.skinny_gemm_f32 if st["dt"] == torch.float32 else _C.skinny_gemm
+        linear = _step_linear(st["dt"])
         if cursor is not None:
             C, D = self.embed_dim, self.depth_num_tokens
             _C.embed_step_at(self.tok_emb_code.weight.detach(), ids, D, D, -D, self.pos_emb_code.detach()[0], C, -C, cursor, 1, self.img_num_tokens, x)
@@ -715,7 +734,7 @@ class RQTransformer(Prior):
         constant of the launch either way."""
         from ... import _C
         x, x2, a, qkv, att, hid = st["xd"], st["x2"], st["a"], st["qkv"], st["att"], st["hid"]
-        linear = _C.skinny_gemm_f32 if st["dt"] == torch.float32 else _C.skinny_gemm
+        linear = _step_linear(st["dt"])
         attend = _C.decode_attention if depth_cache else _C.short_decode_attention
         if d > 0 and cursor is not None:
             D = self.depth_num_tokens

@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 30  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 31  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -622,6 +622,29 @@ int enh_skinny_gemm_f32(const float* x, const float* W, int64_t M, int64_t N, in
 int enh_sample_logits(const float* logits, int B, int V, float temperature, int top_k, float top_p, const float* uniforms, uint64_t seed,
                       uint32_t call, uint32_t step, int64_t row0, int64_t* codes, int64_t code_stride, float* logits_out,
                       int64_t logits_out_stride, uint8_t* mask_out, float* probs_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 sampling with MXFP8 weights (csrc/gpt_decode_w8.hip): the weight-only 8-bit form of a decode step's products.
+ * The operand format, fixed: a weight W [N, K] in nn.Linear layout, K % 32 == 0, is two row-major arrays,
+ *   codes  [N, K]      uint8: OCP e4m3fn (bias 7, largest finite 448 = 0x7e, 0x7f / 0xff NaN; not the fnuz form),
+ *   scales [N, K / 32] uint8: E8M0, byte s = 2^(s - 127), one per 32 consecutive k of a row,
+ * and W[n, k] = e4m3(codes[n, k]) 2^(scales[n, k / 32] - 127).  Per block of 32 (OCP Microscaling Formats v1.0): amax = max |w|,
+ * X = clamp(floor(log2 amax) - 8, -127, 127) (X = 0 when amax == 0), code = e4m3fn(RNE(w 2^-X)) saturated to +-448: values in (448, 512)
+ * saturate and finite input never gives a NaN code.  Non-finite input: a block that holds an infinity or a NaN gets X = 120 (scale byte 247);
+ * an infinity becomes +-448, a NaN the NaN code 0x7f with its sign, and the block's finite values are coded at that scale.
+ * No float atomics; the same bits on every run.
+ * ------------------------------------------------------------------------------------------------ */
+/* Rows [0, N) of w (f32, K values each, w_row_stride elements apart; rows 16-byte aligned) become rows code_row0 .. code_row0 + N - 1 of `codes`
+ * (row pitch K) and rows scale_row0 .. of `scales` (row pitch K / 32): q, k and v quantized one after another at row offsets 0, C and 2C are
+ * the fused [3C, C] operand.  One pass over w; nothing outside those rows is written. */
+int enh_mxfp8_quantize(const float* w, int64_t N, int64_t K, int64_t w_row_stride, uint8_t* codes, int64_t code_row0, uint8_t* scales,
+                       int64_t scale_row0, void* stream);
+/* enh_skinny_gemm_h16 with W given as (codes, scales): y[M,N] = act(x[M,K] W^T + bias[N]) (+ res[M,N]), x in the 16-bit format of dtype,
+ * 1 <= M <= 64, N % 8 == 0, K % 32 == 0 (else ENH_E_SHAPE); the same epilogue, outputs, K slabs and workspace (enh_skinny_gemm_workspace_bytes).
+ * The codes are widened to the operand format exactly, every 32-wide block is one MFMA step whose f32 result is multiplied by the block's power of
+ * two as it is added to the f32 sum: the scale costs no accuracy.  The codes and scales are read exactly once. */
+int enh_skinny_gemm_w8(const enh_h16* x, const uint8_t* codes, const uint8_t* scales, int64_t M, int64_t N, int64_t K, const float* bias, int act,
+                       const float* res, float* out_f32, enh_h16* out_h16, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stage-2 GPT, teacher-forced forward (csrc/gpt_prefill.hip: the attention, csrc/gpt_rows.hip: the row kernels; reference enhancing/modules/stage2/layers.py:57-97,132-136,193-211 with

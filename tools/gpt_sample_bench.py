@@ -9,7 +9,11 @@ Timing: HIP events around a window of back-to-back calls (10 steps; 100 kernel l
 cache), median, minimum and maximum of 7 windows that alternate between the two paths, after a warm-up.
 
 --graph writes profiles/gpt_sample_graph.txt instead: the eager loop against replays of one captured position (sample(graph=True)) at batch 1 and 4
-(tools/sample_graph_bench.py)."""
+(tools/sample_graph_bench.py).
+
+--weights fp8 writes profiles/gpt_sample_fp8.txt instead: the step with MXFP8 Block weights (sample(weights="fp8")) against the
+16-bit step at batch 1, 4 and 16, alternating windows in this process, and the five products alone in both forms with the TB/s of the bytes each
+actually moves."""
 import argparse
 import math
 import os
@@ -140,6 +144,72 @@ def graph_mode(m, L, out):
         f.write(text)
 
 
+def fp8_mode(m, L, out):
+    """--weights fp8: the MXFP8-weight step against the 16-bit step, and the five products alone; writes profiles/gpt_sample_fp8.txt"""
+    C, V, T, H = m.embed_dim, m.vocab_img_size, m.img_num_tokens, m.n_heads
+    dt = torch.float16
+    w16 = (12 * C * C * L + V * C) * 2
+    w8 = 12 * C * C * L + 12 * C * C * L // 32 + V * C * 2
+    lines = [f"stage-2 GPT sampling step, MXFP8 Block weights against 16-bit weights, on {torch.cuda.get_device_name(0)}: C={C} layers={L} heads={H} V={V}, "
+             f"fp16 activations and caches; weights per step {w16 / 1e9:.2f} GB (16-bit) / {w8 / 1e9:.2f} GB (fp8: codes + scales + the 16-bit head)",
+             "times: median [min .. max] of 7 alternating windows in one process; a step window is 10 steps, a kernel window is 100 launches over rotating",
+             "operand buffers of >= 1 GB in all; kernel times are event times over back-to-back launches: they include the launch boundary (~1-2 us each)",
+             f"{'batch':>5} {'cache':>5} {'16-bit ms [min .. max]':>28} {'fp8 ms [min .. max]':>28} {'16-bit/fp8':>10} {'beyond spread':>13} {'fp8 GB':>7} {'fp8 TB/s':>8}"]
+    f3 = lambda v: f"{v[1]:.3f} [{v[0]:.3f} .. {v[2]:.3f}]"
+    f1 = lambda v: f"{v[1] * 1e3:.1f} [{v[0] * 1e3:.1f} .. {v[2] * 1e3:.1f}]"
+    for b in (1, 4, 16):
+        sts = {w: m._decode_state(b, dt, "cuda", weights=w) for w in ("h16", "fp8")}
+        codes = torch.randint(0, V, (b, T), device="cuda")
+        for n in (1, 512, 1024):
+            t = n - 1
+
+            def step(w):
+                def run(i):
+                    m._decode_step(sts[w], t, codes[:, t - 1] if t else codes[:, 0] % 1000)
+                    _C.sample_logits(sts[w]["logits"], codes[:, t], top_k=None, top_p=None, seed=1, step=t)
+                return run
+            h, f = ab(step("h16"), step("fp8"), inner=10)
+            moved = w8 + 2 * L * b * n * C * 2 + L * b * C * (4 * 6 + 2 * 10)
+            lines.append(f"{b:>5} {n:>5} {f3(h):>28} {f3(f):>28} {h[1] / f[1]:>10.3f} {'yes' if f[2] < h[0] else 'no':>13} {moved / 1e9:>7.2f} "
+                         f"{moved / (f[1] * 1e-3) / 1e12:>8.2f}")
+        del sts
+        torch.cuda.empty_cache()
+    lines.append("beyond spread: the slowest fp8 window is faster than the fastest 16-bit window of the same point")
+    lines.append("kernels alone (fp16 activations), us: median [min .. max]; TB/s of the bytes each form moves; kept = fp8 TB/s / 16-bit TB/s:")
+    for b in (1, 4, 16):
+        for name, N, K in (("qkv", 3 * C, C), ("proj", C, C), ("p0", 4 * C, C), ("p1", C, 4 * C), ("head", V, C)):
+            nbuf = max(2, -(-(1 << 30) // (N * K)))
+            x = torch.randn(b, K, device="cuda").half()
+            y = torch.empty(b, N, device="cuda")
+            ws = [(torch.randn(N, K, device="cuda") / math.sqrt(K)) for _ in range(2)]
+            w16s = [ws[i % 2].half() for i in range(-(-nbuf // 2))]
+            by16 = 2 * N * K + 2 * b * K + 4 * b * N
+            if name == "head":       # stays 16-bit under weights="fp8": one form
+                d, _ = ab(lambda i: _C.skinny_gemm(x, w16s[i % len(w16s)], y), lambda i: None, inner=100)
+                lines.append(f"  {name:>4} M={b:<2} N={N:<5} K={K:<5}: 16-bit {f1(d):>24} us {by16 / d[1] / 1e9:5.2f} TB/s   (the head stays 16-bit)")
+                continue
+            q8 = []
+            for i in range(nbuf):
+                q = (torch.empty(N, K, dtype=torch.uint8, device="cuda"), torch.empty(N, K // 32, dtype=torch.uint8, device="cuda"))
+                _C.quantize_mxfp8(ws[i % 2], q[0], q[1])
+                q8.append(q)
+            by8 = N * K + N * K // 32 + 2 * b * K + 4 * b * N
+            d, f = ab(lambda i: _C.skinny_gemm(x, w16s[i % len(w16s)], y), lambda i: _C.skinny_gemm_w8(x, *q8[i % nbuf], y), inner=100)
+            t16, t8 = by16 / d[1] / 1e9, by8 / f[1] / 1e9
+            lines.append(f"  {name:>4} M={b:<2} N={N:<5} K={K:<5}: 16-bit {f1(d):>24} us {t16:5.2f} TB/s   fp8 {f1(f):>24} us {t8:5.2f} TB/s   "
+                         f"time {d[1] / f[1]:5.2f}x   kept {t8 / t16:4.2f}")
+            del ws, w16s, q8
+        torch.cuda.empty_cache()
+    ops8 = sum(t.numel() * t.element_size() for W in m._sample_operands(dt, "fp8")["layers"] for k in ("wqkv", "wproj", "w0", "w1") for t in W[k])
+    ops16 = sum(W[k].numel() * 2 for W in m._operand_copies(dt)["layers"] for k in ("wqkv", "wproj", "w0", "w1"))
+    lines.append(f"operand copies of the Blocks held by the process: {ops8 / 1e9:.2f} GB (fp8) against {ops16 / 1e9:.2f} GB (16-bit)")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -147,9 +217,11 @@ def main():
     ap.add_argument("--whole", type=int, default=1, help="also time a whole 1024-step sample at batch 4")
     ap.add_argument("--graph", action="store_true", help="instead of the tables: the eager loop against replays of one captured position "
                     "(profiles/gpt_sample_graph.txt)")
+    ap.add_argument("--weights", choices=("h16", "fp8"), default="h16", help="fp8: instead of the tables, the MXFP8-weight step against the 16-bit "
+                    "step and the products alone (profiles/gpt_sample_fp8.txt)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "gpt_sample_graph.txt" if args.graph else "gpt_sample.txt")
+        args.out = os.path.join(ROOT, "profiles", "gpt_sample_graph.txt" if args.graph else "gpt_sample_fp8.txt" if args.weights == "fp8" else "gpt_sample.txt")
     C, H, V, T, L = 6144, 16, 8192, 1024, args.layers
     torch.manual_seed(0)
     with torch.device("cuda"):
@@ -158,6 +230,8 @@ def main():
             m.pos_emb_code.normal_(0, 0.02)
     if args.graph:
         return graph_mode(m, L, args.out)
+    if args.weights == "fp8":
+        return fp8_mode(m, L, args.out)
     dt = torch.float16
     wbytes = (12 * C * C * L + V * C) * 2
     lines = [f"stage-2 sampling step on {torch.cuda.get_device_name(0)}: C={C} layers={L} heads={H} V={V}, fp16 operands; weights {wbytes / 1e9:.2f} GB per step",
