@@ -10,7 +10,8 @@
 //   enh_decode_attention  one new token per (batch, head) against a cache [B, H, Tmax, hs]: appends k / v at slot t and returns
 //                         softmax(q K[0..t]^T / sqrt(hs)) V[0..t].  Slot t is taken from the step's qkv row, never read back from the cache; slots > t
 //                         are never touched.  The cache length is cut into pieces of at most 256 slots (grid.y); partial (max, sum, out) triples are
-//                         merged in ascending piece order by a second kernel.
+//                         merged in ascending piece order by a second kernel (the plan and the merge: decode_attn.h, shared with the MXFP8-cache
+//                         form of gpt_decode_kv8.hip).
 //   enh_sample_logits     temperature, top-k, softmax, top-p and an inverse-CDF draw of one row per workgroup (GPT.sample lines 233-258).
 //   enh_skinny_gemm_f32   the exact mode's form of the product: f32 operands, vector ALU, tree-ordered sums.
 // The step's LayerNorm and embedding are row kernels and stand beside the teacher-forced forward's: gpt_rows.hip (enh_row_ln_scale, enh_gpt_embed).
@@ -20,12 +21,11 @@
 // device memory instead of from their arguments, so the launches of one position, captured into a HIP graph, can be replayed for the next one.
 // Each is a kernel of its own name around the __device__ body of its by-value sibling: the same arithmetic, the same bits.
 #include "common.h"
+#include "decode_attn.h"
 #include "embed_row.h"
 #include "skinny_gemm.h"
 #include <type_traits>
 
-#define GD_ATT_PIECE 256      // cache slots per workgroup of the decode attention (its scores live in LDS)
-#define GD_ATT_MAX_T 8192
 #define GD_SAMPLE_MAX_V 16384
 #define GD_SAMPLE_PER 16      // logits per thread of the sampler (1024 threads)
 
@@ -269,44 +269,10 @@ __global__ __launch_bounds__(256) void gpt_decode_attn_kernel(const void* __rest
   gd_attn_piece<OT, F32>(qkv_, Kc_, Vc_, H, hs, Tmax, t, nsplit, split_len, scale, out_, part);
 }
 
-// pieces in ascending order under the common maximum: the body of gpt_decode_attn_merge_kernel and of its cursor form
-template <typename OT, bool F32>
-__device__ __forceinline__ void gd_attn_merge(const float* __restrict__ part, int H, int hs, int nsplit, void* __restrict__ out_) {
-  typedef typename std::conditional<F32, float, uint16_t>::type CT;
-  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
-  const float* pp = part + (size_t)bh * nsplit * (hs + 2);
-  float mx = -__builtin_inff();
-  for (int s = 0; s < nsplit; ++s) mx = fmaxf(mx, pp[(size_t)s * (hs + 2) + hs]);
-  float l = 0.f;
-  for (int s = 0; s < nsplit; ++s) l += pp[(size_t)s * (hs + 2) + hs + 1] * expf(pp[(size_t)s * (hs + 2) + hs] - mx);
-  CT* out = reinterpret_cast<CT*>(out_) + (size_t)b * H * hs + (size_t)h * hs;
-  for (int d = threadIdx.x; d < hs; d += 128) {
-    float o = 0.f;
-    for (int s = 0; s < nsplit; ++s) o += pp[(size_t)s * (hs + 2) + d] * expf(pp[(size_t)s * (hs + 2) + hs] - mx);
-    const float y = o / l;
-    if constexpr (F32) out[d] = y;
-    else out[d] = pack1<OT>(y);
-  }
-}
-
+// the pieces in ascending order (decode_attn.h gd_attn_merge, as the cursor form below)
 template <typename OT, bool F32>
 __global__ __launch_bounds__(128) void gpt_decode_attn_merge_kernel(const float* __restrict__ part, int H, int hs, int nsplit, void* __restrict__ out_) {
   gd_attn_merge<OT, F32>(part, H, hs, nsplit, out_);
-}
-
-// pieces of a cache of `len` slots: at most GD_ATT_PIECE slots each, and more, down to 64 slots, while B * H workgroups leave the chip idle.
-// Host and device: the cursor kernels below plan on the device from the position they read there, with the integers of the host's plan.
-__host__ __device__ static inline void gd_att_plan(int64_t BH, int len, int* nsplit, int* split_len) {
-  int64_t by_len = (len + GD_ATT_PIECE - 1) / GD_ATT_PIECE;
-  int64_t want = (512 + BH - 1) / BH;
-  const int64_t most = (len + 63) / 64;
-  if (want > most) want = most;
-  int64_t ns = by_len > want ? by_len : want;
-  if (ns < 1) ns = 1;
-  int64_t sl = (len + ns - 1) / ns;
-  sl = (sl + 31) / 32 * 32;
-  *split_len = (int)sl;
-  *nsplit = (int)((len + sl - 1) / sl);
 }
 
 extern "C" size_t enh_decode_attention_workspace_bytes(int B, int H, int hs, int Tmax) {
@@ -357,12 +323,6 @@ extern "C" int enh_cursor_advance(int* cursor, void* stream) {
   enh_note_kernel_plain("gpt_cursor_advance_kernel");
   gpt_cursor_advance_kernel<<<1, 1, 0, (hipStream_t)stream>>>(cursor);
   return enh_check_launch("enh_cursor_advance");
-}
-
-// the step t = *cursor + t_offset, or -1 when it lies outside the cache: then no workgroup reads or writes anything
-__device__ __forceinline__ int gd_cursor_step(const int* __restrict__ cursor, int t_offset, int Tmax) {
-  const int64_t t = (int64_t)*cursor + t_offset;
-  return t >= 0 && t < Tmax ? (int)t : -1;
 }
 
 // gpt_decode_attn_kernel under a grid sized for the whole cache (gridDim.y = (Tmax + 63) / 64 >= every plan's nsplit): the pieces past the plan return

@@ -165,12 +165,14 @@ SIGNATURES = {
     "enh_short_decode_attention": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     "enh_cursor_advance": (_i32, [_vp, _vp]),
     "enh_decode_attention_at": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _i32, _vp]),
+    "enh_decode_attention_kv8": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _i32, _vp]),
+    "enh_decode_attention_kv8_at": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _i32, _vp]),
     "enh_embed_step_at": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "enh_sample_logits_at": (_i32, [_vp, _i32, _i32, _f32, _i32, _f32, _u64, _u32, _vp, _i32, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp]),
 }
 
 _LIB = None
-ABI_VERSION = 31 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 32 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -1143,6 +1145,36 @@ def decode_attention(qkv, k_cache, v_cache, t: int, out):
                                                  _p(out, dt, "out"), _p(ws), ws.numel(), _DT_OF[dt], _stream()), "enh_decode_attention"), unit="byte")
 
 
+def _kv8_shapes(who: str, qkv, k_codes, k_scales, v_codes, v_scales, out):
+    """(B, H, Tmax, hs, dtype) of a decode attention over MXFP8 caches, or a RuntimeError: codes [B,H,Tmax,hs] and scales [B,H,Tmax,hs/32] uint8,
+    qkv [B,3C] and out [B,C] in one 16-bit format"""
+    if k_codes.dim() != 4:
+        raise RuntimeError(f"{who}: k_codes {tuple(k_codes.shape)} must be [B, H, Tmax, hs]")
+    B, H, Tmax, hs = k_codes.shape
+    if (tuple(v_codes.shape) != (B, H, Tmax, hs) or hs % MX_BLOCK or tuple(k_scales.shape) != (B, H, Tmax, hs // MX_BLOCK)
+            or tuple(v_scales.shape) != (B, H, Tmax, hs // MX_BLOCK) or tuple(qkv.shape) != (B, 3 * H * hs) or tuple(out.shape) != (B, H * hs)):
+        raise RuntimeError(f"{who}: qkv {tuple(qkv.shape)} codes {tuple(k_codes.shape)} {tuple(v_codes.shape)} scales {tuple(k_scales.shape)} "
+                           f"{tuple(v_scales.shape)} out {tuple(out.shape)} do not fit (scales [B, H, Tmax, hs / {MX_BLOCK}])")
+    dt = qkv.dtype
+    if dt not in H16:
+        raise RuntimeError(f"{who}: qkv and out must be bf16 or fp16 (the exact f32 mode has no MXFP8 cache), got {dt}")
+    return B, H, Tmax, hs, dt
+
+
+def decode_attention_kv8(qkv, k_codes, k_scales, v_codes, v_scales, t: int, out):
+    """decode_attention over an MXFP8 cache (enh_decode_attention_kv8): quantizes the step's k / v rows, appends their codes and scales at slot t
+    of k_codes / v_codes [B,H,Tmax,hs] and k_scales / v_scales [B,H,Tmax,hs/32] (uint8) and writes out[B,C] = softmax(q K[0..t]^T / sqrt(hs)) V[0..t]
+    over the dequantized cache, slot t included; qkv [B,3C] and out bf16 | fp16"""
+    B, H, Tmax, hs, dt = _kv8_shapes("decode_attention_kv8", qkv, k_codes, k_scales, v_codes, v_scales, out)
+    L = lib()
+    ws = _workspace(L.enh_decode_attention_workspace_bytes(B, H, hs, Tmax), qkv.device)
+    # bytes moved: the codes and the scales of slots 0 .. t of both caches
+    _timed(None, 2.0 * B * H * (int(t) + 1) * (hs + hs // MX_BLOCK),
+           lambda: _check(L.enh_decode_attention_kv8(_p(qkv, dt, "qkv"), _p(k_codes, U8, "k_codes"), _p(k_scales, U8, "k_scales"), _p(v_codes, U8, "v_codes"),
+                                                     _p(v_scales, U8, "v_scales"), B, H, hs, Tmax, int(t), _p(out, dt, "out"), _p(ws), ws.numel(),
+                                                     _DT_OF[dt], _stream()), "enh_decode_attention_kv8"), unit="byte")
+
+
 def row_ln_scale(x, w, b, out, colscale=None, eps: float = 1e-5):
     """out = LayerNorm(x) (* colscale): x [M,D] f32, M <= 64, D % 8 == 0 up to 8192; out f32 or 16-bit"""
     M, D = x.shape
@@ -1471,6 +1503,17 @@ def decode_attention_at(qkv, k_cache, v_cache, cursor, out, t_offset: int = 0) -
     _check(L.enh_decode_attention_at(_p(qkv, dt, "qkv"), _p(k_cache, dt, "k_cache"), _p(v_cache, dt, "v_cache"), B, H, hs, Tmax,
                                      _cursor_ptr(cursor, "decode_attention_at"), int(t_offset), _p(out, dt, "out"), _p(ws), ws.numel(), _DT_OF[dt],
                                      _stream()), "enh_decode_attention_at")
+
+
+def decode_attention_kv8_at(qkv, k_codes, k_scales, v_codes, v_scales, cursor, out, t_offset: int = 0) -> None:
+    """decode_attention_kv8 at t = cursor + t_offset, read on the device (enh_decode_attention_kv8_at): its bits at the same t, in the output and in
+    the cache; t outside the cache: nothing is read or written"""
+    B, H, Tmax, hs, dt = _kv8_shapes("decode_attention_kv8_at", qkv, k_codes, k_scales, v_codes, v_scales, out)
+    L = lib()
+    ws = _workspace(L.enh_decode_attention_workspace_bytes(B, H, hs, Tmax), qkv.device)
+    _check(L.enh_decode_attention_kv8_at(_p(qkv, dt, "qkv"), _p(k_codes, U8, "k_codes"), _p(k_scales, U8, "k_scales"), _p(v_codes, U8, "v_codes"),
+                                         _p(v_scales, U8, "v_scales"), B, H, hs, Tmax, _cursor_ptr(cursor, "decode_attention_kv8_at"), int(t_offset),
+                                         _p(out, dt, "out"), _p(ws), ws.numel(), _DT_OF[dt], _stream()), "enh_decode_attention_kv8_at")
 
 
 def embed_step_at(table, ids, n: int, id_t_stride: int, id_offset: int, pos, pos_t_stride: int, pos_offset: int, cursor, t_lo: int, t_hi: int, out) -> None:

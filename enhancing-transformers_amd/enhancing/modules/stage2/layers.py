@@ -27,9 +27,14 @@ Both also take `weights=` (None: ENH_SAMPLE_WEIGHTS, default "h16"; DESIGN.md §
 operand (e4m3fn codes, one E8M0 scale per 32 k; prior.py `_sample_operands`) through enh_skinny_gemm_w8 (csrc/gpt_decode_w8.hip); the head,
 the activations and the caches stay 16-bit.  The three step methods choose their product through prior.py `_step_linear`.
 
+Both also take `cache=` (None: ENH_SAMPLE_CACHE, default "h16"): "fp8" holds every cache that enh_decode_attention serves (all
+Blocks of GPT, the spatial stack of RQTransformer) as MXFP8 codes and scales with the blocks along the head dimension (prior.py `_kv_caches`)
+and attends through enh_decode_attention_kv8 (csrc/gpt_decode_kv8.hip), which quantizes the step's k / v rows as it appends them; the RQ depth
+caches stay 16-bit.  The step methods choose the launch through prior.py `_step_attention`.
+
 Left out: an exact-f32 backward, more than one condition token, HIP-graph capture of position 0 and of the teacher-forced entries, graphs kept
-from call to call, relu^2 / LayerNorm fused into GEMM epilogues, 8-bit activations or caches (W8A8), MXFP6 / MXFP4, a quantized head, MXFP8 in
-the teacher-forced entries, quantized checkpoints on disk."""
+from call to call, relu^2 / LayerNorm fused into GEMM epilogues, 8-bit activations (W8A8), an 8-bit form of the RQ depth caches, MXFP6 / MXFP4,
+a quantized head, MXFP8 in the teacher-forced entries, quantized checkpoints on disk."""
 import os
 from typing import Optional, Tuple
 
@@ -37,7 +42,7 @@ import torch
 import torch.nn as nn
 
 from .prior import (FORWARD_HIDDEN_CAP, MAX_BATCH, MAX_EMBED, MAX_HEAD, MAX_TOKENS, MAX_VOCAB, OPERAND_DTYPE, Prior,  # noqa: F401  (re-exported)
-                    _block_rows, _block_rows_backward, _block_step, _grad_linears, _row_linear, _step_linear)
+                    _block_rows, _block_rows_backward, _block_step, _grad_linears, _kv_caches, _row_linear, _step_attention, _step_linear)
 
 BACKWARD_SAVED_CAP = 16 << 30  # bytes of forward_backward()'s saved activations: shipped size 24 x 172,096 B per token, 4 sequences of 1024 per chunk
 MAX_DEPTH = 8           # enh_rq_embed_seq, enh_short_causal_attention_forward: the stage-1 residual quantizer's cap on num_quantizers
@@ -218,7 +223,8 @@ class GPT(Prior):
     @torch.no_grad()
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
                use_fp16: bool = True, *, seed: Optional[int] = None, forced_codes: Optional[torch.Tensor] = None, return_logits: bool = True,
-               call: int = 0, row_offset: int = 0, graph: Optional[bool] = None, weights: Optional[str] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+               call: int = 0, row_offset: int = 0, graph: Optional[bool] = None, weights: Optional[str] = None,
+               cache: Optional[str] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """reference layers.py:213-266: returns (logits [B, T*V] after the temperature and the top-k mask, codes [B, T]).
 
         graph=True replays every position after the first from ONE captured HIP graph per chunk: the launches of a position
@@ -229,6 +235,11 @@ class GPT(Prior):
         E8M0 scale per 32 k, quantized once from the f32 masters) through enh_skinny_gemm_w8: half the weight bytes of a step and of the operand
         copies; the head, activations and caches stay in the 16-bit format.  "h16" is the 16-bit weights; None reads ENH_SAMPLE_WEIGHTS (default
         "h16").  It needs use_fp16=True and composes with graph=True (a different launch in the captured position).
+
+        cache="fp8" holds every layer's k / v cache as MXFP8 codes and scales (blocks of 32 along the head dimension, 1 + 1/32 bytes
+        per element instead of 2) and attends through enh_decode_attention_kv8: the step's k / v rows are quantized as they are appended, and the
+        step's own attention reads them quantized too.  "h16" is the 16-bit caches; None reads ENH_SAMPLE_CACHE (default "h16").  It needs
+        use_fp16=True and composes with graph=True and weights="fp8".
 
         use_fp16=True runs the 16-bit operand format of ENH_PRECISION (default fp16) with f32 accumulation; False the exact mode (f32 operands on the vector ALU, f32 cache and
         row kernels).  The draw is an inverse-CDF walk in index order with one uniform per (seed, call, step, row_offset + row): the distribution of
@@ -252,23 +263,25 @@ class GPT(Prior):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         dt = self._operand_dtype(use_fp16, "GPT.sample")
         weights = self._sample_weights(weights, use_fp16, "GPT.sample")
+        cache = self._sample_cache(cache, use_fp16, "GPT.sample")
         codes = torch.empty(B, T, dtype=torch.int64, device=dev)
         logits = torch.empty(B, T * V, dtype=torch.float32, device=dev) if return_logits else None
         if self._use_graph(graph):
-            self._sample_graphed(B, dev, lambda b: self._decode_state(b, dt, dev, weights=weights), lambda st, s, e, positions: self._sample_rows_graphed(
+            state = lambda b: self._decode_state(b, dt, dev, weights=weights, cache=cache)
+            self._sample_graphed(B, dev, state, lambda st, s, e, positions: self._sample_rows_graphed(
                 st, positions, conds[s:e], codes[s:e], None if logits is None else logits[s:e], None if forced_codes is None else forced_codes[s:e],
                 top_k, top_p, float(softmax_temperature), seed, call, row_offset + s))
             return logits, codes
         for s in range(0, B, MAX_BATCH):
             e = min(s + MAX_BATCH, B)
             self._sample_rows(conds[s:e], codes[s:e], None if logits is None else logits[s:e], None if forced_codes is None else forced_codes[s:e],
-                              dt, top_k, top_p, float(softmax_temperature), seed, call, row_offset + s, weights)
+                              dt, top_k, top_p, float(softmax_temperature), seed, call, row_offset + s, weights, cache)
         return logits, codes
 
-    def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0, weights: str = "h16"):
+    def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0, weights: str = "h16", cache: str = "h16"):
         from ... import _C
         T, V = self.img_num_tokens, self.vocab_img_size
-        st = self._decode_state(conds.shape[0], dt, conds.device, weights=weights)
+        st = self._decode_state(conds.shape[0], dt, conds.device, weights=weights, cache=cache)
         feed = codes if forced is None else forced
         for t in range(T):
             self._decode_step(st, t, conds if t == 0 else feed[:, t - 1])
@@ -292,14 +305,14 @@ class GPT(Prior):
 
         positions(self.img_num_tokens, first, later)
 
-    def _decode_state(self, b: int, dt: torch.dtype, dev, cache_len: Optional[int] = None, weights: str = "h16") -> dict:
-        """the buffers of one chunk of b <= 64 rows: residual stream, activations, the step's logits and every layer's k / v cache [b, H, T, hs];
-        ops: the operands of `weights` (prior.py `_sample_operands`)"""
+    def _decode_state(self, b: int, dt: torch.dtype, dev, cache_len: Optional[int] = None, weights: str = "h16", cache: str = "h16") -> dict:
+        """the buffers of one chunk of b <= 64 rows: residual stream, activations, the step's logits and every layer's k / v cache [b, H, T, hs]
+        in the form of `cache` (prior.py `_kv_caches`); ops: the operands of `weights` (prior.py `_sample_operands`)"""
         f32, C, H = torch.float32, self.embed_dim, self.n_heads
         T = cache_len or self.img_num_tokens
         e = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=dev)
         return dict(dt=dt, b=b, x=e(b, C, dtype=f32), x2=e(b, C, dtype=f32), a=e(b, C), qkv=e(b, 3 * C), att=e(b, C), hid=e(b, 4 * C),
-                    logits=e(b, self.vocab_img_size, dtype=f32), caches=[(e(b, H, T, C // H), e(b, H, T, C // H)) for _ in self.blocks],
+                    logits=e(b, self.vocab_img_size, dtype=f32), caches=_kv_caches(len(self.blocks), b, H, T, C // H, dt, dev, cache),
                     ops=self._sample_operands(dt, weights))
 
     def _decode_step(self, st: dict, t: Optional[int], ids: torch.Tensor, cursor: Optional[torch.Tensor] = None) -> None:
@@ -312,15 +325,14 @@ class GPT(Prior):
         if cursor is not None:
             C = self.embed_dim
             _C.embed_step_at(self.tok_emb_code.weight.detach(), ids, 1, 1, -1, self.pos_emb_code.detach()[0], C, -C, cursor, 1, self.img_num_tokens, x)
-            attend = lambda q, kc, vc, o: _C.decode_attention_at(q, kc, vc, cursor, o)
         else:
             if t == 0:
                 _C.gpt_embed(self.tok_emb_cond.weight.detach(), ids, self.pos_emb_cond.detach()[0, 0], x)
             else:
                 _C.gpt_embed(self.tok_emb_code.weight.detach(), ids, self.pos_emb_code.detach()[0, t - 1], x)
-            attend = lambda q, kc, vc, o: _C.decode_attention(q, kc, vc, t, o)
-        for blk, W, (kc, vc) in zip(self.blocks, st["ops"]["layers"], st["caches"]):
-            _block_step(blk, W, linear, lambda q, o: attend(q, kc, vc, o), x, x2, a, qkv, att, hid)
+        attend = _step_attention(t, cursor)
+        for blk, W, kv in zip(self.blocks, st["ops"]["layers"], st["caches"]):
+            _block_step(blk, W, linear, lambda q, o: attend(q, kv, o), x, x2, a, qkv, att, hid)
         _C.row_ln_scale(x, self.layer_norm.weight, self.layer_norm.bias, a, eps=self.layer_norm.eps)
         linear(a, st["ops"]["head"], st["logits"])
 
@@ -579,7 +591,7 @@ class RQTransformer(Prior):
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
                use_fp16: bool = True, *, seed: Optional[int] = None, forced_codes: Optional[torch.Tensor] = None, return_logits: bool = True,
                call: int = 0, row_offset: int = 0, slot0_ln: str = "once", graph: Optional[bool] = None,
-               weights: Optional[str] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+               weights: Optional[str] = None, cache: Optional[str] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """reference layers.py:397-547 (sample, sample_spatial_step, sample_depth_step) with one condition token: returns (logits [B T, D, V] f32
         after the temperature and the top-k mask, codes [B, T, D] int64).  GPT.sample's contract: the loop is restated per
         step, one row per batch element.  Per position t the spatial Blocks run under a cache of T slots on the input row
@@ -611,7 +623,11 @@ class RQTransformer(Prior):
         calls; while per-kernel timing is on (_C.TIMER) the loop runs.
 
         weights="fp8" is GPT.sample's: every Linear of every Block of BOTH stacks as its MXFP8 operand through enh_skinny_gemm_w8, the head in the
-        16-bit format; None reads ENH_SAMPLE_WEIGHTS (default "h16"); it needs use_fp16=True."""
+        16-bit format; None reads ENH_SAMPLE_WEIGHTS (default "h16"); it needs use_fp16=True.
+
+        cache="fp8" is GPT.sample's for the SPATIAL stack: its k / v caches are MXFP8 codes and scales behind enh_decode_attention_kv8 (DESIGN.md
+        §3.14); the depth caches (D <= 8 slots, enh_short_decode_attention) stay 16-bit.  None reads ENH_SAMPLE_CACHE (default "h16"); it needs
+        use_fp16=True."""
         if not (torch.is_tensor(conds) and conds.is_cuda):
             raise NotImplementedError("RQTransformer.sample: sampling runs on a ROCm device only: conds must be a device tensor (the spatial / depth "
                                       "decode loop is HIP kernels: there is no CPU path)")
@@ -639,10 +655,11 @@ class RQTransformer(Prior):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         dt = self._operand_dtype(use_fp16, "RQTransformer.sample")
         weights = self._sample_weights(weights, use_fp16, "RQTransformer.sample")
+        cache = self._sample_cache(cache, use_fp16, "RQTransformer.sample")
         codes = torch.empty(B, T, D, dtype=torch.int64, device=dev)
         logits = torch.empty(B * T, D, V, dtype=torch.float32, device=dev) if return_logits else None
         if self._use_graph(graph):
-            self._sample_graphed(B, dev, lambda b: self._decode_state(b, dt, dev, weights), lambda st, s, e, positions: self._sample_rows_graphed(
+            self._sample_graphed(B, dev, lambda b: self._decode_state(b, dt, dev, weights, cache), lambda st, s, e, positions: self._sample_rows_graphed(
                 st, positions, conds[s:e], codes[s:e], None if logits is None else logits.view(B, T, D, V)[s:e],
                 None if forced_codes is None else forced_codes[s:e], top_k, top_p, float(softmax_temperature), seed, call, row_offset + s,
                 slot0_ln == "twice", depth_decode == "cache"))
@@ -651,27 +668,27 @@ class RQTransformer(Prior):
             e = min(s + MAX_BATCH, B)
             self._sample_rows(conds[s:e], codes[s:e], None if logits is None else logits.view(B, T, D, V)[s:e],
                               None if forced_codes is None else forced_codes[s:e], dt, top_k, top_p, float(softmax_temperature), seed, call,
-                              row_offset + s, slot0_ln == "twice", depth_decode == "cache", weights)
+                              row_offset + s, slot0_ln == "twice", depth_decode == "cache", weights, cache)
         return logits, codes
 
-    def _decode_state(self, b: int, dt: torch.dtype, dev, weights: str = "h16") -> dict:
+    def _decode_state(self, b: int, dt: torch.dtype, dev, weights: str = "h16", cache: str = "h16") -> dict:
         """the buffers of one chunk of b <= 64 rows: the spatial and the depth residual stream, activations, the step's logits, every spatial
-        layer's k / v cache [b, Hs, T, C / Hs] and every depth layer's [b, Hd, D, C / Hd]; ops: the operands of `weights` (prior.py
-        `_sample_operands`)"""
+        layer's k / v cache [b, Hs, T, C / Hs] in the form of `cache` (prior.py `_kv_caches`) and every depth layer's [b, Hd, D, C / Hd], always
+        16-bit; ops: the operands of `weights` (prior.py `_sample_operands`)"""
         f32, C, T, D = torch.float32, self.embed_dim, self.img_num_tokens, self.depth_num_tokens
         Hs, Hd = self.spatial_n_heads, self.depth_n_heads
         e = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=dev)
         return dict(dt=dt, b=b, xs=e(b, C, dtype=f32), xd=e(b, C, dtype=f32), x2=e(b, C, dtype=f32), a=e(b, C), qkv=e(b, 3 * C), att=e(b, C),
                     hid=e(b, 4 * C), logits=e(b, self.vocab_img_size, dtype=f32),
-                    spatial=[(e(b, Hs, T, C // Hs), e(b, Hs, T, C // Hs)) for _ in self.spatial_transformer],
+                    spatial=_kv_caches(len(self.spatial_transformer), b, Hs, T, C // Hs, dt, dev, cache),
                     depth=[(e(b, Hd, D, C // Hd), e(b, Hd, D, C // Hd)) for _ in self.depth_transformer], ops=self._sample_operands(dt, weights))
 
     def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0, ln_twice: bool, depth_cache: bool,
-                     weights: str = "h16"):
+                     weights: str = "h16", cache: str = "h16"):
         """one chunk of b <= 64 rows: codes [b, T, D] (a view the draws are written into), logits [b, T, D, V] (a view) or None"""
         from ... import _C
         T, D = self.img_num_tokens, self.depth_num_tokens
-        st = self._decode_state(conds.shape[0], dt, conds.device, weights)
+        st = self._decode_state(conds.shape[0], dt, conds.device, weights, cache)
         feed = codes if forced is None else forced
         for t in range(T):
             self._spatial_step(st, t, conds if t == 0 else feed[:, t - 1, :])
@@ -714,15 +731,14 @@ class RQTransformer(Prior):
         if cursor is not None:
             C, D = self.embed_dim, self.depth_num_tokens
             _C.embed_step_at(self.tok_emb_code.weight.detach(), ids, D, D, -D, self.pos_emb_code.detach()[0], C, -C, cursor, 1, self.img_num_tokens, x)
-            attend = lambda q, kc, vc, o: _C.decode_attention_at(q, kc, vc, cursor, o)
         else:
             if t == 0:
                 _C.gpt_embed(self.tok_emb_cond.weight.detach(), ids, self.pos_emb_cond.detach()[0, 0], x)
             else:
                 _C.rq_embed_step(self.tok_emb_code.weight.detach(), ids, self.pos_emb_code.detach()[0, t - 1], x)
-            attend = lambda q, kc, vc, o: _C.decode_attention(q, kc, vc, t, o)
-        for blk, W, (kc, vc) in zip(self.spatial_transformer, st["ops"]["spatial"], st["spatial"]):
-            _block_step(blk, W, linear, lambda q, o: attend(q, kc, vc, o), x, x2, a, qkv, att, hid)
+        attend = _step_attention(t, cursor)
+        for blk, W, kv in zip(self.spatial_transformer, st["ops"]["spatial"], st["spatial"]):
+            _block_step(blk, W, linear, lambda q, o: attend(q, kv, o), x, x2, a, qkv, att, hid)
         _C.row_ln_scale(x, self.ln_spatial.weight, self.ln_spatial.bias, st["xd"], eps=self.ln_spatial.eps)
 
     def _depth_step(self, st: dict, t: Optional[int], d: int, ids: Optional[torch.Tensor], ln_twice: bool, depth_cache: bool,

@@ -1,6 +1,7 @@
 """What the stage-2 priors of layers.py (GPT, RQTransformer) and their optimizer (engine/optim.py GPTAdam) share, each stated once: the limits of
 the kernels, the launches of one Block over whole sequences forward (`_block_rows`) and backward (`_block_rows_backward`) with the products between
-them (`_row_linear`, `_grad_linears`), the launches of one Block in a cached sampling step (`_block_step`) and the product they run (`_step_linear`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`; MXFP8: `_layer_operands_fp8`), the flat parameter layout
+them (`_row_linear`, `_grad_linears`), the launches of one Block in a cached sampling step (`_block_step`) and the product they run (`_step_linear`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`; MXFP8: `_layer_operands_fp8`), the k / v caches of a sampling chunk and the attention over them (`_kv_caches`, `_step_attention`), the flat
+parameter layout
 (`flat_layout`), a layer's slice of the optimizer's operand arena (`ARENA_LAYER`), and `Prior`, the base class: init, input checks, the
 version-keyed operand cache, the one-chunk-at-a-time buffer cache and the two teacher-forced drivers (forward: chunks, cross-entropy rows, mean; forward_backward: chunks under the
 saved-activation cap, the loss scale, gradients set in the first chunk and added to in the later ones)."""
@@ -17,6 +18,7 @@ MAX_TOKENS = 8192       # enh_decode_attention: slots of the k / v cache
 FORWARD_HIDDEN_CAP = 2 << 30   # bytes of forward()'s [chunk T, 4C] hidden activation (f32 + operand copy): shipped size, 6 sequences per chunk
 OPERAND_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
 SAMPLE_WEIGHTS = ("h16", "fp8")      # sample(weights=): the Block weights of a decode step as 16-bit operands, or as MXFP8 codes and scales
+SAMPLE_CACHES = ("h16", "fp8")       # sample(cache=): the k / v caches of the long decode attention as 16-bit tensors, or as MXFP8 codes and scales
 
 # one layer's slice of GPTAdam's 16-bit operand arena: (operand, the Linear masters that are its row blocks, offset / C^2, rows / C, cols / C)
 ARENA_LAYER = (("wqkv", ("attn.query", "attn.key", "attn.value"), 0, 3, 1), ("wproj", ("attn.proj",), 3, 1, 1), ("w0", ("mlp.p0",), 4, 4, 1),
@@ -163,6 +165,26 @@ def _block_rows(blk, W, linear, dt, S: int, attention, x, x_out, a, a2, qkv, att
         linear(a2, W["w0"], hid32, bias=blk.mlp.p0.bias)
         _C.relu_sq(hid, hid32)
         linear(hid, W["w1"], x_out, bias=blk.mlp.p1.bias, res=x2)
+
+
+def _kv_caches(n_layers: int, b: int, H: int, T: int, hs: int, dt: torch.dtype, dev, cache: str) -> list:
+    """per layer the k / v cache of enh_decode_attention: under "h16" the pair (k, v) [b, H, T, hs] in the operand format, under "fp8" the MXFP8
+    form (k_codes, k_scales, v_codes, v_scales), codes [b, H, T, hs] and scales [b, H, T, hs / 32] uint8 (include/enh_hip.h): no 16-bit tensor"""
+    if cache != "fp8":
+        return [(torch.empty(b, H, T, hs, dtype=dt, device=dev), torch.empty(b, H, T, hs, dtype=dt, device=dev)) for _ in range(n_layers)]
+    from ... import _C
+    u8 = lambda n: torch.empty(b, H, T, n, dtype=torch.uint8, device=dev)
+    return [(u8(hs), u8(hs // _C.MX_BLOCK), u8(hs), u8(hs // _C.MX_BLOCK)) for _ in range(n_layers)]
+
+
+def _step_attention(t, cursor=None):
+    """attend(qkv, kv, out), the attention of a cached sampling step over the long cache `kv` of one layer (`_kv_caches`), at step t or, in the
+    cursor form, at the step the device int32 `cursor` holds: enh_decode_attention for a 16-bit (k, v) pair, enh_decode_attention_kv8 for the four
+    tensors of an MXFP8 cache"""
+    from ... import _C
+    if cursor is not None:
+        return lambda q, kv, o: (_C.decode_attention_kv8_at if len(kv) == 4 else _C.decode_attention_at)(q, *kv, cursor, o)
+    return lambda q, kv, o: (_C.decode_attention_kv8 if len(kv) == 4 else _C.decode_attention)(q, *kv, t, o)
 
 
 def _block_step(blk, W, linear, attention, x, x2, a, qkv, att, hid) -> None:
@@ -342,6 +364,17 @@ class Prior(nn.Module):
         if weights == "fp8" and not use_fp16:
             raise ValueError(f"{who}: weights=\"fp8\" streams MXFP8 weights against 16-bit activations; the exact mode (use_fp16=False) has no such form")
         return weights
+
+    @staticmethod
+    def _sample_cache(cache, use_fp16: bool, who: str) -> str:
+        """sample(cache=): None reads ENH_SAMPLE_CACHE (default "h16"); "fp8" needs the 16-bit mode (q and the step's k / v rows are 16-bit)"""
+        if cache is None:
+            cache = os.environ.get("ENH_SAMPLE_CACHE", "h16")
+        if cache not in SAMPLE_CACHES:
+            raise ValueError(f"{who}: cache (or ENH_SAMPLE_CACHE) must be one of {SAMPLE_CACHES}, got {cache!r}")
+        if cache == "fp8" and not use_fp16:
+            raise ValueError(f"{who}: cache=\"fp8\" quantizes 16-bit k / v rows into an MXFP8 cache; the exact mode (use_fp16=False) has no such form")
+        return cache
 
     def _sample_operands(self, dt: torch.dtype, weights: str):
         """the operands of sample(): `_operand_copies(dt)`, or under weights == "fp8" the MXFP8 form, where every Linear of every Block is a

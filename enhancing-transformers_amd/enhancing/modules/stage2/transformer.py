@@ -58,7 +58,7 @@ class CondTransformer(nn.Module):
                use_fp16: bool = True, **kw) -> torch.Tensor:
         """reference transformer.py:78-95, for both priors: GPT draws codes [B, T], RQTransformer [B, T, D] (for a residual tokenizer), and
         `code_shape` is applied to them as the reference does (e.g. [32, 32] or [32, 32, 4]).  **kw goes to the prior's sample (seed, forced_codes,
-        slot0_ln, ...).  The drawn codes are kept in `last_codes`.  An RQ prior that is off the device refuses (sampling runs on a ROCm device only)."""
+        slot0_ln, graph, weights, cache, ...).  The drawn codes are kept in `last_codes`.  An RQ prior that is off the device refuses (sampling runs on a ROCm device only)."""
         conds = conds.view(conds.shape[0], -1)
         kw.setdefault("return_logits", False)
         _, codes = self.transformer.sample(conds=conds, top_k=top_k, top_p=top_p, softmax_temperature=softmax_temperature, use_fp16=use_fp16, **kw)

@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 31  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 32  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -645,6 +645,28 @@ int enh_mxfp8_quantize(const float* w, int64_t N, int64_t K, int64_t w_row_strid
  * two as it is added to the f32 sum: the scale costs no accuracy.  The codes and scales are read exactly once. */
 int enh_skinny_gemm_w8(const enh_h16* x, const uint8_t* codes, const uint8_t* scales, int64_t M, int64_t N, int64_t K, const float* bias, int act,
                        const float* res, float* out_f32, enh_h16* out_h16, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 sampling with an MXFP8 k / v cache (csrc/gpt_decode_kv8.hip): enh_decode_attention over caches held in the operand format above, with
+ * the blocks of 32 running along the head dimension.  The cache layout, fixed: per layer four row-major uint8 tensors,
+ *   k_codes, v_codes   [B, H, Tmax, hs]       e4m3fn codes,
+ *   k_scales, v_scales [B, H, Tmax, hs / 32]  E8M0, one per 32 consecutive elements of a head row,
+ * 1 + 1/32 bytes per element instead of 2, and K[b, h, j, d] = e4m3(k_codes[b, h, j, d]) 2^(k_scales[b, h, j, d / 32] - 127).
+ * The step's k and v rows (the 16-bit values of qkv, widened to f32) are quantized with enh_mxfp8_quantize's rounding and appended at slot t, and the
+ * step's own attention reads slot t through those quantized values: out = softmax(q K[0..t]^T / sqrt(hs)) V[0..t] over the dequantized cache as
+ * stored, so a slot contributes the same k / v to every step that reads it (enh_decode_attention takes slot t unquantized from qkv).  q stays
+ * 16-bit; scores, softmax and P V accumulate in f32; dequantization is exact.  Slots > t are neither read nor written.
+ * No float atomics; the same bits on every run.
+ * ------------------------------------------------------------------------------------------------ */
+/* qkv [B, 3C] and out [B, C] in the 16-bit format of dtype (ENH_DT_BF16 | ENH_DT_F16 only); hs a multiple of 64 up to 384, Tmax <= 8192,
+ * 0 <= t < Tmax; qkv and the code tensors 16-byte aligned.  The pieces, the workspace (enh_decode_attention_workspace_bytes) and the ascending merge
+ * are enh_decode_attention's. */
+int enh_decode_attention_kv8(const void* qkv, uint8_t* k_codes, uint8_t* k_scales, uint8_t* v_codes, uint8_t* v_scales, int B, int H, int hs, int Tmax,
+                             int t, void* out, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+/* the cursor form (see enh_decode_attention_at below): t = *cursor + t_offset read on the device, the same bits at the same t; the workspace is
+ * always required; t outside [0, Tmax): nothing is read or written. */
+int enh_decode_attention_kv8_at(const void* qkv, uint8_t* k_codes, uint8_t* k_scales, uint8_t* v_codes, uint8_t* v_scales, int B, int H, int hs,
+                                int Tmax, const int* cursor, int t_offset, void* out, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stage-2 GPT, teacher-forced forward (csrc/gpt_prefill.hip: the attention, csrc/gpt_rows.hip: the row kernels; reference enhancing/modules/stage2/layers.py:57-97,132-136,193-211 with

@@ -13,7 +13,11 @@ cache), median, minimum and maximum of 7 windows that alternate between the two 
 
 --weights fp8 writes profiles/gpt_sample_fp8.txt instead: the step with MXFP8 Block weights (sample(weights="fp8")) against the
 16-bit step at batch 1, 4 and 16, alternating windows in this process, and the five products alone in both forms with the TB/s of the bytes each
-actually moves."""
+actually moves.
+
+--cache fp8 writes profiles/gpt_sample_kv8.txt instead: the step with MXFP8 k / v caches (sample(cache="fp8")) against the step
+with 16-bit caches at batch 1, 4, 16 and 64, alternating windows in this process, under the weights of --weights (h16 or fp8: with fp8 the file is
+profiles/gpt_sample_kv8_w8.txt), and the decode attention alone in both forms with the TB/s of the bytes each actually moves."""
 import argparse
 import math
 import os
@@ -210,6 +214,78 @@ def fp8_mode(m, L, out):
         f.write(text)
 
 
+def _fill_kv(kv, gen_scale=0.5):
+    """random cache contents: 16-bit tensors N(0, 0.5); MXFP8 codes without the NaN code (bit 3 cleared) under scales around 2^-7"""
+    if len(kv) == 2:
+        for z in kv:
+            z.normal_(0, gen_scale)
+        return
+    for codes, scales in (kv[:2], kv[2:]):
+        codes.random_(0, 256).bitwise_and_(0xF7)
+        scales.random_(118, 122)
+
+
+def kv8_mode(m, L, out, weights):
+    """--cache fp8: the step with MXFP8 caches against the step with 16-bit caches, and the decode attention alone; writes profiles/gpt_sample_kv8*.txt"""
+    from enhancing.modules.stage2.prior import _kv_caches
+    C, V, T, H = m.embed_dim, m.vocab_img_size, m.img_num_tokens, m.n_heads
+    hs, dt = C // H, torch.float16
+    wb = (12 * C * C * L + V * C) * 2 if weights == "h16" else 12 * C * C * L + 12 * C * C * L // 32 + V * C * 2
+    kv16 = lambda b, n: 2 * L * b * n * C * 2
+    kv8 = lambda b, n: 2 * L * b * n * (C + C // 32)
+    lines = [f"stage-2 GPT sampling step, MXFP8 k / v caches against 16-bit caches, on {torch.cuda.get_device_name(0)}: C={C} layers={L} heads={H} V={V}, "
+             f"fp16 activations, {'16-bit' if weights == 'h16' else 'MXFP8'} Block weights ({wb / 1e9:.2f} GB per step)",
+             f"caches held at T={T}, batch 64: {kv16(64, T) / 1e9:.1f} GB (16-bit) / {kv8(64, T) / 1e9:.1f} GB (fp8: codes + scales)",
+             "times: median [min .. max] of 7 alternating windows in one process; a step window is 10 steps, a kernel window is 100 launches over 2 to 16",
+             "rotating cache buffers (0.4 GB in all at batch 1, >= 1 GB from batch 4); kernel times are event times over back-to-back launches: they include the launch boundary (~1-2 us each)",
+             f"{'batch':>5} {'cache':>5} {'16-bit ms [min .. max]':>28} {'fp8 ms [min .. max]':>28} {'16-bit/fp8':>10} {'beyond spread':>13} {'kv GB 16':>8} {'kv GB fp8':>9}"]
+    f3 = lambda v: f"{v[1]:.3f} [{v[0]:.3f} .. {v[2]:.3f}]"
+    f1 = lambda v: f"{v[1] * 1e3:.1f} [{v[0] * 1e3:.1f} .. {v[2] * 1e3:.1f}]"
+    for b in (1, 4, 16, 64):
+        sts = {c: m._decode_state(b, dt, "cuda", weights=weights, cache=c) for c in ("h16", "fp8")}
+        for st in sts.values():
+            for kv in st["caches"]:
+                _fill_kv(kv)
+        codes = torch.randint(0, V, (b, T), device="cuda")
+        for n in (1, 512, 1024):
+            t = n - 1
+
+            def step(c):
+                def run(i):
+                    m._decode_step(sts[c], t, codes[:, t - 1] if t else codes[:, 0] % 1000)
+                    _C.sample_logits(sts[c]["logits"], codes[:, t], top_k=None, top_p=None, seed=1, step=t)
+                return run
+            h, f = ab(step("h16"), step("fp8"), inner=10)
+            lines.append(f"{b:>5} {n:>5} {f3(h):>28} {f3(f):>28} {h[1] / f[1]:>10.3f} {'yes' if f[2] < h[0] else 'no':>13} {kv16(b, n) / 1e9:>8.2f} "
+                         f"{kv8(b, n) / 1e9:>9.2f}")
+        del sts
+        torch.cuda.empty_cache()
+    lines.append("beyond spread: the slowest fp8 window is faster than the fastest 16-bit window of the same point")
+    lines.append("decode attention alone (one layer, fp16 q), us: median [min .. max]; TB/s of the cache bytes each form reads; kept = fp8 TB/s / 16-bit TB/s:")
+    for b in (1, 4, 16, 64):
+        per16 = 2 * b * T * C * 2
+        nbuf = max(2, min(16, -(-(1 << 30) // per16)))
+        qkv = torch.randn(b, 3 * C, device="cuda").half()
+        o = torch.empty(b, C, device="cuda").half()
+        c16 = _kv_caches(nbuf, b, H, T, hs, dt, "cuda", "h16")
+        c8 = _kv_caches(nbuf, b, H, T, hs, dt, "cuda", "fp8")
+        for kv in c16 + c8:
+            _fill_kv(kv)
+        for n in (1, 512, 1024):
+            by16, by8 = 2 * b * n * C * 2, 2 * b * n * (C + C // 32)
+            d, f = ab(lambda i: _C.decode_attention(qkv, *c16[i % nbuf], n - 1, o), lambda i: _C.decode_attention_kv8(qkv, *c8[i % nbuf], n - 1, o), inner=100)
+            t16, t8 = by16 / d[1] / 1e9, by8 / f[1] / 1e9
+            lines.append(f"  decode_attention B={b:<2} len={n:<4}: 16-bit {f1(d):>24} us {by16 / 1e6:7.1f} MB {t16:5.2f} TB/s   fp8 {f1(f):>24} us {by8 / 1e6:7.1f} MB "
+                         f"{t8:5.2f} TB/s   time {d[1] / f[1]:5.2f}x   kept {t8 / t16:4.2f}")
+        del c16, c8
+        torch.cuda.empty_cache()
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -219,9 +295,14 @@ def main():
                     "(profiles/gpt_sample_graph.txt)")
     ap.add_argument("--weights", choices=("h16", "fp8"), default="h16", help="fp8: instead of the tables, the MXFP8-weight step against the 16-bit "
                     "step and the products alone (profiles/gpt_sample_fp8.txt)")
+    ap.add_argument("--cache", choices=("h16", "fp8"), default="h16", help="fp8: instead of the tables, the step with MXFP8 k / v caches against the step "
+                    "with 16-bit caches under the weights of --weights, and the decode attention alone (profiles/gpt_sample_kv8.txt, with --weights fp8 "
+                    "profiles/gpt_sample_kv8_w8.txt)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "gpt_sample_graph.txt" if args.graph else "gpt_sample_fp8.txt" if args.weights == "fp8" else "gpt_sample.txt")
+        name = ("gpt_sample_graph.txt" if args.graph else ("gpt_sample_kv8_w8.txt" if args.weights == "fp8" else "gpt_sample_kv8.txt") if args.cache == "fp8"
+                else "gpt_sample_fp8.txt" if args.weights == "fp8" else "gpt_sample.txt")
+        args.out = os.path.join(ROOT, "profiles", name)
     C, H, V, T, L = 6144, 16, 8192, 1024, args.layers
     torch.manual_seed(0)
     with torch.device("cuda"):
@@ -230,6 +311,8 @@ def main():
             m.pos_emb_code.normal_(0, 0.02)
     if args.graph:
         return graph_mode(m, L, args.out)
+    if args.cache == "fp8":
+        return kv8_mode(m, L, args.out, args.weights)
     if args.weights == "fp8":
         return fp8_mode(m, L, args.out)
     dt = torch.float16

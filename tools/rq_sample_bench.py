@@ -15,7 +15,10 @@ of every path.  Not 1024 positions: a few positions per fill.
 the same fills (tools/sample_graph_bench.py), then one whole image through sample() both ways.
 
 --weights fp8 writes profiles/rq_sample_fp8.txt instead: one position with MXFP8 Block weights in both stacks (sample(weights="fp8"), DESIGN.md
-§3.13) against the 16-bit position at batch 1 and 4 and the same fills, alternating windows in this process."""
+§3.13) against the 16-bit position at batch 1 and 4 and the same fills, alternating windows in this process.
+
+--cache fp8 writes profiles/rq_sample_kv8.txt instead: one position with MXFP8 spatial k / v caches (sample(cache="fp8")) against
+the position with 16-bit caches at batch 1, 4 and 64 and the same fills, alternating windows in this process."""
 import argparse
 import math
 import os
@@ -241,6 +244,55 @@ def fp8_mode(kw, out):
         f.write(text)
 
 
+def kv8_mode(kw, out):
+    """--cache fp8: one position (the spatial step, the D depth steps, their draws) with MXFP8 spatial k / v caches against 16-bit caches"""
+    C, V, T, D = kw["embed_dim"], kw["vocab_img_size"], kw["img_num_tokens"], kw["depth_num_tokens"]
+    Ls, Ld = kw["spatial_n_layers"], kw["depth_n_layers"]
+    dt = torch.float16
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        m = RQTransformer(**kw)
+        with torch.no_grad():
+            for p in (m.pos_emb_cond, m.pos_emb_code, m.pos_emb_depth):
+                p.normal_(0, 0.02)
+    f3 = lambda v: f"{v[1]:.3f} [{v[0]:.3f} .. {v[2]:.3f}]"
+    held = lambda b, per: 2 * Ls * b * T * per
+    lines = [f"stage-2 RQTransformer sampling, MXFP8 spatial k / v caches against 16-bit caches, on {torch.cuda.get_device_name(0)}: C={C} spatial layers={Ls} "
+             f"depth layers={Ld} T={T} D={D} V={V}, fp16 activations, 16-bit weights; the depth caches ({D} slots) are 16-bit in both",
+             f"spatial caches held at batch 64: {held(64, 2 * C) / 1e9:.2f} GB (16-bit) / {held(64, C + C // 32) / 1e9:.2f} GB (fp8: codes + scales)",
+             "ms per position (spatial step + the D depth steps with their draws): median [min .. max] of 7 alternating windows of 10 positions in one process",
+             f"{'batch':>5} {'slot':>5} {'16-bit ms [min .. max]':>28} {'fp8 ms [min .. max]':>28} {'16-bit/fp8':>10} {'beyond spread':>13} {'launches':>8}"]
+    for b in (1, 4, 64):
+        sts = {c: m._decode_state(b, dt, "cuda", "h16", c) for c in ("h16", "fp8")}
+        for kv in sts["h16"]["spatial"]:
+            for z in kv:
+                z.normal_(0, 0.5)
+        for kv in sts["fp8"]["spatial"]:
+            for codes8, scales in (kv[:2], kv[2:]):
+                codes8.random_(0, 256).bitwise_and_(0xF7)      # no NaN code
+                scales.random_(118, 122)
+        codes = torch.randint(0, V, (b, T, D), device="cuda")
+        for t in (1, 256, 512, T - 1):
+            def position(c):
+                def run(i):
+                    m._spatial_step(sts[c], t, codes[:, t - 1, :])
+                    for d in range(D):
+                        m._depth_step(sts[c], t, d, None if d == 0 else codes[:, t, :d], False, False)
+                        _C.sample_logits(sts[c]["logits"], codes[:, t, d], top_k=None, top_p=None, seed=1, step=t * D + d)
+                return run
+            h, f = alternate([position("h16"), position("fp8")], inner=10)
+            n_sp, n_dp = launches_per_position(b, C, V, D, Ls, Ld, t)
+            lines.append(f"{b:>5} {t:>5} {f3(h):>28} {f3(f):>28} {h[1] / f[1]:>10.3f} {'yes' if f[2] < h[0] else 'no':>13} {n_sp + n_dp:>8}")
+        del sts
+        torch.cuda.empty_cache()
+    lines.append("beyond spread: the slowest fp8 window is faster than the fastest 16-bit window of the same point")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -250,14 +302,19 @@ def main():
     ap.add_argument("--whole", type=int, default=1, help="--graph: also draw one whole image through sample() both ways")
     ap.add_argument("--weights", choices=("h16", "fp8"), default="h16", help="fp8: instead of the tables, one position with MXFP8 Block weights "
                     "against 16-bit weights (profiles/rq_sample_fp8.txt)")
+    ap.add_argument("--cache", choices=("h16", "fp8"), default="h16", help="fp8: instead of the tables, one position with MXFP8 spatial k / v caches "
+                    "against 16-bit caches (profiles/rq_sample_kv8.txt)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "rq_sample_graph.txt" if args.graph else "rq_sample_fp8.txt" if args.weights == "fp8" else "rq_sample.txt")
+        args.out = os.path.join(ROOT, "profiles", "rq_sample_graph.txt" if args.graph else "rq_sample_kv8.txt" if args.cache == "fp8" else
+                                "rq_sample_fp8.txt" if args.weights == "fp8" else "rq_sample.txt")
     kw = dict(get_config_from_file(os.path.join(ROOT, "configs", "imagenet_rqtransformer_rqvae_base.yaml")).model.params.transformer.params)
     if args.spatial_layers is not None:
         kw["spatial_n_layers"] = args.spatial_layers
     if args.graph:
         return graph_mode(kw, args.out, bool(args.whole))
+    if args.cache == "fp8":
+        return kv8_mode(kw, args.out)
     if args.weights == "fp8":
         return fp8_mode(kw, args.out)
     C, V, T, D = kw["embed_dim"], kw["vocab_img_size"], kw["img_num_tokens"], kw["depth_num_tokens"]

@@ -1,5 +1,5 @@
 """Class-conditional image sampling with a stage-2 config:  python tools/sample_images.py -c configs/imagenet_gpt_vitvq_base.yaml --ckpt last.ckpt
---classes 207 360 --top_k 100 --top_p 0.95 --temperature 1.0 --seed 0 [--graph] [--weights fp8] --out samples.png
+--classes 207 360 --top_k 100 --top_p 0.95 --temperature 1.0 --seed 0 [--graph] [--weights fp8] [--cache fp8] --out samples.png
 
 Builds the config's CondTransformer (condition model, stage-1 tokenizer, and the prior: GPT, or RQTransformer over a residual tokenizer as in
 configs/imagenet_rqtransformer_rqvae_base.yaml), loads `--ckpt` (a {"state_dict": ...} file; without it the config's own `path` entries or the
@@ -31,6 +31,8 @@ def main(argv=None):
                     "the same codes); without it ENH_GRAPHS=1 decides")
     ap.add_argument("--weights", choices=("h16", "fp8"), default=None, help="fp8: stream the Block weights as MXFP8 operands (sample(weights=\"fp8\"): half "
                     "the weight bytes of a step and of the operand copies); without it ENH_SAMPLE_WEIGHTS decides (default h16)")
+    ap.add_argument("--cache", choices=("h16", "fp8"), default=None, help="fp8: hold the k / v caches as MXFP8 codes and scales (sample(cache=\"fp8\"): half "
+                    "the cache bytes of a step and of device memory); without it ENH_SAMPLE_CACHE decides (default h16)")
     ap.add_argument("--nrow", type=int, default=4)
     ap.add_argument("--out", default="samples.png")
     args = ap.parse_args(argv)
@@ -42,7 +44,7 @@ def main(argv=None):
         model.init_from_ckpt(args.ckpt)
     conds = torch.tensor(args.classes, dtype=torch.int64, device="cuda")
     img = model.sample(conds, top_k=args.top_k, top_p=args.top_p, softmax_temperature=args.temperature, use_fp16=not args.fp32, seed=args.seed,
-                       graph=True if args.graph else None, weights=args.weights)
+                       graph=True if args.graph else None, weights=args.weights, cache=args.cache)
     from PIL import Image
     grid = make_grid(img.float().cpu(), nrow=args.nrow)
     Image.fromarray((grid.permute(1, 2, 0).numpy() * 255).astype(np.uint8)).save(args.out)
