@@ -140,6 +140,9 @@ SIGNATURES = {
     "enh_skinny_gemm_f32": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
     "enh_mxfp8_quantize": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "enh_skinny_gemm_w8": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
+    "enh_mxfp4_quantize": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "enh_skinny_gemm_w4_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "enh_skinny_gemm_w4": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
     "enh_causal_attention_forward": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp]),
     "enh_causal_attention_forward_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
     "enh_ln_timeshift": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _i32, _vp]),
@@ -172,7 +175,7 @@ SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 32 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 33 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -1087,7 +1090,7 @@ def skinny_gemm(x, w, out, bias=None, relu_sq: bool = False, res=None):
 
 
 U8 = torch.uint8
-MX_BLOCK = 32        # k per E8M0 scale of an MXFP8 operand (include/enh_hip.h)
+MX_BLOCK = 32        # k per E8M0 scale of an MXFP8 or MXFP4 operand (include/enh_hip.h)
 
 
 def quantize_mxfp8(w, codes, scales, row0: int = 0):
@@ -1126,6 +1129,45 @@ def skinny_gemm_w8(x, codes, scales, out, bias=None, relu_sq: bool = False, res=
            lambda: _check(L.enh_skinny_gemm_w8(_p(x, H16, "x"), _p(codes, U8, "codes"), _p(scales, U8, "scales"), M, N, K, _p(bias, F32, "bias"),
                                                ACT_RELU_SQ if relu_sq else 0, _p(res, F32, "res"), _p(o32, F32, "out"), _p(o16, H16, "out"), _p(ws), nb,
                                                _dt(x, o16), _stream()), "enh_skinny_gemm_w8"), unit="byte")
+
+
+def quantize_mxfp4(w, codes, scales, row0: int = 0):
+    """the MXFP4 operand of a weight (enh_mxfp4_quantize): w [N, K] f32, K % 32 == 0, rows contiguous (any row stride that keeps them 16-byte
+    aligned) -> rows row0 .. row0 + N - 1 of codes [Nt, K / 2] uint8 (two e2m1 codes per byte, k even in the low nibble) and scales [Nt, K / 32]
+    uint8 (E8M0); the other rows are not touched"""
+    if w.dim() != 2 or codes.dim() != 2 or scales.dim() != 2:
+        raise RuntimeError(f"quantize_mxfp4: w {tuple(w.shape)} codes {tuple(codes.shape)} scales {tuple(scales.shape)} must be matrices")
+    N, K = w.shape
+    if K % MX_BLOCK or codes.shape[1] != K // 2 or tuple(scales.shape) != (codes.shape[0], K // MX_BLOCK) or row0 < 0 or row0 + N > codes.shape[0]:
+        raise RuntimeError(f"quantize_mxfp4: w {tuple(w.shape)} codes {tuple(codes.shape)} scales {tuple(scales.shape)} row0 {row0} do not fit "
+                           f"(K must be a multiple of {MX_BLOCK}, codes [rows, K / 2], scales [rows, K / {MX_BLOCK}])")
+    if not w.is_cuda or w.dtype != F32 or (K > 1 and w.stride(1) != 1):
+        raise RuntimeError(f"quantize_mxfp4: w must be an f32 device tensor whose rows are contiguous, got {w.dtype} on {w.device} strides {w.stride()}")
+    stride = w.stride(0) if N > 1 else K
+    # bytes moved: the masters once, the codes and the scales
+    _timed(None, 4.0 * N * K + N * (K // 2) + N * (K // MX_BLOCK),
+           lambda: _check(lib().enh_mxfp4_quantize(ctypes.c_void_p(w.data_ptr()), N, K, int(stride), _p(codes, U8, "codes"), int(row0),
+                                                   _p(scales, U8, "scales"), int(row0), _stream()), "enh_mxfp4_quantize"), unit="byte")
+
+
+def skinny_gemm_w4(x, codes, scales, out, bias=None, relu_sq: bool = False, res=None):
+    """skinny_gemm with the weight given as its MXFP4 operand (enh_skinny_gemm_w4): out[M,N] = act(x[M,K] dequant(codes, scales)^T + bias) (+ res);
+    x 16-bit, codes [N, K / 2] uint8, scales [N, K / 32] uint8, M <= 64, N % 8 == 0, K % 32 == 0; out f32 or x's 16-bit format"""
+    M, K = x.shape
+    N = codes.shape[0]
+    if (codes.dim() != 2 or K % MX_BLOCK or codes.shape[1] != K // 2 or tuple(scales.shape) != (N, K // MX_BLOCK) or tuple(out.shape) != (M, N)
+            or (res is not None and tuple(res.shape) != (M, N)) or (bias is not None and bias.numel() != N)):
+        raise RuntimeError(f"skinny_gemm_w4: x {tuple(x.shape)} codes {tuple(codes.shape)} scales {tuple(scales.shape)} out {tuple(out.shape)} do not fit "
+                           f"(K must be a multiple of {MX_BLOCK}, codes [N, K / 2], scales [N, K / {MX_BLOCK}])")
+    L = lib()
+    nb = L.enh_skinny_gemm_w4_workspace_bytes(M, N, K)
+    ws = _workspace(nb, x.device) if nb else None
+    o32, o16 = (out, None) if out.dtype == F32 else (None, out)
+    # bytes moved: the codes and the scales once, x, the result
+    _timed(None, 0.5 * N * K + float(N) * (K // MX_BLOCK) + 2.0 * M * K + float(out.element_size()) * M * N,
+           lambda: _check(L.enh_skinny_gemm_w4(_p(x, H16, "x"), _p(codes, U8, "codes"), _p(scales, U8, "scales"), M, N, K, _p(bias, F32, "bias"),
+                                               ACT_RELU_SQ if relu_sq else 0, _p(res, F32, "res"), _p(o32, F32, "out"), _p(o16, H16, "out"), _p(ws), nb,
+                                               _dt(x, o16), _stream()), "enh_skinny_gemm_w4"), unit="byte")
 
 
 def decode_attention(qkv, k_cache, v_cache, t: int, out):

@@ -1,11 +1,12 @@
 """What the stage-2 priors of layers.py (GPT, RQTransformer) and their optimizer (engine/optim.py GPTAdam) share, each stated once: the limits of
 the kernels, the launches of one Block over whole sequences forward (`_block_rows`) and backward (`_block_rows_backward`) with the products between
-them (`_row_linear`, `_grad_linears`), the launches of one Block in a cached sampling step (`_block_step`) and the product they run (`_step_linear`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`; MXFP8: `_layer_operands_fp8`), the k / v caches of a sampling chunk and the attention over them (`_kv_caches`, `_step_attention`), the flat
+them (`_row_linear`, `_grad_linears`), the launches of one Block in a cached sampling step (`_block_step`) and the product they run (`_step_linear`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`; MXFP8 and MXFP4: `_layer_operands_mx`), the k / v caches of a sampling chunk and the attention over them (`_kv_caches`, `_step_attention`), the flat
 parameter layout
 (`flat_layout`), a layer's slice of the optimizer's operand arena (`ARENA_LAYER`), and `Prior`, the base class: init, input checks, the
 version-keyed operand cache, the one-chunk-at-a-time buffer cache and the two teacher-forced drivers (forward: chunks, cross-entropy rows, mean; forward_backward: chunks under the
 saved-activation cap, the loss scale, gradients set in the first chunk and added to in the later ones)."""
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -17,7 +18,8 @@ MAX_HEAD = 384          # enh_decode_attention
 MAX_TOKENS = 8192       # enh_decode_attention: slots of the k / v cache
 FORWARD_HIDDEN_CAP = 2 << 30   # bytes of forward()'s [chunk T, 4C] hidden activation (f32 + operand copy): shipped size, 6 sequences per chunk
 OPERAND_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
-SAMPLE_WEIGHTS = ("h16", "fp8")      # sample(weights=): the Block weights of a decode step as 16-bit operands, or as MXFP8 codes and scales
+SAMPLE_WEIGHTS = ("h16", "fp8", "fp4")      # sample(weights=): the Block weights of a decode step as 16-bit operands, or as MXFP8 / MXFP4 codes and scales
+QUANT_WEIGHTS = {"fp8": "MXFP8", "fp4": "MXFP4"}
 SAMPLE_CACHES = ("h16", "fp8")       # sample(cache=): the k / v caches of the long decode attention as 16-bit tensors, or as MXFP8 codes and scales
 
 # one layer's slice of GPTAdam's 16-bit operand arena: (operand, the Linear masters that are its row blocks, offset / C^2, rows / C, cols / C)
@@ -87,26 +89,49 @@ def _mxfp8_operand(masters) -> tuple:
     return codes, scales
 
 
-def _layer_operands_fp8(blocks) -> list:
-    """`_layer_operands` with every Linear weight as its MXFP8 operand, a (codes, scales) pair; biases and time_mix stay f32"""
+class MXFP4(NamedTuple):
+    """the MXFP4 operand of a weight [N, K] (include/enh_hip.h): codes [N, K / 2] uint8, two e2m1 codes per byte, and scales [N, K / 32] uint8"""
+    codes: torch.Tensor
+    scales: torch.Tensor
+
+
+def _mxfp4_operand(masters) -> MXFP4:
+    """`_mxfp8_operand` in the 4-bit format: quantized on the device straight from the f32 `masters`, no 16-bit or 8-bit copy is ever made"""
+    from ... import _C
+    K = masters[0].shape[1]
+    N = sum(m.shape[0] for m in masters)
+    codes = torch.empty(N, K // 2, dtype=torch.uint8, device=masters[0].device)
+    scales = torch.empty(N, K // _C.MX_BLOCK, dtype=torch.uint8, device=masters[0].device)
+    row0 = 0
+    for m in masters:
+        _C.quantize_mxfp4(m.detach(), codes, scales, row0=row0)
+        row0 += m.shape[0]
+    return MXFP4(codes, scales)
+
+
+def _layer_operands_mx(blocks, operand) -> list:
+    """`_layer_operands` with every Linear weight through `operand` (`_mxfp8_operand`: a (codes, scales) pair, `_mxfp4_operand`: an MXFP4); biases
+    and time_mix stay f32"""
     layers = []
     for blk in blocks:
         a, m = blk.attn, blk.mlp
-        layers.append(dict(wqkv=_mxfp8_operand([a.query.weight, a.key.weight, a.value.weight]), bqkv=qkv_bias(a), wproj=_mxfp8_operand([a.proj.weight]),
-                           w0=_mxfp8_operand([m.p0.weight]), w1=_mxfp8_operand([m.p1.weight]), time_mix=a.time_mix.detach().reshape(-1).contiguous()))
+        layers.append(dict(wqkv=operand([a.query.weight, a.key.weight, a.value.weight]), bqkv=qkv_bias(a), wproj=operand([a.proj.weight]),
+                           w0=operand([m.p0.weight]), w1=operand([m.p1.weight]), time_mix=a.time_mix.detach().reshape(-1).contiguous()))
     return layers
 
 
 # ---- the products --------------------------------------------------------------------------------------------------------------------------
 def _step_linear(dt: torch.dtype):
     """linear(inp, w, out, bias, relu_sq, res), the product of a cached sampling step (M <= 64 rows), chosen by the operand it is given: the exact
-    mode's f32 form, enh_skinny_gemm_h16 for a 16-bit weight, enh_skinny_gemm_w8 for an MXFP8 (codes, scales) pair"""
+    mode's f32 form, enh_skinny_gemm_h16 for a 16-bit weight, enh_skinny_gemm_w8 for an MXFP8 (codes, scales) pair, enh_skinny_gemm_w4 for an MXFP4"""
     from ... import _C
     if dt == torch.float32:
         return _C.skinny_gemm_f32
 
     def linear(inp, w, out, bias=None, relu_sq=False, res=None):
-        if isinstance(w, tuple):
+        if isinstance(w, MXFP4):
+            _C.skinny_gemm_w4(inp, w.codes, w.scales, out, bias=bias, relu_sq=relu_sq, res=res)
+        elif isinstance(w, tuple):
             _C.skinny_gemm_w8(inp, w[0], w[1], out, bias=bias, relu_sq=relu_sq, res=res)
         else:
             _C.skinny_gemm(inp, w, out, bias=bias, relu_sq=relu_sq, res=res)
@@ -356,13 +381,13 @@ class Prior(nn.Module):
 
     @staticmethod
     def _sample_weights(weights, use_fp16: bool, who: str) -> str:
-        """sample(weights=): None reads ENH_SAMPLE_WEIGHTS (default "h16"); "fp8" needs the 16-bit mode (its activations are 16-bit operands)"""
+        """sample(weights=): None reads ENH_SAMPLE_WEIGHTS (default "h16"); "fp8" and "fp4" need the 16-bit mode (their activations are 16-bit operands)"""
         if weights is None:
             weights = os.environ.get("ENH_SAMPLE_WEIGHTS", "h16")
         if weights not in SAMPLE_WEIGHTS:
             raise ValueError(f"{who}: weights (or ENH_SAMPLE_WEIGHTS) must be one of {SAMPLE_WEIGHTS}, got {weights!r}")
-        if weights == "fp8" and not use_fp16:
-            raise ValueError(f"{who}: weights=\"fp8\" streams MXFP8 weights against 16-bit activations; the exact mode (use_fp16=False) has no such form")
+        if weights in QUANT_WEIGHTS and not use_fp16:
+            raise ValueError(f"{who}: weights=\"{weights}\" streams {QUANT_WEIGHTS[weights]} weights against 16-bit activations; the exact mode (use_fp16=False) has no such form")
         return weights
 
     @staticmethod
@@ -377,21 +402,23 @@ class Prior(nn.Module):
         return cache
 
     def _sample_operands(self, dt: torch.dtype, weights: str):
-        """the operands of sample(): `_operand_copies(dt)`, or under weights == "fp8" the MXFP8 form, where every Linear of every Block is a
-        (codes, scales) pair and only the head is a 16-bit copy.  Built once on the device from the f32 masters and keyed on their data pointers
-        and version counters like the 16-bit copies; building it builds no 16-bit copy of a Block weight.  Under a GPTAdam, whose step kernel
-        writes the masters behind those counters, the optimizer's step drops every entry of `_operands`, so the next call rebuilds."""
-        if weights != "fp8":
+        """the operands of sample(): `_operand_copies(dt)`, or under weights == "fp8" / "fp4" the MXFP8 / MXFP4 form, where every Linear of every
+        Block is a (codes, scales) pair / an MXFP4 and only the head is a 16-bit copy.  Built once on the device from the f32 masters and keyed on
+        their data pointers and version counters like the 16-bit copies; building it builds no copy of a Block weight in another format.  Under a
+        GPTAdam, whose step kernel writes the masters behind those counters, the optimizer's step drops every entry of `_operands`, so the next
+        call rebuilds."""
+        if weights not in QUANT_WEIGHTS:
             return self._operand_copies(dt)
+        operand = _mxfp4_operand if weights == "fp4" else _mxfp8_operand
         masters = [p for _, p in sorted(self.named_parameters())]
         key = tuple((p.data_ptr(), p._version) for p in masters)
-        hit = self._operands.get(("fp8", dt))
+        hit = self._operands.get((weights, dt))
         if hit is not None and hit[0] == key:
             return hit[1]
-        self._operands.pop(("fp8", dt), None)      # release the stale copies before their replacements are allocated
-        ops = {k: _layer_operands_fp8(stack) for k, (_, stack) in self._block_stacks().items()}
+        self._operands.pop((weights, dt), None)      # release the stale copies before their replacements are allocated
+        ops = {k: _layer_operands_mx(stack, operand) for k, (_, stack) in self._block_stacks().items()}
         ops["head"] = self.head.weight.detach().to(dt).contiguous()
-        self._operands[("fp8", dt)] = (key, ops)
+        self._operands[(weights, dt)] = (key, ops)
         return ops
 
     def _flat_grads(self, dev) -> torch.Tensor:

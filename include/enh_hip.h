@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 32  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 33  /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -644,6 +644,30 @@ int enh_mxfp8_quantize(const float* w, int64_t N, int64_t K, int64_t w_row_strid
  * The codes are widened to the operand format exactly, every 32-wide block is one MFMA step whose f32 result is multiplied by the block's power of
  * two as it is added to the f32 sum: the scale costs no accuracy.  The codes and scales are read exactly once. */
 int enh_skinny_gemm_w8(const enh_h16* x, const uint8_t* codes, const uint8_t* scales, int64_t M, int64_t N, int64_t K, const float* bias, int act,
+                       const float* res, float* out_f32, enh_h16* out_h16, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 sampling with MXFP4 weights (csrc/gpt_decode_w4.hip): the weight-only 4-bit form of a decode step's products.
+ * The operand format, fixed: a weight W [N, K] in nn.Linear layout, K % 32 == 0, is two row-major arrays,
+ *   codes  [N, K / 2]  uint8: two OCP e2m1 codes per byte, k even in the low nibble and k odd in the high nibble.  A nibble is sign, 2 exponent
+ *                             bits (bias 1), 1 mantissa bit: codes 0 .. 7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6; no NaN and no infinity,
+ *   scales [N, K / 32] uint8: E8M0 as for MXFP8, byte s = 2^(s - 127), one per 32 consecutive k of a row; 0xff is the format's NaN,
+ * and W[n, k] = e2m1(code[n, k]) 2^(scales[n, k / 32] - 127).  Per block of 32 (OCP Microscaling Formats v1.0): amax = max |w|,
+ * X = clamp(floor(log2 amax) - 2, -127, 127) (X = 0 when amax == 0), code = RNE(w 2^-X) on the eight-value grid, ties to the even code
+ * (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), saturated to +-6: values in (6, 8) saturate; -0.0 keeps its sign.
+ * Non-finite input: a block that holds an infinity or a NaN gets the scale byte 0xff and all-zero codes, so the whole block dequantizes to NaN,
+ * and the product gives NaN for every row of W that holds such a block.
+ * No float atomics; the same bits on every run.
+ * ------------------------------------------------------------------------------------------------ */
+/* enh_mxfp8_quantize for this format: rows [0, N) of w become rows code_row0 .. of `codes` (row pitch K / 2 bytes, 4-byte aligned) and rows
+ * scale_row0 .. of `scales` (row pitch K / 32).  One pass over w; nothing outside those rows is written. */
+int enh_mxfp4_quantize(const float* w, int64_t N, int64_t K, int64_t w_row_stride, uint8_t* codes, int64_t code_row0, uint8_t* scales,
+                       int64_t scale_row0, void* stream);
+/* enh_skinny_gemm_w8's contract with W in this format: 1 <= M <= 64, N % 8 == 0, K % 32 == 0 (else ENH_E_SHAPE), the same epilogue and outputs,
+ * exact widening, one MFMA step per 32-wide block scaled in f32, codes and scales read exactly once.  Its slabs hold at least two K chunks per
+ * wave, so its slab plan and workspace are its own: enh_skinny_gemm_w4_workspace_bytes (0 when no workspace is needed). */
+size_t enh_skinny_gemm_w4_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int enh_skinny_gemm_w4(const enh_h16* x, const uint8_t* codes, const uint8_t* scales, int64_t M, int64_t N, int64_t K, const float* bias, int act,
                        const float* res, float* out_f32, enh_h16* out_h16, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
