@@ -175,10 +175,12 @@ template <typename OT, bool CLIP>
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, uint16_t* __restrict__ p16, int64_t n, float lr, float beta1,
                              float beta2, float eps, float wd, float gscale, float inv_bc1, float inv_sqrt_bc2, const float* __restrict__ skip,
-                             const float* __restrict__ loss_scale, const float* __restrict__ clip_coef, float clip_value) {
+                             const float* __restrict__ loss_scale, const float* __restrict__ clip_coef, float clip_value,
+                             const double* __restrict__ step_state) {
   const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i >= n) return;
   if (skip && *skip != 0.f) return;
+  if (step_state) { inv_bc1 = (float)step_state[1]; inv_sqrt_bc2 = (float)step_state[2]; }      // the bias corrections of the applied step (adamw_advance_kernel)
   if (loss_scale) gscale /= *loss_scale;      // GradScaler's unscale, folded into the step (the scale is a power of two: exact)
   if (CLIP && clip_coef) gscale *= *clip_coef;
   float pv[4], gv[4], mv[4], vv[4];
@@ -336,22 +338,40 @@ extern "C" int enh_cast_f32_h16(const float* x, enh_h16* y, int64_t n, int dtype
   return enh_check_launch("enh_cast_f32_h16");
 }
 
+// The step number of enh_adamw_step kept on the device: state = f64 [>= 3] = (t, 1 / (1 - beta1^t), 1 / sqrt(1 - beta2^t)), t the number of APPLIED
+// steps.  Runs in front of the AdamW launch: unless the flag is set, t advances and the two factors are formed for the new t exactly as the host forms them
+// from a `step` passed by value (double, rounded to float once).  A dropped step leaves all three alone, as GradScaler.step leaves AdamW's state["step"].
+__global__ void adamw_advance_kernel(double* __restrict__ state, const float* __restrict__ found_inf, double b1, double b2) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (found_inf && *found_inf != 0.f) return;
+  const double t = state[0] + 1.0;
+  state[0] = t;
+  state[1] = (double)(float)(1.0 / (1.0 - pow(b1, t)));
+  state[2] = (double)(float)(1.0 / sqrt(1.0 - pow(b2, t)));
+}
+
 extern "C" int enh_adamw_step(float* p, const float* g, float* m, float* v, enh_h16* p_bf16, int64_t n, int step,
                               float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                              const float* skip_flag, const float* loss_scale_dev, const float* clip_coef_dev, float clip_value, int dtype,
-                              void* stream) {
+                              const float* skip_flag, const float* loss_scale_dev, const float* clip_coef_dev, float clip_value, double* step_state,
+                              int dtype, void* stream) {
   ENH_REQUIRE_DT(dtype, "enh_adamw_step");
-  ENH_REQUIRE(p && g && m && v && n > 0 && step >= 1 && clip_value >= 0.f, ENH_E_BADARG, "enh_adamw_step: bad argument");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  ENH_REQUIRE(p && g && m && v && n > 0 && (step >= 1 || step_state) && clip_value >= 0.f, ENH_E_BADARG, "enh_adamw_step: bad argument");
+  ENH_REQUIRE(!step_state || ((uintptr_t)step_state & 7) == 0, ENH_E_BADARG, "enh_adamw_step: step_state must be 8-byte aligned");
+  float inv_bc1 = 0.f, inv_sqrt_bc2 = 0.f;
+  if (step_state) {      // `step` is not read: the kernel takes the factors of the device count
+    adamw_advance_kernel<<<1, 64, 0, (hipStream_t)stream>>>(step_state, skip_flag, (double)beta1, (double)beta2);
+  } else {
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    inv_bc1 = (float)(1.0 / bc1); inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  }
   const int64_t n4 = (n + 3) / 4;
   const int grid = (int)((n4 + 255) / 256);
-  const float inv_bc1 = (float)(1.0 / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   if (clip_coef_dev || clip_value > 0.f)
     ENH_DT_DISPATCH(dtype, (adamw_kernel<OT, true><<<grid, 256, 0, (hipStream_t)stream>>>(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, grad_scale, inv_bc1,
-                                                                                         inv_sqrt_bc2, skip_flag, loss_scale_dev, clip_coef_dev, clip_value)));
+                                                                                         inv_sqrt_bc2, skip_flag, loss_scale_dev, clip_coef_dev, clip_value, step_state)));
   else
     ENH_DT_DISPATCH(dtype, (adamw_kernel<OT, false><<<grid, 256, 0, (hipStream_t)stream>>>(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, grad_scale, inv_bc1,
-                                                                                          inv_sqrt_bc2, skip_flag, loss_scale_dev, nullptr, 0.f)));
+                                                                                          inv_sqrt_bc2, skip_flag, loss_scale_dev, nullptr, 0.f, step_state)));
   return enh_check_launch("enh_adamw_step");
 }
 

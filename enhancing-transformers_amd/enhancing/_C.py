@@ -125,7 +125,7 @@ SIGNATURES = {
     "enh_gemm_bf16_split": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "enh_layernorm_forward_x3": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "enh_attention_forward_x3": (_i32, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
-    "enh_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _f32, _i32, _vp]),
+    "enh_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _i32, _vp]),
     "enh_grad_clip_coef_workspace_bytes": (_sz, [_i64]),
     "enh_grad_clip_coef": (_i32, [_vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "enh_adam_step_segments": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _f32, _f64, _f64, _f32, _f32, _vp, _vp, _vp, _f32, _i32, _vp]),
@@ -175,7 +175,7 @@ SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 33 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 34 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -645,16 +645,22 @@ def grad_clip_coef(g, max_norm: float, grad_scale: float, out, loss_scale=None, 
                           "enh_grad_clip_coef"), unit="byte")
 
 
-def adamw_step(p, g, m, v, p_bf16, step: int, lr: float, beta1: float = 0.9, beta2: float = 0.99, eps: float = 1e-8,
+def adamw_step(p, g, m, v, p_bf16, step, lr: float, beta1: float = 0.9, beta2: float = 0.99, eps: float = 1e-8,
                weight_decay: float = 1e-4, grad_scale: float = 1.0, skip_flag=None, loss_scale=None, clip_coef=None, clip_value: float = 0.0):
-    """clip_coef (device f32 [1], optional): multiplies the gradient after the loss-scale division (grad_clip_coef's out[1:]); clip_value > 0: the unscaled
+    """step: the step number t >= 1 whose bias corrections this launch applies, or a device f64 [4] = (applied steps, 1 / (1 - beta1^t),
+    1 / sqrt(1 - beta2^t), 0): the count then lives on the device and is advanced in front of the update unless skip_flag is set — a dropped step
+    does not count, as under GradScaler.step (engine/optim.py step_operand).
+    clip_coef (device f32 [1], optional): multiplies the gradient after the loss-scale division (grad_clip_coef's out[1:]); clip_value > 0: the unscaled
     gradient is clamped to [-clip_value, clip_value] before the moments (0 = off)"""
+    state = step if isinstance(step, torch.Tensor) else None
+    if state is not None and state.numel() < 3:
+        raise RuntimeError("adamw_step: a device step state is f64 [4] (applied steps, the two bias-correction factors, 0)")
     # 30 B per parameter: p, g, m, v read (16) + p, m, v written (12) + the bf16 operand shadow written (2)
     _timed("adamw_kernel", (28.0 + (2.0 if p_bf16 is not None else 0.0)) * p.numel(),
            lambda: _check(lib().enh_adamw_step(_p(p, F32, "p"), _p(g, F32, "g"), _p(m, F32, "m"), _p(v, F32, "v"), _p(p_bf16, H16, "p_bf16"),
-                                               p.numel(), step, lr, beta1, beta2, eps, weight_decay, grad_scale, _p(skip_flag, F32, "skip_flag"),
-                                               _p(loss_scale, F32, "loss_scale"), _p(clip_coef, F32, "clip_coef"), float(clip_value), _dt(p_bf16),
-                                               _stream()), "enh_adamw_step"), unit="byte")
+                                               p.numel(), 0 if state is not None else int(step), lr, beta1, beta2, eps, weight_decay, grad_scale,
+                                               _p(skip_flag, F32, "skip_flag"), _p(loss_scale, F32, "loss_scale"), _p(clip_coef, F32, "clip_coef"),
+                                               float(clip_value), _p(state, F64, "step"), _dt(p_bf16), _stream()), "enh_adamw_step"), unit="byte")
 
 
 def adam_segment_table(segments, n: int, arena_n: int, device):

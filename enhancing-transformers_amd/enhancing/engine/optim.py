@@ -44,9 +44,11 @@ class LossScaler:
     by the forward that builds the graph (fp16 operands in the loss networks: gradients of ~1e-5 would sit in fp16's subnormal range).
     Initial scale: the environment variable `env` names.  ENH_LOSS_SCALE (2^16, GradScaler's) for the engine and GPTAdam; ENH_LOSS_NET_SCALE (2^12) for
     the loss networks: a gradient of 1 per logit, times the scale, has to fit fp16 itself, and 2^16 would spend its first steps backing off.  Growth x2
-    after ENH_LOSS_SCALE_INTERVAL (2000, GradScaler's; 0 = never) clean steps, x0.5 on an inf / nan (that step is skipped).
+    after ENH_LOSS_SCALE_INTERVAL (2000, GradScaler's; 0 = never) clean steps, x0.5 on an inf / nan (that step is skipped: it writes nothing and does
+    not count as an AdamW step, see `step_operand`).
     check=False scales but does not check (the engine's ENH_NONFINITE_CHECK=0): found_inf is None, no step is dropped and the scale never moves.
-    count_skipped: keep `skipped_steps`, a device count of the dropped steps (the engine's; read it with .item() outside the step)."""
+    count_skipped: keep `skipped_steps`, a device count of the dropped steps (the engine's; read it with .item() outside the step).
+    state_dict / load_state_dict: scale, tracker and skipped_steps on the host, what an optimizer's checkpoint carries as its `scaler` entry."""
     DEFAULT_SCALE = dict(ENH_LOSS_SCALE=65536.0, ENH_LOSS_NET_SCALE=4096.0)
 
     def __init__(self, device, init_scale: float = None, growth_interval: int = None, env: str = "ENH_LOSS_NET_SCALE", enabled: bool = False,
@@ -71,6 +73,49 @@ class LossScaler:
     def value(self) -> float:
         return float(self.scale_t.item()) if self.enabled else 1.0
 
+    @property
+    def checks(self) -> bool:
+        """this scaler can drop the step it is handed"""
+        return self.enabled and self.found_inf is not None
+
+    def state_dict(self) -> dict:
+        return dict(scale=self.scale_t.detach().cpu(), tracker=self.tracker.detach().cpu(),
+                    skipped_steps=None if self.skipped_steps is None else self.skipped_steps.detach().cpu())
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.scale_t.copy_(sd["scale"]); self.tracker.copy_(sd["tracker"])
+        if self.skipped_steps is not None and sd.get("skipped_steps") is not None:
+            self.skipped_steps.copy_(sd["skipped_steps"])
+
+
+def step_operand(store, scaler=None):
+    """The `step` operand of the AdamW launch `store`'s next optimizer step makes, and the bookkeeping that goes with it.
+    Without a scaler that can drop the step (bf16 / fp32, a disabled scaler, ENH_NONFINITE_CHECK=0) every step is applied: the host count
+    `store.step_count` advances and goes in by value.  Under a scaler that checks the host cannot know whether this step will be applied, and
+    GradScaler.step does not call AdamW's step on an overflow: the count moves to the device (`store.step_state`, f64 [4] = applied steps and the two
+    bias-correction factors of _C.adamw_step) where the launch advances it only when the flag is clear — no host read, nothing to synchronise on.  From
+    its first such step on a store keeps the device count (an unchecked step then advances it unconditionally); `store.step_count` reads it."""
+    if getattr(store, "step_state", None) is None and (scaler is None or not scaler.checks):
+        store.step_count += 1
+        return store.step_count
+    return device_step_count(store)
+
+
+def applied_steps(store) -> int:
+    """the number of steps `store`'s optimizer has applied, wherever it is counted (reads the device count when there is one: synchronises)"""
+    state = getattr(store, "step_state", None)
+    return store.step_count if state is None else int(state[0].item())
+
+
+def device_step_count(store):
+    """move `store`'s step number to the device, once (the fp16 engine does at construction, so that its step never allocates) -> store.step_state"""
+    if getattr(store, "step_state", None) is None:
+        import torch
+        state = torch.zeros(4, dtype=torch.float64, device=store.p.device)
+        state[0] = store.step_count
+        store.step_state = state
+    return store.step_state
+
 
 def scaled_step(g, grad_scale: float, clip, clip_out, scaler, adam, grads_unscaled: bool = False) -> None:
     """The clipped, loss-scaled optimizer step all three optimizers take: GradScaler.step + GradScaler.update around the caller's Adam launch, with no
@@ -82,7 +127,8 @@ def scaled_step(g, grad_scale: float, clip, clip_out, scaler, adam, grads_unscal
     neither launch gets the loss_scale operand, the flag and the update still run.
     adam: the caller's Adam launch; called once, with exactly those of skip_flag / loss_scale / clip_coef / clip_value that apply (none: the plain call).
     Under a scaler that checks: one pass over g sets found_inf (the norm pass when there is one: the sum of squares and the flag ride on the same loads),
-    the Adam launch reads it and writes nothing when it is set, enh_loss_scale_update halves / doubles the scale on the device."""
+    the Adam launch reads it and writes nothing when it is set — its step number included, which therefore lives on the device (step_operand below,
+    GPTAdam's `state`) — and enh_loss_scale_update halves / doubles the scale on the device."""
     from .. import _C
     clip_norm, clip_value = clip
     sc = scaler if scaler is not None and scaler.enabled else None
@@ -109,23 +155,35 @@ def scaled_step(g, grad_scale: float, clip, clip_out, scaler, adam, grads_unscal
 
 
 class _StoreAdamW(_GradClip):
-    """what FusedAdamW and FlatAdamW share: AdamW's state lives in `self.store` (a ParamStore: step_count, m, v)"""
+    """what FusedAdamW and FlatAdamW share: AdamW's state lives in `self.store` (a ParamStore: step_count, m, v), GradScaler's in `self.scaler`
+    (the engine's or the store's LossScaler, or None).  `step` is torch's state["step"]: the number of APPLIED steps; a step the scaler drops does not
+    count (step_operand above).  An enabled scaler is part of the state: a run restored without it would restart at the initial scale and drop a burst
+    of steps the uninterrupted run does not drop."""
 
     def zero_grad(self, set_to_none: bool = False) -> None:
         self.store.zero_grad()
 
     def state_dict(self) -> dict:
-        s = self.store
-        return dict(step=s.step_count, m=s.m.detach().cpu(), v=s.v.detach().cpu(), param_groups=self.param_groups)
+        s, sc = self.store, self.scaler
+        sd = dict(step=applied_steps(s), m=s.m.detach().cpu(), v=s.v.detach().cpu(), param_groups=self.param_groups)
+        if sc is not None and sc.enabled:
+            sd["scaler"] = sc.state_dict()
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
-        s = self.store
+        s, sc = self.store, self.scaler
         s.step_count = int(sd["step"])
         s.m.copy_(sd["m"]); s.v.copy_(sd["v"])
         self.param_groups = sd["param_groups"]
+        if sc is not None and "scaler" in sd:      # (a checkpoint written before the scaler was part of it has no entry: the scale starts over)
+            sc.load_state_dict(sd["scaler"])
 
 
 class FusedAdamW(_StoreAdamW):
+    """torch.optim.AdamW over the engine's flat buffers (Stage1Engine.optimizer_step).  Under the fp16 engine step() is GradScaler.step +
+    GradScaler.update around it, on the device: an overflow drops the step, which then writes nothing, is counted in engine.skipped_steps and leaves
+    AdamW's step number where it was, so the next applied update carries the bias corrections torch's would.  state_dict() holds the scaler."""
+
     def __init__(self, engine, lr: float, betas=(0.9, 0.99), eps: float = 1e-8, weight_decay: float = 1e-4) -> None:
         self.engine = engine
         self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
@@ -134,6 +192,10 @@ class FusedAdamW(_StoreAdamW):
     @property
     def store(self):
         return self.engine.store
+
+    @property
+    def scaler(self):
+        return getattr(self.engine, "scaler", None)
 
     @property
     def grad_norm(self):
@@ -157,6 +219,11 @@ class FlatAdamW(_StoreAdamW):
         self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
         self.grad_scale = 1.0
         self.comm = None
+
+    @property
+    def scaler(self):
+        """the store's LossScaler (the discriminator's: losses/vqperceptual.py disc_store), or None"""
+        return getattr(self.store, "loss_scaler", None)
 
     def attach_sync(self, module, **kw):
         """bucketed asynchronous gradient all-reduce for this store, driven by autograd hooks on `module`'s parameters (engine/ddp.py)"""
@@ -191,10 +258,9 @@ class FlatAdamW(_StoreAdamW):
         elif dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             dist.all_reduce(s.g)
             scale /= dist.get_world_size()
-        s.step_count += 1
-        clip = self._clip_args()
-        scaled_step(s.g, scale, clip, self._clip_buf(clip, s.g.device), getattr(s, "loss_scaler", None), lambda **kw: _C.adamw_step(
-            s.p, s.g, s.m, s.v, None, s.step_count, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], scale, **kw))
+        clip, step = self._clip_args(), step_operand(s, self.scaler)
+        scaled_step(s.g, scale, clip, self._clip_buf(clip, s.g.device), self.scaler, lambda **kw: _C.adamw_step(
+            s.p, s.g, s.m, s.v, None, step, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], scale, **kw))
         from ..losses.op.conv_nhwc import invalidate_packed_weights
         invalidate_packed_weights()          # the kernel wrote the weights through raw pointers: cached operand images are stale
 

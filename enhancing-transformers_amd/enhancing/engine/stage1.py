@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import _C
-from .optim import LossScaler, scaled_step
+from .optim import LossScaler, device_step_count, scaled_step, step_operand
 
 F32, BF16, F16 = torch.float32, torch.bfloat16, torch.float16
 # precision modes of the engine: the two product paths ("bf16" / "fp16": 16-bit MFMA operands of that format, fp32 accumulation / residual stream /
@@ -67,12 +67,25 @@ class ParamStore:
                 self.w[n] = p.data
         # GEMM operand view of every weight: the 16-bit shadow (product paths) or the fp32 master itself (exact mode)
         self.wa = self.w16 if self.half else self.w
-        self.step_count = 0
-        self.comm_done = False             # data-parallel: this step's gradient all-reduce has already been waited for (unscale_grads before the step)
+        self._steps = 0                    # AdamW's step number = the applied optimizer steps, on the host until a scaler that can drop a step takes part:
+        self.step_state = None             # then device f64 [4], advanced by the AdamW launch itself (engine/optim.py step_operand); `step_count` reads either
+        self.comm_done = False            # data-parallel: this step's gradient all-reduce has already been waited for (unscale_grads before the step)
         self.grads_unscaled = False        # fp16 engine: the flat gradient holds loss_scale x gradient from backward until unscale_grads() / the optimizer step
         self.version = 0                   # bumped whenever the fp32 masters may have changed: lazily rebuilt operand images (the x3 weights) compare it
         self.operand_hooks: List = []      # callables that rebuild derived GEMM operands (e.g. the towers' pre-scaled q | k | v weights) from the masters
         self.refresh_shadows()
+
+    @property
+    def step_count(self) -> int:
+        """the number of optimizer steps applied so far (torch.optim.AdamW's state["step"]; a step dropped by the loss scaler does not count).  Once the
+        count lives on the device this reads it (synchronises: for checkpoints, tests and logging; the step itself never does)"""
+        return self._steps if self.step_state is None else int(self.step_state[0].item())
+
+    @step_count.setter
+    def step_count(self, n: int) -> None:
+        self._steps = int(n)
+        if self.step_state is not None:
+            self.step_state[0] = int(n)      # (the launch forms the bias-correction factors of the next applied step from this alone)
 
     @staticmethod
     def layout(params):
@@ -498,6 +511,8 @@ class Stage1Engine:
                                  count_skipped=True) if self.scaled else None
         sc = self.scaler
         self.scale_t, self.found_inf, self.skipped_steps = (sc.scale_t, sc.found_inf, sc.skipped_steps) if self.scaled else (None, None, None)
+        if sc is not None and sc.checks:      # a step may be dropped: AdamW's step number is counted where the drop is decided
+            device_step_count(self.store)
         # (total_norm, clip coefficient) of the last optimizer_step that asked for the gradient norm: written by enh_grad_clip_coef, the coefficient is
         # read by the AdamW launch — neither ever visits the host inside the step
         self._clip_out = torch.zeros(2, dtype=F32, device=self.device)
@@ -891,11 +906,11 @@ class Stage1Engine:
                 self.comm.finish()
             s.comm_done = False
             grad_scale = grad_scale / self.comm.world
-        s.step_count += 1
-        # under fp16 this is GradScaler.step + GradScaler.update (reference main.py:25,52 --use_amp) on the device.  The host step count advances
-        # either way: a dropped step then only shifts the bias correction by one step.
+        # under fp16 this is GradScaler.step + GradScaler.update (reference main.py:25,52 --use_amp) on the device: the step number is then a device
+        # count that a dropped step does not advance (step_operand); bf16 / fp32 / ENH_NONFINITE_CHECK=0 pass the host count by value.
+        step = step_operand(s, self.scaler)
         scaled_step(s.g, grad_scale, (clip_norm, clip_value), self._clip_out, self.scaler, lambda **kw: _C.adamw_step(
-            s.p, s.g, s.m, s.v, s.p16 if self.half else None, s.step_count, lr, betas[0], betas[1], eps, weight_decay, grad_scale, **kw),
+            s.p, s.g, s.m, s.v, s.p16 if self.half else None, step, lr, betas[0], betas[1], eps, weight_decay, grad_scale, **kw),
             grads_unscaled=s.grads_unscaled)
         s.refresh_operands()      # operands derived from the masters (the towers' pre-scaled q | k | v weights, the x3 images: _refresh_x3_operands)
 

@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 33  /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 34 /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -382,10 +382,14 @@ int enh_cast_f32_h16_head_scaled_strided(const float* x, int64_t x_stride, enh_h
  * clip_coef_dev (optional device float): multiplied into the gradient scale after the loss-scale division — the coefficient of
  * torch.nn.utils.clip_grad_norm_, from enh_grad_clip_coef (out + 1).  clip_value (0 = off): the unscaled gradient g * scale is clamped to
  * [-clip_value, clip_value] before the moments (Lightning's gradient_clip_algorithm="value"; a nan stays a nan).  With NULL and 0 the step is the
- * step without these operands, bit for bit. */
+ * step without these operands, bit for bit.
+ * step_state (optional device double[3], 8-byte aligned; ABI v34): the step number lives on the device — (t, 1 / (1 - beta1^t), 1 / sqrt(1 - beta2^t)) with t
+ * the number of APPLIED steps; `step` is then not read.  A one-thread launch in front of the AdamW kernel advances t and forms the two factors for it
+ * unless skip_flag is set: a dropped step leaves the count where it was, as GradScaler.step leaves AdamW's (start from (t0, any, any); only t is state).
+ * With NULL the bias corrections are those of `step` (>= 1), formed on the host: the launch of before. */
 int enh_adamw_step(float* p, const float* g, float* m, float* v, enh_h16* p_h16, int64_t n, int step, float lr,
                    float beta1, float beta2, float eps, float weight_decay, float grad_scale, const float* skip_flag, const float* loss_scale_dev,
-                   const float* clip_coef_dev, float clip_value, int dtype, void* stream);
+                   const float* clip_coef_dev, float clip_value, double* step_state, int dtype, void* stream);
 /* GradScaler.update() on the device: found_inf != 0 -> *scale *= backoff_factor, *growth_tracker = 0; otherwise ++*growth_tracker and after
  * growth_interval clean steps in a row *scale *= growth_factor (growth_interval = 0: never grow = a static scale with backoff).  *scale is kept
  * inside [1, 2^24].  torch defaults: growth 2, backoff 0.5, interval 2000, initial scale 65536. */

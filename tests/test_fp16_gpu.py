@@ -463,7 +463,8 @@ def test_large_config5_towers_fp16():
 
 def test_fp16_training_steps_follow_the_oracle_and_skip_on_overflow():
     """five AdamW steps through the loss-scaled fp16 backward track the fp32 oracle's trajectory (tiny config: every kernel family incl. the small-shape
-    GEMMs); then a step whose gradient is poisoned with an inf is dropped — parameters, moments and the fp16 operand shadow keep their bits — and counted."""
+    GEMMs); then a step whose gradient is poisoned with an inf is dropped — parameters, moments and the fp16 operand shadow keep their bits — and counted;
+    the update after it is the oracle's AdamW step 6 (the applied count), not 7."""
     import vitvq_oracle as O
     cfg = O.TINY_CFG
     P = O.make_params(cfg, 21)
@@ -501,6 +502,14 @@ def test_fp16_training_steps_follow_the_oracle_and_skip_on_overflow():
     o_loss, _, o_grads, _ = O.train_step_grads(xs[0], {k: v.detach().cpu() for k, v in m.state_dict().items() if k in Po}, cfg)
     worst_g = max(rel(p.grad, o_grads[k]) for k, p in m.named_parameters() if k in o_grads)
     assert worst_g <= 5e-3, worst_g
+    # and its update is AdamW's SIXTH step: the dropped one does not count (GradScaler.step does not call optimizer.step() on an overflow)
+    eng.optimizer_step(lr)
+    for k, gk in o_grads.items():
+        O.adamw_step(Po[k], gk, mo[k], vo[k], 6, lr)
+    sd = {k: p.detach().cpu() for k, p in m.named_parameters()}
+    worst = max(rel(sd[k], Po[k]) for k in o_grads)
+    print(f"fp16 update after the dropped step: worst parameter rel error vs the fp32 oracle at step 6 {worst:.2e}")
+    assert worst <= 5e-3 and eng.store.step_count == 6 and eng.skipped_steps.item() == 1.0
 
 
 def test_encode_codes_defaults_to_the_single_fp16_pass_and_x3_stays_available():
