@@ -143,6 +143,9 @@ SIGNATURES = {
     "enh_mxfp4_quantize": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "enh_skinny_gemm_w4_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "enh_skinny_gemm_w4": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
+    "enh_mxfp6_quantize": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "enh_skinny_gemm_w6_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "enh_skinny_gemm_w6": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
     "enh_causal_attention_forward": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp]),
     "enh_causal_attention_forward_f32": (_i32, [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
     "enh_ln_timeshift": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _i32, _vp]),
@@ -175,7 +178,7 @@ SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 34 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 35 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -1096,7 +1099,7 @@ def skinny_gemm(x, w, out, bias=None, relu_sq: bool = False, res=None):
 
 
 U8 = torch.uint8
-MX_BLOCK = 32        # k per E8M0 scale of an MXFP8 or MXFP4 operand (include/enh_hip.h)
+MX_BLOCK = 32        # k per E8M0 scale of an MXFP8, MXFP6 or MXFP4 operand (include/enh_hip.h)
 
 
 def quantize_mxfp8(w, codes, scales, row0: int = 0):
@@ -1174,6 +1177,51 @@ def skinny_gemm_w4(x, codes, scales, out, bias=None, relu_sq: bool = False, res=
            lambda: _check(L.enh_skinny_gemm_w4(_p(x, H16, "x"), _p(codes, U8, "codes"), _p(scales, U8, "scales"), M, N, K, _p(bias, F32, "bias"),
                                                ACT_RELU_SQ if relu_sq else 0, _p(res, F32, "res"), _p(o32, F32, "out"), _p(o16, H16, "out"), _p(ws), nb,
                                                _dt(x, o16), _stream()), "enh_skinny_gemm_w4"), unit="byte")
+
+
+def mxfp6_row_bytes(K: int) -> int:
+    """bytes of a row of MXFP6 codes (include/enh_hip.h): whole 128-k chunks of 96 bytes"""
+    return 96 * ((K + 127) // 128)
+
+
+def quantize_mxfp6(w, codes, scales, row0: int = 0):
+    """the MXFP6 operand of a weight (enh_mxfp6_quantize): w [N, K] f32, K % 32 == 0, rows contiguous (any row stride that keeps them 16-byte
+    aligned) -> rows row0 .. row0 + N - 1 of codes [Nt, 96 ceil(K / 128)] uint8 (e2m3 codes, 128-k chunks of 96 bytes in the product's order;
+    include/enh_hip.h) and scales [Nt, K / 32] uint8 (E8M0); the other rows are not touched"""
+    if w.dim() != 2 or codes.dim() != 2 or scales.dim() != 2:
+        raise RuntimeError(f"quantize_mxfp6: w {tuple(w.shape)} codes {tuple(codes.shape)} scales {tuple(scales.shape)} must be matrices")
+    N, K = w.shape
+    if (K % MX_BLOCK or codes.shape[1] != mxfp6_row_bytes(K) or tuple(scales.shape) != (codes.shape[0], K // MX_BLOCK) or row0 < 0
+            or row0 + N > codes.shape[0]):
+        raise RuntimeError(f"quantize_mxfp6: w {tuple(w.shape)} codes {tuple(codes.shape)} scales {tuple(scales.shape)} row0 {row0} do not fit "
+                           f"(K must be a multiple of {MX_BLOCK}, codes [rows, 96 ceil(K / 128)], scales [rows, K / {MX_BLOCK}])")
+    if not w.is_cuda or w.dtype != F32 or (K > 1 and w.stride(1) != 1):
+        raise RuntimeError(f"quantize_mxfp6: w must be an f32 device tensor whose rows are contiguous, got {w.dtype} on {w.device} strides {w.stride()}")
+    stride = w.stride(0) if N > 1 else K
+    # bytes moved: the masters once, the codes and the scales
+    _timed(None, 4.0 * N * K + N * mxfp6_row_bytes(K) + N * (K // MX_BLOCK),
+           lambda: _check(lib().enh_mxfp6_quantize(ctypes.c_void_p(w.data_ptr()), N, K, int(stride), _p(codes, U8, "codes"), int(row0),
+                                                   _p(scales, U8, "scales"), int(row0), _stream()), "enh_mxfp6_quantize"), unit="byte")
+
+
+def skinny_gemm_w6(x, codes, scales, out, bias=None, relu_sq: bool = False, res=None):
+    """skinny_gemm with the weight given as its MXFP6 operand (enh_skinny_gemm_w6): out[M,N] = act(x[M,K] dequant(codes, scales)^T + bias) (+ res);
+    x 16-bit, codes [N, 96 ceil(K / 128)] uint8, scales [N, K / 32] uint8, M <= 64, N % 8 == 0, K % 32 == 0; out f32 or x's 16-bit format"""
+    M, K = x.shape
+    N = codes.shape[0]
+    if (codes.dim() != 2 or K % MX_BLOCK or codes.shape[1] != mxfp6_row_bytes(K) or tuple(scales.shape) != (N, K // MX_BLOCK)
+            or tuple(out.shape) != (M, N) or (res is not None and tuple(res.shape) != (M, N)) or (bias is not None and bias.numel() != N)):
+        raise RuntimeError(f"skinny_gemm_w6: x {tuple(x.shape)} codes {tuple(codes.shape)} scales {tuple(scales.shape)} out {tuple(out.shape)} do not fit "
+                           f"(K must be a multiple of {MX_BLOCK}, codes [N, 96 ceil(K / 128)], scales [N, K / {MX_BLOCK}])")
+    L = lib()
+    nb = L.enh_skinny_gemm_w6_workspace_bytes(M, N, K)
+    ws = _workspace(nb, x.device) if nb else None
+    o32, o16 = (out, None) if out.dtype == F32 else (None, out)
+    # bytes moved: the codes and the scales once, x, the result
+    _timed(None, float(N) * mxfp6_row_bytes(K) + float(N) * (K // MX_BLOCK) + 2.0 * M * K + float(out.element_size()) * M * N,
+           lambda: _check(L.enh_skinny_gemm_w6(_p(x, H16, "x"), _p(codes, U8, "codes"), _p(scales, U8, "scales"), M, N, K, _p(bias, F32, "bias"),
+                                               ACT_RELU_SQ if relu_sq else 0, _p(res, F32, "res"), _p(o32, F32, "out"), _p(o16, H16, "out"), _p(ws), nb,
+                                               _dt(x, o16), _stream()), "enh_skinny_gemm_w6"), unit="byte")
 
 
 def decode_attention(qkv, k_cache, v_cache, t: int, out):

@@ -26,8 +26,9 @@ enh_sample_logits_at) that run the bodies of their by-value siblings, and enh_cu
 Both also take `weights=` (None: ENH_SAMPLE_WEIGHTS, default "h16"): "fp8" streams every Linear of every Block as an MXFP8
 operand (e4m3fn codes, one E8M0 scale per 32 k; prior.py `_sample_operands`) through enh_skinny_gemm_w8 (csrc/gpt_decode_w8.hip); the head,
 the activations and the caches stay 16-bit.  "fp4" does the same with MXFP4 operands (two e2m1 codes per byte, the same scales)
-through enh_skinny_gemm_w4 (csrc/gpt_decode_w4.hip): a quarter of the weight bytes, and a format that moves the logits far more.  The three step
-methods choose their product through prior.py `_step_linear`.
+through enh_skinny_gemm_w4 (csrc/gpt_decode_w4.hip): a quarter of the weight bytes, and a format that moves the logits far more.  "fp6" lies between them: MXFP6 operands (e2m3 codes, 32 to 24
+bytes in the order the product consumes them, the same scales) through enh_skinny_gemm_w6 (csrc/gpt_decode_w6.hip), 0.76 of fp8's
+weight bytes at fp8's accuracy on block-scaled weights.  The three step methods choose their product through prior.py `_step_linear`.
 
 Both also take `cache=` (None: ENH_SAMPLE_CACHE, default "h16"): "fp8" holds every cache that enh_decode_attention serves (all
 Blocks of GPT, the spatial stack of RQTransformer) as MXFP8 codes and scales with the blocks along the head dimension (prior.py `_kv_caches`)
@@ -35,8 +36,8 @@ and attends through enh_decode_attention_kv8 (csrc/gpt_decode_kv8.hip), which qu
 caches stay 16-bit.  The step methods choose the launch through prior.py `_step_attention`.
 
 Left out: an exact-f32 backward, more than one condition token, HIP-graph capture of position 0 and of the teacher-forced entries, graphs kept
-from call to call, relu^2 / LayerNorm fused into GEMM epilogues, 8-bit activations (W8A8), an 8-bit form of the RQ depth caches, MXFP6,
-a quantized head, MXFP8 / MXFP4 in the teacher-forced entries, W4A8, quantized checkpoints on disk."""
+from call to call, relu^2 / LayerNorm fused into GEMM epilogues, 8-bit activations (W8A8), an 8-bit form of the RQ depth caches, the e3m2
+form of MXFP6, a quantized head, MXFP8 / MXFP6 / MXFP4 in the teacher-forced entries, W4A8 / W6A8 on the scaled MFMA, quantized checkpoints on disk."""
 import os
 from typing import Optional, Tuple
 
@@ -239,6 +240,8 @@ class GPT(Prior):
         "h16").  It needs use_fp16=True and composes with graph=True (a different launch in the captured position).
         weights="fp4" is the same with MXFP4 operands (two e2m1 codes per byte and the same scales) through enh_skinny_gemm_w4: a
         quarter of the weight bytes, at 0.14 - 0.19 relative logit shift on random Gaussian models against fp8's 0.04 - 0.05.
+        weights="fp6" is the same with MXFP6 operands (e2m3 codes, 0.78 bytes per weight, the same scales) through
+        enh_skinny_gemm_w6: 0.76 of fp8's weight bytes at 0.036 - 0.046 relative logit shift on the same models, which is fp8's.
 
         cache="fp8" holds every layer's k / v cache as MXFP8 codes and scales (blocks of 32 along the head dimension, 1 + 1/32 bytes
         per element instead of 2) and attends through enh_decode_attention_kv8: the step's k / v rows are quantized as they are appended, and the
@@ -627,8 +630,8 @@ class RQTransformer(Prior):
         calls; while per-kernel timing is on (_C.TIMER) the loop runs.
 
         weights="fp8" is GPT.sample's: every Linear of every Block of BOTH stacks as its MXFP8 operand through enh_skinny_gemm_w8, the head in the
-        16-bit format; weights="fp4" the same with MXFP4 operands through enh_skinny_gemm_w4; None reads ENH_SAMPLE_WEIGHTS (default "h16"); both
-        need use_fp16=True.
+        16-bit format; weights="fp6" / "fp4" the same with MXFP6 / MXFP4 operands through enh_skinny_gemm_w6 / enh_skinny_gemm_w4; None reads
+        ENH_SAMPLE_WEIGHTS (default "h16"); all three need use_fp16=True.
 
         cache="fp8" is GPT.sample's for the SPATIAL stack: its k / v caches are MXFP8 codes and scales behind enh_decode_attention_kv8 (DESIGN.md
         §3.14); the depth caches (D <= 8 slots, enh_short_decode_attention) stay 16-bit.  None reads ENH_SAMPLE_CACHE (default "h16"); it needs

@@ -1,6 +1,6 @@
 """What the stage-2 priors of layers.py (GPT, RQTransformer) and their optimizer (engine/optim.py GPTAdam) share, each stated once: the limits of
 the kernels, the launches of one Block over whole sequences forward (`_block_rows`) and backward (`_block_rows_backward`) with the products between
-them (`_row_linear`, `_grad_linears`), the launches of one Block in a cached sampling step (`_block_step`) and the product they run (`_step_linear`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`; MXFP8 and MXFP4: `_layer_operands_mx`), the k / v caches of a sampling chunk and the attention over them (`_kv_caches`, `_step_attention`), the flat
+them (`_row_linear`, `_grad_linears`), the launches of one Block in a cached sampling step (`_block_step`) and the product they run (`_step_linear`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`; MXFP8, MXFP6 and MXFP4: `_layer_operands_mx`), the k / v caches of a sampling chunk and the attention over them (`_kv_caches`, `_step_attention`), the flat
 parameter layout
 (`flat_layout`), a layer's slice of the optimizer's operand arena (`ARENA_LAYER`), and `Prior`, the base class: init, input checks, the
 version-keyed operand cache, the one-chunk-at-a-time buffer cache and the two teacher-forced drivers (forward: chunks, cross-entropy rows, mean; forward_backward: chunks under the
@@ -18,8 +18,8 @@ MAX_HEAD = 384          # enh_decode_attention
 MAX_TOKENS = 8192       # enh_decode_attention: slots of the k / v cache
 FORWARD_HIDDEN_CAP = 2 << 30   # bytes of forward()'s [chunk T, 4C] hidden activation (f32 + operand copy): shipped size, 6 sequences per chunk
 OPERAND_DTYPE = {"fp16": torch.float16, "bf16": torch.bfloat16}
-SAMPLE_WEIGHTS = ("h16", "fp8", "fp4")      # sample(weights=): the Block weights of a decode step as 16-bit operands, or as MXFP8 / MXFP4 codes and scales
-QUANT_WEIGHTS = {"fp8": "MXFP8", "fp4": "MXFP4"}
+SAMPLE_WEIGHTS = ("h16", "fp8", "fp6", "fp4")      # sample(weights=): the Block weights of a decode step as 16-bit operands, or as MXFP8 / MXFP6 / MXFP4 codes and scales
+QUANT_WEIGHTS = {"fp8": "MXFP8", "fp6": "MXFP6", "fp4": "MXFP4"}
 SAMPLE_CACHES = ("h16", "fp8")       # sample(cache=): the k / v caches of the long decode attention as 16-bit tensors, or as MXFP8 codes and scales
 
 # one layer's slice of GPTAdam's 16-bit operand arena: (operand, the Linear masters that are its row blocks, offset / C^2, rows / C, cols / C)
@@ -109,9 +109,33 @@ def _mxfp4_operand(masters) -> MXFP4:
     return MXFP4(codes, scales)
 
 
+class MXFP6(NamedTuple):
+    """the MXFP6 operand of a weight [N, K] (include/enh_hip.h): codes [N, 96 ceil(K / 128)] uint8, e2m3 codes in 128-k chunks of 96 bytes in the
+    product's order, and scales [N, K / 32] uint8"""
+    codes: torch.Tensor
+    scales: torch.Tensor
+
+
+def _mxfp6_operand(masters) -> MXFP6:
+    """`_mxfp4_operand` in the 6-bit format: quantized on the device straight from the f32 `masters`, no copy in another format is ever made"""
+    from ... import _C
+    K = masters[0].shape[1]
+    N = sum(m.shape[0] for m in masters)
+    codes = torch.empty(N, _C.mxfp6_row_bytes(K), dtype=torch.uint8, device=masters[0].device)
+    scales = torch.empty(N, K // _C.MX_BLOCK, dtype=torch.uint8, device=masters[0].device)
+    row0 = 0
+    for m in masters:
+        _C.quantize_mxfp6(m.detach(), codes, scales, row0=row0)
+        row0 += m.shape[0]
+    return MXFP6(codes, scales)
+
+
+MX_OPERAND = {"fp8": _mxfp8_operand, "fp6": _mxfp6_operand, "fp4": _mxfp4_operand}
+
+
 def _layer_operands_mx(blocks, operand) -> list:
-    """`_layer_operands` with every Linear weight through `operand` (`_mxfp8_operand`: a (codes, scales) pair, `_mxfp4_operand`: an MXFP4); biases
-    and time_mix stay f32"""
+    """`_layer_operands` with every Linear weight through `operand` (`_mxfp8_operand`: a (codes, scales) pair, `_mxfp6_operand`: an MXFP6,
+    `_mxfp4_operand`: an MXFP4); biases and time_mix stay f32"""
     layers = []
     for blk in blocks:
         a, m = blk.attn, blk.mlp
@@ -123,7 +147,8 @@ def _layer_operands_mx(blocks, operand) -> list:
 # ---- the products --------------------------------------------------------------------------------------------------------------------------
 def _step_linear(dt: torch.dtype):
     """linear(inp, w, out, bias, relu_sq, res), the product of a cached sampling step (M <= 64 rows), chosen by the operand it is given: the exact
-    mode's f32 form, enh_skinny_gemm_h16 for a 16-bit weight, enh_skinny_gemm_w8 for an MXFP8 (codes, scales) pair, enh_skinny_gemm_w4 for an MXFP4"""
+    mode's f32 form, enh_skinny_gemm_h16 for a 16-bit weight, enh_skinny_gemm_w8 for an MXFP8 (codes, scales) pair, enh_skinny_gemm_w6 for an MXFP6,
+    enh_skinny_gemm_w4 for an MXFP4"""
     from ... import _C
     if dt == torch.float32:
         return _C.skinny_gemm_f32
@@ -131,6 +156,8 @@ def _step_linear(dt: torch.dtype):
     def linear(inp, w, out, bias=None, relu_sq=False, res=None):
         if isinstance(w, MXFP4):
             _C.skinny_gemm_w4(inp, w.codes, w.scales, out, bias=bias, relu_sq=relu_sq, res=res)
+        elif isinstance(w, MXFP6):
+            _C.skinny_gemm_w6(inp, w.codes, w.scales, out, bias=bias, relu_sq=relu_sq, res=res)
         elif isinstance(w, tuple):
             _C.skinny_gemm_w8(inp, w[0], w[1], out, bias=bias, relu_sq=relu_sq, res=res)
         else:
@@ -381,7 +408,7 @@ class Prior(nn.Module):
 
     @staticmethod
     def _sample_weights(weights, use_fp16: bool, who: str) -> str:
-        """sample(weights=): None reads ENH_SAMPLE_WEIGHTS (default "h16"); "fp8" and "fp4" need the 16-bit mode (their activations are 16-bit operands)"""
+        """sample(weights=): None reads ENH_SAMPLE_WEIGHTS (default "h16"); "fp8", "fp6" and "fp4" need the 16-bit mode (their activations are 16-bit operands)"""
         if weights is None:
             weights = os.environ.get("ENH_SAMPLE_WEIGHTS", "h16")
         if weights not in SAMPLE_WEIGHTS:
@@ -402,14 +429,14 @@ class Prior(nn.Module):
         return cache
 
     def _sample_operands(self, dt: torch.dtype, weights: str):
-        """the operands of sample(): `_operand_copies(dt)`, or under weights == "fp8" / "fp4" the MXFP8 / MXFP4 form, where every Linear of every
-        Block is a (codes, scales) pair / an MXFP4 and only the head is a 16-bit copy.  Built once on the device from the f32 masters and keyed on
+        """the operands of sample(): `_operand_copies(dt)`, or under weights == "fp8" / "fp6" / "fp4" the MXFP8 / MXFP6 / MXFP4 form, where every Linear of
+        every Block is a (codes, scales) pair / an MXFP6 / an MXFP4 and only the head is a 16-bit copy.  Built once on the device from the f32 masters and keyed on
         their data pointers and version counters like the 16-bit copies; building it builds no copy of a Block weight in another format.  Under a
         GPTAdam, whose step kernel writes the masters behind those counters, the optimizer's step drops every entry of `_operands`, so the next
         call rebuilds."""
         if weights not in QUANT_WEIGHTS:
             return self._operand_copies(dt)
-        operand = _mxfp4_operand if weights == "fp4" else _mxfp8_operand
+        operand = MX_OPERAND[weights]
         masters = [p for _, p in sorted(self.named_parameters())]
         key = tuple((p.data_ptr(), p._version) for p in masters)
         hit = self._operands.get((weights, dt))

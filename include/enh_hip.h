@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 34 /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 35 /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -672,6 +672,37 @@ int enh_mxfp4_quantize(const float* w, int64_t N, int64_t K, int64_t w_row_strid
  * wave, so its slab plan and workspace are its own: enh_skinny_gemm_w4_workspace_bytes (0 when no workspace is needed). */
 size_t enh_skinny_gemm_w4_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int enh_skinny_gemm_w4(const enh_h16* x, const uint8_t* codes, const uint8_t* scales, int64_t M, int64_t N, int64_t K, const float* bias, int act,
+                       const float* res, float* out_f32, enh_h16* out_h16, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 sampling with MXFP6 weights (csrc/gpt_decode_w6.hip): the weight-only 6-bit form of a decode step's products.
+ * The operand format, fixed: a weight W [N, K] in nn.Linear layout, K % 32 == 0, is two row-major arrays,
+ *   codes  [N, 96 ceil(K / 128)] uint8: OCP FP6 E2M3 codes, six bits each: sign, 2 exponent bits (bias 1), 3 mantissa bits, code s << 5 | e << 3 | m,
+ *                             magnitude m / 8 for e = 0 and 2^(e - 1) (1 + m / 8) for e = 1 .. 3; the largest value is 7.5; no NaN and no infinity.
+ *                             A row is a sequence of 128-k chunks of 96 bytes; a last chunk that is only partly inside K is stored whole and the
+ *                             codes of k >= K are 0.  Within chunk c, piece q = 0 .. 3 is a 192-bit little-endian integer whose bits 0 .. 127 are
+ *                             the chunk's bytes [16 q, 16 q + 16) and whose bits 128 .. 191 are its bytes [64 + 8 q, 64 + 8 q + 8).  Position
+ *                             j = 8 i + e of a piece (i = 0 .. 3, e = 0 .. 7) is bits [6 j, 6 j + 6) and holds the code of k = 128 c + 32 i + 8 q + e:
+ *                             position order is the element order of v_cvt_scalef32_pk32_{f16,bf16}_fp6, element 0 in the lowest bits, so a lane's
+ *                             two loads and one conversion are the four MFMA operands of a chunk as they stand,
+ *   scales [N, K / 32] uint8: E8M0 as for MXFP8, byte s = 2^(s - 127), one per 32 consecutive k of a row in natural order; 0xff is the format's NaN,
+ * and W[n, k] = e2m3(code[n, k]) 2^(scales[n, k / 32] - 127).  Per block of 32 (OCP Microscaling Formats v1.0): amax = max |w|,
+ * X = clamp(floor(log2 amax) - 2, -127, 127) (X = 0 when amax == 0), code = RNE(w 2^-X) on the 32-value grid, ties to the even code, saturated
+ * to +-7.5: values in (7.5, 8) saturate, the tie 7.75 too; -0.0 keeps its sign.
+ * Non-finite input: a block that holds an infinity or a NaN gets the scale byte 0xff and all-zero codes, so the whole block dequantizes to NaN,
+ * and the product gives NaN for every row of W that holds such a block.
+ * No float atomics; the same bits on every run.
+ * ------------------------------------------------------------------------------------------------ */
+/* enh_mxfp4_quantize for this format: rows [0, N) of w become rows code_row0 .. of `codes` (row pitch 96 ceil(K / 128) bytes, 16-byte aligned) and
+ * rows scale_row0 .. of `scales` (row pitch K / 32).  One pass over w; a partial last chunk is written whole, zero past K; nothing outside those
+ * rows is written. */
+int enh_mxfp6_quantize(const float* w, int64_t N, int64_t K, int64_t w_row_stride, uint8_t* codes, int64_t code_row0, uint8_t* scales,
+                       int64_t scale_row0, void* stream);
+/* enh_skinny_gemm_w4's contract with W in this format: 1 <= M <= 64, N % 8 == 0, K % 32 == 0 (else ENH_E_SHAPE), the same epilogue and outputs,
+ * exact widening (one conversion per lane and chunk, no lane swaps), one MFMA step per 32-wide block scaled in f32, codes and scales read exactly
+ * once.  Its slab plan and workspace are its own: enh_skinny_gemm_w6_workspace_bytes (0 when no workspace is needed). */
+size_t enh_skinny_gemm_w6_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int enh_skinny_gemm_w6(const enh_h16* x, const uint8_t* codes, const uint8_t* scales, int64_t M, int64_t N, int64_t K, const float* bias, int act,
                        const float* res, float* out_f32, enh_h16* out_h16, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

@@ -18,6 +18,9 @@ actually moves.
 --weights fp4 writes profiles/gpt_sample_fp4.txt instead: the step with MXFP4 Block weights (sample(weights="fp4")) against the
 fp8 and the 16-bit step, the three alternating in this process, and the four Block products alone in the three forms.
 
+--weights fp6 writes profiles/gpt_sample_fp6.txt instead: the step with MXFP6 Block weights (sample(weights="fp6")) against the
+16-bit, the fp8 and the fp4 step, the four alternating in this process, and the four Block products alone in the four forms.
+
 --cache fp8 writes profiles/gpt_sample_kv8.txt instead: the step with MXFP8 k / v caches (sample(cache="fp8")) against the step
 with 16-bit caches at batch 1, 4, 16 and 64, alternating windows in this process, under the weights of --weights (h16 or fp8: with fp8 the file is
 profiles/gpt_sample_kv8_w8.txt), and the decode attention alone in both forms with the TB/s of the bytes each actually moves."""
@@ -301,6 +304,84 @@ def fp4_mode(m, L, out):
         f.write(text)
 
 
+def fp6_mode(m, L, out):
+    """--weights fp6: the MXFP6-weight step against the 16-bit, the MXFP8-weight and the MXFP4-weight step, the four alternating in one process, and
+    the four Block products alone in the four forms; writes profiles/gpt_sample_fp6.txt"""
+    C, V, T, H = m.embed_dim, m.vocab_img_size, m.img_num_tokens, m.n_heads
+    dt = torch.float16
+    blocks = 12 * C * C * L
+    wb = {"h16": (blocks + V * C) * 2, "fp8": blocks + blocks // 32 + V * C * 2, "fp6": blocks * 3 // 4 + blocks // 32 + V * C * 2,
+          "fp4": blocks // 2 + blocks // 32 + V * C * 2}
+    forms = ("h16", "fp8", "fp6", "fp4")
+    lines = [f"stage-2 GPT sampling step, MXFP6 Block weights against 16-bit, MXFP8 and MXFP4 weights, on {torch.cuda.get_device_name(0)}: C={C} layers={L} "
+             f"heads={H} V={V}, fp16 activations and caches; weights per step {wb['h16'] / 1e9:.2f} GB (16-bit) / {wb['fp8'] / 1e9:.2f} GB (fp8) / "
+             f"{wb['fp6'] / 1e9:.2f} GB (fp6) / {wb['fp4'] / 1e9:.2f} GB (fp4: codes + scales + the 16-bit head)",
+             "times: median [min .. max] of 7 rounds of alternating windows in one process; a step window is 10 steps, a kernel window is 100 launches over",
+             "rotating operand buffers of >= 1 GB in all; kernel times are event times over back-to-back launches: they include the launch boundary (~1-2 us each)",
+             f"{'batch':>5} {'cache':>5} {'16-bit ms [min .. max]':>28} {'fp8 ms [min .. max]':>28} {'fp6 ms [min .. max]':>28} {'fp4 ms [min .. max]':>28} "
+             f"{'fp8/fp6':>8} {'fp6/fp4':>8} {'not slower':>10} {'beyond fp8':>10} {'between':>8} {'fp6 GB':>7} {'fp6 TB/s':>8}"]
+    f3 = lambda v: f"{v[1]:.3f} [{v[0]:.3f} .. {v[2]:.3f}]"
+    f1 = lambda v: f"{v[1] * 1e3:.1f} [{v[0] * 1e3:.1f} .. {v[2] * 1e3:.1f}]"
+    for b in (1, 4, 16):
+        sts = {w: m._decode_state(b, dt, "cuda", weights=w) for w in forms}
+        codes = torch.randint(0, V, (b, T), device="cuda")
+        for n in (1, 1024):
+            t = n - 1
+
+            def step(w):
+                def run(i):
+                    m._decode_step(sts[w], t, codes[:, t - 1] if t else codes[:, 0] % 1000)
+                    _C.sample_logits(sts[w]["logits"], codes[:, t], top_k=None, top_p=None, seed=1, step=t)
+                return run
+            h, e, s, f = alternate([step(w) for w in forms], inner=10)
+            moved = wb["fp6"] + 2 * L * b * n * C * 2 + L * b * C * (4 * 6 + 2 * 10)
+            lines.append(f"{b:>5} {n:>5} {f3(h):>28} {f3(e):>28} {f3(s):>28} {f3(f):>28} {e[1] / s[1]:>8.3f} {s[1] / f[1]:>8.3f} "
+                         f"{'yes' if s[2] <= e[2] else 'NO':>10} {'yes' if s[2] < e[0] else 'no':>10} {(e[1] - s[1]) / (e[1] - f[1]):>8.2f} "
+                         f"{moved / 1e9:>7.2f} {moved / (s[1] * 1e-3) / 1e12:>8.2f}")
+        del sts
+        torch.cuda.empty_cache()
+    lines.append("not slower: the slowest fp6 window is no slower than the slowest fp8 window of the same point; beyond fp8: the slowest fp6 window is faster")
+    lines.append("than the fastest fp8 window; between: where the fp6 median lies on the way from the fp8 median (0) to the fp4 median (1); the bytes say 0.46")
+    lines.append("kernels alone (fp16 activations), us: median [min .. max]; TB/s of the bytes each form moves:")
+    for b in (1, 4, 16):
+        for name, N, K in (("qkv", 3 * C, C), ("proj", C, C), ("p0", 4 * C, C), ("p1", C, 4 * C)):
+            nbuf = max(2, -(-(1 << 30) // (N * K)))      # sized for the 16-bit form; the other forms rotate over as many buffers as make >= 1 GB too
+            x = torch.randn(b, K, device="cuda").half()
+            y = torch.empty(b, N, device="cuda")
+            ws = [(torch.randn(N, K, device="cuda") / math.sqrt(K)) for _ in range(2)]
+            w16s = [ws[i % 2].half() for i in range(-(-nbuf // 2))]
+            q8, q6, q4 = [], [], []
+            for i in range(nbuf):
+                q = (torch.empty(N, K, dtype=torch.uint8, device="cuda"), torch.empty(N, K // 32, dtype=torch.uint8, device="cuda"))
+                _C.quantize_mxfp8(ws[i % 2], q[0], q[1])
+                q8.append(q)
+            for i in range(-(-4 * nbuf // 3)):
+                q = (torch.empty(N, _C.mxfp6_row_bytes(K), dtype=torch.uint8, device="cuda"), torch.empty(N, K // 32, dtype=torch.uint8, device="cuda"))
+                _C.quantize_mxfp6(ws[i % 2], q[0], q[1])
+                q6.append(q)
+            for i in range(2 * nbuf):
+                q = (torch.empty(N, K // 2, dtype=torch.uint8, device="cuda"), torch.empty(N, K // 32, dtype=torch.uint8, device="cuda"))
+                _C.quantize_mxfp4(ws[i % 2], q[0], q[1])
+                q4.append(q)
+            io = 2 * b * K + 4 * b * N
+            by16, by8, by6, by4 = 2 * N * K + io, N * K + N * K // 32 + io, N * K * 3 // 4 + N * K // 32 + io, N * K // 2 + N * K // 32 + io
+            d, e, s, f = alternate([lambda i: _C.skinny_gemm(x, w16s[i % len(w16s)], y), lambda i: _C.skinny_gemm_w8(x, *q8[i % nbuf], y),
+                                    lambda i: _C.skinny_gemm_w6(x, *q6[i % len(q6)], y), lambda i: _C.skinny_gemm_w4(x, *q4[i % (2 * nbuf)], y)], inner=100)
+            t16, t8, t6, t4 = by16 / d[1] / 1e9, by8 / e[1] / 1e9, by6 / s[1] / 1e9, by4 / f[1] / 1e9
+            lines.append(f"  {name:>4} M={b:<2} N={N:<5} K={K:<5}: 16-bit {f1(d):>22} us {t16:5.2f} TB/s   fp8 {f1(e):>22} us {t8:5.2f} TB/s   "
+                         f"fp6 {f1(s):>22} us {t6:5.2f} TB/s   fp4 {f1(f):>22} us {t4:5.2f} TB/s   fp6 time vs fp8 {e[1] / s[1]:5.2f}x vs fp4 {f[1] / s[1]:5.2f}x")
+            del ws, w16s, q8, q6, q4
+        torch.cuda.empty_cache()
+    held = lambda w: sum(t.numel() * t.element_size() for W in m._sample_operands(dt, w)["layers"] for k in ("wqkv", "wproj", "w0", "w1") for t in W[k])
+    lines.append(f"operand copies of the Blocks held by the process: {held('fp6') / 1e9:.2f} GB (fp6) against {held('fp8') / 1e9:.2f} GB (fp8) and "
+                 f"{held('fp4') / 1e9:.2f} GB (fp4)")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def _fill_kv(kv, gen_scale=0.5):
     """random cache contents: 16-bit tensors N(0, 0.5); MXFP8 codes without the NaN code (bit 3 cleared) under scales around 2^-7"""
     if len(kv) == 2:
@@ -318,11 +399,12 @@ def kv8_mode(m, L, out, weights):
     C, V, T, H = m.embed_dim, m.vocab_img_size, m.img_num_tokens, m.n_heads
     hs, dt = C // H, torch.float16
     blocks = 12 * C * C * L
-    wb = {"h16": (blocks + V * C) * 2, "fp8": blocks + blocks // 32 + V * C * 2, "fp4": blocks // 2 + blocks // 32 + V * C * 2}[weights]
+    wb = {"h16": (blocks + V * C) * 2, "fp8": blocks + blocks // 32 + V * C * 2, "fp6": blocks * 3 // 4 + blocks // 32 + V * C * 2,
+          "fp4": blocks // 2 + blocks // 32 + V * C * 2}[weights]
     kv16 = lambda b, n: 2 * L * b * n * C * 2
     kv8 = lambda b, n: 2 * L * b * n * (C + C // 32)
     lines = [f"stage-2 GPT sampling step, MXFP8 k / v caches against 16-bit caches, on {torch.cuda.get_device_name(0)}: C={C} layers={L} heads={H} V={V}, "
-             f"fp16 activations, {dict(h16='16-bit', fp8='MXFP8', fp4='MXFP4')[weights]} Block weights ({wb / 1e9:.2f} GB per step)",
+             f"fp16 activations, {dict(h16='16-bit', fp8='MXFP8', fp6='MXFP6', fp4='MXFP4')[weights]} Block weights ({wb / 1e9:.2f} GB per step)",
              f"caches held at T={T}, batch 64: {kv16(64, T) / 1e9:.1f} GB (16-bit) / {kv8(64, T) / 1e9:.1f} GB (fp8: codes + scales)",
              "times: median [min .. max] of 7 alternating windows in one process; a step window is 10 steps, a kernel window is 100 launches over 2 to 16",
              "rotating cache buffers (0.4 GB in all at batch 1, >= 1 GB from batch 4); kernel times are event times over back-to-back launches: they include the launch boundary (~1-2 us each)",
@@ -381,16 +463,16 @@ def main():
     ap.add_argument("--whole", type=int, default=1, help="also time a whole 1024-step sample at batch 4")
     ap.add_argument("--graph", action="store_true", help="instead of the tables: the eager loop against replays of one captured position "
                     "(profiles/gpt_sample_graph.txt)")
-    ap.add_argument("--weights", choices=("h16", "fp8", "fp4"), default="h16", help="fp8: instead of the tables, the MXFP8-weight step against the 16-bit "
+    ap.add_argument("--weights", choices=("h16", "fp8", "fp6", "fp4"), default="h16", help="fp8: instead of the tables, the MXFP8-weight step against the 16-bit "
                     "step and the products alone (profiles/gpt_sample_fp8.txt); fp4: the MXFP4-weight step against both, the three alternating "
-                    "(profiles/gpt_sample_fp4.txt)")
+                    "(profiles/gpt_sample_fp4.txt); fp6: the MXFP6-weight step against all three (profiles/gpt_sample_fp6.txt)")
     ap.add_argument("--cache", choices=("h16", "fp8"), default="h16", help="fp8: instead of the tables, the step with MXFP8 k / v caches against the step "
                     "with 16-bit caches under the weights of --weights, and the decode attention alone (profiles/gpt_sample_kv8.txt, with --weights fp8 "
-                    "profiles/gpt_sample_kv8_w8.txt, with --weights fp4 profiles/gpt_sample_kv8_w4.txt)")
+                    "profiles/gpt_sample_kv8_w8.txt, with --weights fp6 profiles/gpt_sample_kv8_w6.txt, with --weights fp4 profiles/gpt_sample_kv8_w4.txt)")
     args = ap.parse_args()
     if args.out is None:
-        name = ("gpt_sample_graph.txt" if args.graph else dict(h16="gpt_sample_kv8.txt", fp8="gpt_sample_kv8_w8.txt", fp4="gpt_sample_kv8_w4.txt")[args.weights]
-                if args.cache == "fp8" else dict(h16="gpt_sample.txt", fp8="gpt_sample_fp8.txt", fp4="gpt_sample_fp4.txt")[args.weights])
+        name = ("gpt_sample_graph.txt" if args.graph else dict(h16="gpt_sample_kv8.txt", fp8="gpt_sample_kv8_w8.txt", fp6="gpt_sample_kv8_w6.txt", fp4="gpt_sample_kv8_w4.txt")[args.weights]
+                if args.cache == "fp8" else dict(h16="gpt_sample.txt", fp8="gpt_sample_fp8.txt", fp6="gpt_sample_fp6.txt", fp4="gpt_sample_fp4.txt")[args.weights])
         args.out = os.path.join(ROOT, "profiles", name)
     C, H, V, T, L = 6144, 16, 8192, 1024, args.layers
     torch.manual_seed(0)
@@ -406,6 +488,8 @@ def main():
         return fp8_mode(m, L, args.out)
     if args.weights == "fp4":
         return fp4_mode(m, L, args.out)
+    if args.weights == "fp6":
+        return fp6_mode(m, L, args.out)
     dt = torch.float16
     wbytes = (12 * C * C * L + V * C) * 2
     lines = [f"stage-2 sampling step on {torch.cuda.get_device_name(0)}: C={C} layers={L} heads={H} V={V}, fp16 operands; weights {wbytes / 1e9:.2f} GB per step",

@@ -20,6 +20,9 @@ the same fills (tools/sample_graph_bench.py), then one whole image through sampl
 --weights fp4 writes profiles/rq_sample_fp4.txt instead: the same position with MXFP4 Block weights (sample(weights="fp4")) against
 the fp8 and the 16-bit position, the three alternating in this process.
 
+--weights fp6 writes profiles/rq_sample_fp6.txt instead: the same position with MXFP6 Block weights (sample(weights="fp6")) against the
+16-bit, the fp8 and the fp4 position, the four alternating in this process.
+
 --cache fp8 writes profiles/rq_sample_kv8.txt instead: one position with MXFP8 spatial k / v caches (sample(cache="fp8")) against
 the position with 16-bit caches at batch 1, 4 and 64 and the same fills, alternating windows in this process."""
 import argparse
@@ -298,6 +301,59 @@ def fp4_mode(kw, out):
         f.write(text)
 
 
+def fp6_mode(kw, out):
+    """--weights fp6: one position (the spatial step, the D depth steps, their draws) with MXFP6 Block weights against 16-bit, MXFP8 and MXFP4
+    weights, the four alternating"""
+    C, V, T, D = kw["embed_dim"], kw["vocab_img_size"], kw["img_num_tokens"], kw["depth_num_tokens"]
+    Ls, Ld = kw["spatial_n_layers"], kw["depth_n_layers"]
+    dt = torch.float16
+    torch.manual_seed(0)
+    with torch.device("cuda"):
+        m = RQTransformer(**kw)
+        with torch.no_grad():
+            for p in (m.pos_emb_cond, m.pos_emb_code, m.pos_emb_depth):
+                p.normal_(0, 0.02)
+    blocks = 12 * C * C * Ls + D * 12 * C * C * Ld
+    head = D * V * C * 2
+    w16, w8, w6, w4 = blocks * 2 + head, blocks + blocks // 32 + head, blocks * 3 // 4 + blocks // 32 + head, blocks // 2 + blocks // 32 + head
+    f3 = lambda v: f"{v[1]:.3f} [{v[0]:.3f} .. {v[2]:.3f}]"
+    forms = ("h16", "fp8", "fp6", "fp4")
+    lines = [f"stage-2 RQTransformer sampling, MXFP6 Block weights against 16-bit, MXFP8 and MXFP4 weights, on {torch.cuda.get_device_name(0)}: C={C} spatial "
+             f"layers={Ls} depth layers={Ld} T={T} D={D} V={V}, fp16 activations and caches",
+             f"GEMM weights read per position {w16 / 1e9:.3f} GB (16-bit) / {w8 / 1e9:.3f} GB (fp8) / {w6 / 1e9:.3f} GB (fp6) / {w4 / 1e9:.3f} GB (fp4: codes + "
+             f"scales + the 16-bit head, read {D} times)",
+             "ms per position (spatial step + the D depth steps with their draws): median [min .. max] of 7 rounds of alternating windows of 10 positions in "
+             "one process",
+             f"{'batch':>5} {'slot':>5} {'16-bit ms [min .. max]':>28} {'fp8 ms [min .. max]':>28} {'fp6 ms [min .. max]':>28} {'fp4 ms [min .. max]':>28} "
+             f"{'fp8/fp6':>8} {'fp6/fp4':>8} {'not slower':>10} {'beyond fp8':>10}"]
+    for b in (1, 4):
+        sts = {w: m._decode_state(b, dt, "cuda", w) for w in forms}
+        codes = torch.randint(0, V, (b, T, D), device="cuda")
+        for t in (1, T - 1):
+            def position(w):
+                def run(i):
+                    m._spatial_step(sts[w], t, codes[:, t - 1, :])
+                    for d in range(D):
+                        m._depth_step(sts[w], t, d, None if d == 0 else codes[:, t, :d], False, False)
+                        _C.sample_logits(sts[w]["logits"], codes[:, t, d], top_k=None, top_p=None, seed=1, step=t * D + d)
+                return run
+            h, e, s, f = alternate([position(w) for w in forms], inner=10)
+            lines.append(f"{b:>5} {t:>5} {f3(h):>28} {f3(e):>28} {f3(s):>28} {f3(f):>28} {e[1] / s[1]:>8.3f} {s[1] / f[1]:>8.3f} "
+                         f"{'yes' if s[2] <= e[2] else 'NO':>10} {'yes' if s[2] < e[0] else 'no':>10}")
+        del sts
+        torch.cuda.empty_cache()
+    lines.append("not slower: the slowest fp6 window is no slower than the slowest fp8 window of the same point; beyond fp8: it is faster than the fastest fp8 window")
+    held = lambda w: sum(t.numel() * t.element_size() for k, st in m._sample_operands(dt, w).items() if k != "head" for W in st
+                         for n in ("wqkv", "wproj", "w0", "w1") for t in W[n])
+    lines.append(f"operand copies of the Blocks held by the process: {held('fp6') / 1e9:.3f} GB (fp6) against {held('fp8') / 1e9:.3f} GB (fp8) and "
+                 f"{held('fp4') / 1e9:.3f} GB (fp4)")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def kv8_mode(kw, out):
     """--cache fp8: one position (the spatial step, the D depth steps, their draws) with MXFP8 spatial k / v caches against 16-bit caches"""
     C, V, T, D = kw["embed_dim"], kw["vocab_img_size"], kw["img_num_tokens"], kw["depth_num_tokens"]
@@ -354,14 +410,15 @@ def main():
     ap.add_argument("--graph", action="store_true", help="instead of the tables: the eager loop against replays of one captured position "
                     "(profiles/rq_sample_graph.txt)")
     ap.add_argument("--whole", type=int, default=1, help="--graph: also draw one whole image through sample() both ways")
-    ap.add_argument("--weights", choices=("h16", "fp8", "fp4"), default="h16", help="fp8: instead of the tables, one position with MXFP8 Block weights "
-                    "against 16-bit weights (profiles/rq_sample_fp8.txt); fp4: with MXFP4 Block weights against both (profiles/rq_sample_fp4.txt)")
+    ap.add_argument("--weights", choices=("h16", "fp8", "fp6", "fp4"), default="h16", help="fp8: instead of the tables, one position with MXFP8 Block weights "
+                    "against 16-bit weights (profiles/rq_sample_fp8.txt); fp4: with MXFP4 Block weights against both (profiles/rq_sample_fp4.txt); "
+                    "fp6: with MXFP6 Block weights against all three (profiles/rq_sample_fp6.txt)")
     ap.add_argument("--cache", choices=("h16", "fp8"), default="h16", help="fp8: instead of the tables, one position with MXFP8 spatial k / v caches "
                     "against 16-bit caches (profiles/rq_sample_kv8.txt)")
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "rq_sample_graph.txt" if args.graph else "rq_sample_kv8.txt" if args.cache == "fp8" else
-                                dict(h16="rq_sample.txt", fp8="rq_sample_fp8.txt", fp4="rq_sample_fp4.txt")[args.weights])
+                                dict(h16="rq_sample.txt", fp8="rq_sample_fp8.txt", fp6="rq_sample_fp6.txt", fp4="rq_sample_fp4.txt")[args.weights])
     kw = dict(get_config_from_file(os.path.join(ROOT, "configs", "imagenet_rqtransformer_rqvae_base.yaml")).model.params.transformer.params)
     if args.spatial_layers is not None:
         kw["spatial_n_layers"] = args.spatial_layers
@@ -373,6 +430,8 @@ def main():
         return fp8_mode(kw, args.out)
     if args.weights == "fp4":
         return fp4_mode(kw, args.out)
+    if args.weights == "fp6":
+        return fp6_mode(kw, args.out)
     C, V, T, D = kw["embed_dim"], kw["vocab_img_size"], kw["img_num_tokens"], kw["depth_num_tokens"]
     Hs, Hd, Ls, Ld = kw["spatial_n_heads"], kw["depth_n_heads"], kw["spatial_n_layers"], kw["depth_n_layers"]
     dt = torch.float16

@@ -1,5 +1,5 @@
 """Class-conditional image sampling with a stage-2 config:  python tools/sample_images.py -c configs/imagenet_gpt_vitvq_base.yaml --ckpt last.ckpt
---classes 207 360 --top_k 100 --top_p 0.95 --temperature 1.0 --seed 0 [--graph] [--weights fp8|fp4] [--cache fp8] --out samples.png
+--classes 207 360 --top_k 100 --top_p 0.95 --temperature 1.0 --seed 0 [--graph] [--weights fp8|fp6|fp4] [--cache fp8] --out samples.png
 
 Builds the config's CondTransformer (condition model, stage-1 tokenizer, and the prior: GPT, or RQTransformer over a residual tokenizer as in
 configs/imagenet_rqtransformer_rqvae_base.yaml), loads `--ckpt` (a {"state_dict": ...} file; without it the config's own `path` entries or the
@@ -29,9 +29,9 @@ def main(argv=None):
     ap.add_argument("--fp32", action="store_true", help="the exact mode (use_fp16=False)")
     ap.add_argument("--graph", action="store_true", help="replay every position after the first from one captured HIP graph (sample(graph=True): "
                     "the same codes); without it ENH_GRAPHS=1 decides")
-    ap.add_argument("--weights", choices=("h16", "fp8", "fp4"), default=None, help="fp8: stream the Block weights as MXFP8 operands (sample(weights=\"fp8\"): half "
-                    "the weight bytes of a step and of the operand copies); fp4: as MXFP4 operands (a quarter; the format moves the logits far more, "
-                    "DESIGN.md §3.15); without it ENH_SAMPLE_WEIGHTS decides (default h16)")
+    ap.add_argument("--weights", choices=("h16", "fp8", "fp6", "fp4"), default=None, help="fp8: stream the Block weights as MXFP8 operands (sample(weights=\"fp8\"): half "
+                    "the weight bytes of a step and of the operand copies); fp6: as MXFP6 operands (0.76 of fp8's bytes at fp8's accuracy on block-scaled weights, DESIGN.md "
+                    "§3.16); fp4: as MXFP4 operands (a quarter; the format moves the logits far more, DESIGN.md §3.15); without it ENH_SAMPLE_WEIGHTS decides (default h16)")
     ap.add_argument("--cache", choices=("h16", "fp8"), default=None, help="fp8: hold the k / v caches as MXFP8 codes and scales (sample(cache=\"fp8\"): half "
                     "the cache bytes of a step and of device memory); without it ENH_SAMPLE_CACHE decides (default h16)")
     ap.add_argument("--nrow", type=int, default=4)
