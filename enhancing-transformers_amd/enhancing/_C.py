@@ -129,6 +129,8 @@ SIGNATURES = {
     "enh_grad_clip_coef_workspace_bytes": (_sz, [_i64]),
     "enh_grad_clip_coef": (_i32, [_vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "enh_adam_step_segments": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _f32, _f64, _f64, _f32, _f32, _vp, _vp, _vp, _f32, _i32, _vp]),
+    "enh_adam_step_segments_s16": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _f32, _f64, _f64, _f32, _f32, _vp, _vp, _vp, _f32, _u64, _vp,
+                                          _i32, _vp]),
     "enh_loss_scale_update": (_i32, [_vp, _vp, _vp, _f32, _f32, _i32, _vp]),
     "enh_nonfinite_flag": (_i32, [_vp, _i64, _vp, _vp]),
     "enh_skinny_gemm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
@@ -178,7 +180,7 @@ SIGNATURES = {
 }
 
 _LIB = None
-ABI_VERSION = 35 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 36 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -708,6 +710,29 @@ def adam_step_segments(p, g, m, v, arena, table, state, lr: float, beta1: float 
                                                        _p(state, F64, "state"), float(lr), float(beta1), float(beta2), float(eps), float(grad_scale),
                                                        _p(skip_flag, F32, "skip_flag"), _p(loss_scale, F32, "loss_scale"), _p(clip_coef, F32, "clip_coef"),
                                                        float(clip_value), dt, _stream()), "enh_adam_step_segments"), unit="byte")
+
+
+def adam_step_segments_s16(p, g, m16, v16, arena, table, state, lr: float, beta1: float = 0.9, beta2: float = 0.96, eps: float = 1e-8,
+                           grad_scale: float = 1.0, skip_flag=None, loss_scale=None, clip_coef=None, clip_value: float = 0.0, seed: int = 0, sr_words=None,
+                           dtype=None):
+    """adam_step_segments with bf16 moments m16, v16 (torch.bfloat16 [n]): widened exactly, p updated from the unrounded f32 moments, the stored moments
+    rounded stochastically with Philox words of (seed, group of 4 elements, applied step count) — include/enh_hip.h enh_adam_step_segments_s16.
+    sr_words (int32 [n], tests only) replaces the Philox words: element e's low half rounds m, its high half v."""
+    n = p.numel()
+    if g.numel() != n or m16.numel() != n or v16.numel() != n or (sr_words is not None and sr_words.numel() != n):
+        raise RuntimeError("adam_step_segments_s16: p, g, m16, v16 (and sr_words) must be equally long")
+    if table.dim() != 2 or table.shape[1] != 4 or state.numel() != 4:
+        raise RuntimeError("adam_step_segments_s16: table must be [nseg, 4] (adam_segment_table) and state f64 [4]")
+    dt = _dt(arena) if arena is not None else (DT_F16 if dtype == F16 else DT_BF16)
+    # 22 B per parameter: p, g (8) + m16, v16 (4) read, p (4) + m16, v16 (4) + the 16-bit operand (2) written
+    _timed(None, 22.0 * n,
+           lambda: _check(lib().enh_adam_step_segments_s16(_p(p, F32, "p"), _p(g, F32, "g"), _p(m16, BF16, "m16"), _p(v16, BF16, "v16"), n,
+                                                           _p(arena, H16, "arena"), 0 if arena is None else arena.numel(), _p(table, I64, "table"),
+                                                           table.shape[0], _p(state, F64, "state"), float(lr), float(beta1), float(beta2), float(eps),
+                                                           float(grad_scale), _p(skip_flag, F32, "skip_flag"), _p(loss_scale, F32, "loss_scale"),
+                                                           _p(clip_coef, F32, "clip_coef"), float(clip_value), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                           _p(sr_words, torch.int32, "sr_words"), dt, _stream()), "enh_adam_step_segments_s16"),
+           unit="byte")
 
 
 def loss_scale_update(scale, found_inf, tracker, growth: float = 2.0, backoff: float = 0.5, interval: int = 2000):

@@ -146,7 +146,8 @@ class CondTransformer(nn.Module):
         if lr is None:
             raise NotImplementedError("stage-2 training needs a learning rate: set `model.learning_rate` (main.py does) before configure_optimizers()")
         from ...engine.optim import GPTAdam
-        opt = GPTAdam(self.transformer, lr=lr, betas=(0.9, 0.96), weight_decay=0.01)
+        # adam_state: "f32" | "bf16" moments (main.py --adam_state); unset = ENH_ADAM_STATE, default f32
+        opt = GPTAdam(self.transformer, lr=lr, betas=(0.9, 0.96), weight_decay=0.01, state=self.__dict__.get("adam_state"))
         self.__dict__["_optimizer"] = opt
         schedulers = []
         if self.scheduler is not None:

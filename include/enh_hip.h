@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 35 /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 36 /* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -428,6 +428,23 @@ int enh_grad_clip_coef(const float* g, int64_t n, float max_norm, float grad_sca
 int enh_adam_step_segments(float* p, const float* g, float* m, float* v, int64_t n, enh_h16* arena, int64_t arena_n, const void* segments, int nseg,
                            double* state, float lr, double beta1, double beta2, float eps, float grad_scale, const float* skip_flag,
                            const float* loss_scale_dev, const float* clip_coef_dev, float clip_value, int dtype, void* stream);
+/* enh_adam_step_segments with the two moments held as bf16 (m16, v16: uint16_t [n], 16-byte aligned): 22 bytes per element instead of 30.  Everything
+ * not listed here is enh_adam_step_segments' contract: the segment table, padding never written, the arena image, the device step state advanced by the
+ * one-workgroup launch, and skip (a non-zero skip_flag writes nothing, m16 and v16 included).  No atomics.
+ * Per element: the old moments are widened exactly (bf16 << 16); gg, the new m and the new v are computed in f32 by the expressions above; p is updated
+ * from the UNROUNDED f32 new moments (a step's own rounding never enters its own update); only what is stored for the next step is rounded.
+ * Stored rounding of an f32 bit pattern u with a 16-bit word r: a finite u is stored as (u + r) >> 16 — stochastic rounding: up with probability
+ * (low half) / 2^16 — and where that would carry a finite value to infinity, as the largest finite bf16 of that sign; a nan or an infinity is stored
+ * by truncation with the quiet bit kept (nan stays nan, inf stays inf).  Integer arithmetic only, so the same through subnormals.
+ * The words: the 4 consecutive elements of group G = e / 4 take one call
+ *   philox4x32_10((uint32)sr_seed, (uint32)(sr_seed >> 32), {(uint32)G, (uint32)(G >> 32), (uint32)t, (uint32)(t >> 32)})
+ * with t = the number of applied steps after the advance (state[0]); word k serves element 4G + k: its low 16 bits round m, its high 16 bits v.  A
+ * dropped step consumes no randomness (t does not move); the same seed gives the same bits on every run.  sr_words (optional, uint32 [n], 16-byte
+ * aligned; tests only) replaces the Philox words with sr_words[e], laid out the same way (low half m, high half v). */
+int enh_adam_step_segments_s16(float* p, const float* g, uint16_t* m16, uint16_t* v16, int64_t n, enh_h16* arena, int64_t arena_n, const void* segments,
+                               int nseg, double* state, float lr, double beta1, double beta2, float eps, float grad_scale, const float* skip_flag,
+                               const float* loss_scale_dev, const float* clip_coef_dev, float clip_value, uint64_t sr_seed, const uint32_t* sr_words,
+                               int dtype, void* stream);
 
 /* Device-side tail of the input pipeline (enhancing/dataloader/imagenet.py:26-54: ... RandomCrop / CenterCrop -> RandomHorizontalFlip -> ToTensor):
  * src uint8 [B,Hs,Ws,3] (decoded + resized images, each in the top-left corner of its slot), meta int32 [B,3] = (y0, x0, flip) -> out f32 [B,3,R,R] in [0,1].

@@ -37,6 +37,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="(extension) 'norm' = clip_grad_norm_ to --gradient_clip_val, 'value' = clamp every element to +-gradient_clip_val")
     parser.add_argument('--track_grad_norm', type=int, default=-1, choices=(-1, 2),
                         help="(extension) 2 = log train/grad_norm (and train/grad_norm_disc) to metrics.jsonl without clipping; -1 = off")
+    parser.add_argument('--adam_state', type=str, default=None, choices=("f32", "bf16"),
+                        help="(extension, stage 2) the Adam moments' format: bf16 = half the optimizer state, stored with stochastic rounding; "
+                             "unset = ENH_ADAM_STATE, default f32")
     return parser
 
 
@@ -57,6 +60,8 @@ if __name__ == '__main__':
     config = get_config_from_file(Path(ROOT) / "configs" / (args.config + ".yaml"))
     model = initialize_from_config(config.model)
     model.learning_rate = args.base_lr
+    if args.adam_state is not None:
+        model.adam_state = args.adam_state      # read by CondTransformer.configure_optimizers (stage 2 only)
     data = initialize_from_config(config.dataset)
     data.prepare_data()
     # reference main.py:52: precision = 16 if --use_amp else 32, i.e. fp16 autocast + GradScaler under --use_amp.  Here that mixed precision (fp16 MFMA
