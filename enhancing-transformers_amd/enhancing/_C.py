@@ -175,12 +175,14 @@ SIGNATURES = {
     "enh_decode_attention_at": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _i32, _vp]),
     "enh_decode_attention_kv8": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _i32, _vp]),
     "enh_decode_attention_kv8_at": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _sz, _i32, _vp]),
+    "enh_kv_cache_fill": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "enh_kv_cache_fill_kv8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "enh_embed_step_at": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "enh_sample_logits_at": (_i32, [_vp, _i32, _i32, _f32, _i32, _f32, _u64, _u32, _vp, _i32, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp]),
 }
 
 _LIB = None
-ABI_VERSION = 36 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
+ABI_VERSION = 37 # ENH_ABI_VERSION of the include/enh_hip.h these signatures were written against
 
 
 def lib():
@@ -1294,6 +1296,43 @@ def decode_attention_kv8(qkv, k_codes, k_scales, v_codes, v_scales, t: int, out)
            lambda: _check(L.enh_decode_attention_kv8(_p(qkv, dt, "qkv"), _p(k_codes, U8, "k_codes"), _p(k_scales, U8, "k_scales"), _p(v_codes, U8, "v_codes"),
                                                      _p(v_scales, U8, "v_scales"), B, H, hs, Tmax, int(t), _p(out, dt, "out"), _p(ws), ws.numel(),
                                                      _DT_OF[dt], _stream()), "enh_decode_attention_kv8"), unit="byte")
+
+
+def kv_cache_fill(qkv, S: int, k_cache, v_cache, slot0: int = 0):
+    """the k and v columns of row (b, s) of the packed qkv [B S, 3C] copied bit for bit to slot slot0 + s of k_cache / v_cache [B,H,Tmax,hs]
+    (enh_kv_cache_fill): what S decode_attention calls append, in one launch; one dtype (bf16 | fp16 | f32); other slots are not touched"""
+    if k_cache.dim() != 4:
+        raise RuntimeError(f"kv_cache_fill: k_cache {tuple(k_cache.shape)} must be [B, H, Tmax, hs]")
+    B, H, Tmax, hs = k_cache.shape
+    dt = qkv.dtype
+    if tuple(v_cache.shape) != (B, H, Tmax, hs) or tuple(qkv.shape) != (B * int(S), 3 * H * hs) or k_cache.dtype != dt or v_cache.dtype != dt:
+        raise RuntimeError(f"kv_cache_fill: qkv {tuple(qkv.shape)} {dt} caches {tuple(k_cache.shape)} {tuple(v_cache.shape)} {k_cache.dtype} do not fit S={S}")
+    if dt not in _DT_OF:
+        raise RuntimeError(f"kv_cache_fill: dtype must be bf16, fp16 or f32, got {dt}")
+    # bytes moved: the k and v columns read and written once
+    _timed(None, 4.0 * qkv.element_size() * B * int(S) * H * hs,
+           lambda: _check(lib().enh_kv_cache_fill(_p(qkv, dt, "qkv"), B, int(S), H, hs, Tmax, int(slot0), _p(k_cache, dt, "k_cache"), _p(v_cache, dt, "v_cache"),
+                                                  _DT_OF[dt], _stream()), "enh_kv_cache_fill"), unit="byte")
+
+
+def kv_cache_fill_kv8(qkv, S: int, k_codes, k_scales, v_codes, v_scales, slot0: int = 0):
+    """kv_cache_fill into an MXFP8 cache (enh_kv_cache_fill_kv8): row (b, s) of qkv [B S, 3C] (bf16 | fp16) is quantized as decode_attention_kv8's
+    append quantizes it and its codes and scales go to slot slot0 + s; the dequantized values are written back over the k and v columns of qkv"""
+    if k_codes.dim() != 4:
+        raise RuntimeError(f"kv_cache_fill_kv8: k_codes {tuple(k_codes.shape)} must be [B, H, Tmax, hs]")
+    B, H, Tmax, hs = k_codes.shape
+    if (tuple(v_codes.shape) != (B, H, Tmax, hs) or hs % MX_BLOCK or tuple(k_scales.shape) != (B, H, Tmax, hs // MX_BLOCK)
+            or tuple(v_scales.shape) != (B, H, Tmax, hs // MX_BLOCK) or tuple(qkv.shape) != (B * int(S), 3 * H * hs)):
+        raise RuntimeError(f"kv_cache_fill_kv8: qkv {tuple(qkv.shape)} codes {tuple(k_codes.shape)} {tuple(v_codes.shape)} scales {tuple(k_scales.shape)} "
+                           f"{tuple(v_scales.shape)} do not fit S={S} (scales [B, H, Tmax, hs / {MX_BLOCK}])")
+    dt = qkv.dtype
+    if dt not in H16:
+        raise RuntimeError(f"kv_cache_fill_kv8: qkv must be bf16 or fp16 (the exact f32 mode has no MXFP8 cache), got {dt}")
+    # bytes moved: the k and v columns read and written back, the codes and the scales written
+    _timed(None, 2.0 * B * int(S) * H * (4 * hs + hs + hs // MX_BLOCK),
+           lambda: _check(lib().enh_kv_cache_fill_kv8(_p(qkv, dt, "qkv"), B, int(S), H, hs, Tmax, int(slot0), _p(k_codes, U8, "k_codes"),
+                                                      _p(k_scales, U8, "k_scales"), _p(v_codes, U8, "v_codes"), _p(v_scales, U8, "v_scales"), _DT_OF[dt],
+                                                      _stream()), "enh_kv_cache_fill_kv8"), unit="byte")
 
 
 def row_ln_scale(x, w, b, out, colscale=None, eps: float = 1e-5):

@@ -35,7 +35,14 @@ Blocks of GPT, the spatial stack of RQTransformer) as MXFP8 codes and scales wit
 and attends through enh_decode_attention_kv8 (csrc/gpt_decode_kv8.hip), which quantizes the step's k / v rows as it appends them; the RQ depth
 caches stay 16-bit.  The step methods choose the launch through prior.py `_step_attention`.
 
-Left out: an exact-f32 backward, more than one condition token, HIP-graph capture of position 0 and of the teacher-forced entries, graphs kept
+Both also take `prefix_codes=`: the first P positions are GIVEN and the rest is drawn, which is image completion and the
+resumption of a partly drawn image.  The given codes enter the caches through one batched prefill per chunk (`_prefill`; prior.py
+`_prefill_stack`): the teacher-forced forward's launches at S = 1, i.e. under the SAMPLER's model, with the rows' k / v written into slots
+0 .. P - 1 by enh_kv_cache_fill / enh_kv_cache_fill_kv8 (csrc/gpt_prefill_cache.hip) and the tile attention over N = P; the loop then runs
+positions P .. T - 1 unchanged, under graph=True from a cursor that starts at P + 1.  CondTransformer.complete is the public form.
+
+Left out: per-row prefix lengths, a prefix for the RQ depth stack, caches kept from call to call, a wide (prefill-shaped) product for MX
+weights, an exact-f32 backward, more than one condition token, HIP-graph capture of position 0 and of the teacher-forced entries, graphs kept
 from call to call, relu^2 / LayerNorm fused into GEMM epilogues, 8-bit activations (W8A8), an 8-bit form of the RQ depth caches, the e3m2
 form of MXFP6, a quantized head, MXFP8 / MXFP6 / MXFP4 in the teacher-forced entries, W4A8 / W6A8 on the scaled MFMA, quantized checkpoints on disk."""
 import os
@@ -45,7 +52,8 @@ import torch
 import torch.nn as nn
 
 from .prior import (FORWARD_HIDDEN_CAP, MAX_BATCH, MAX_EMBED, MAX_HEAD, MAX_TOKENS, MAX_VOCAB, OPERAND_DTYPE, Prior,  # noqa: F401  (re-exported)
-                    _block_rows, _block_rows_backward, _block_step, _grad_linears, _kv_caches, _row_linear, _step_attention, _step_linear)
+                    _block_rows, _block_rows_backward, _block_step, _grad_linears, _kv_caches, _prefill_buffers, _prefill_stack, _row_linear,
+                    _step_attention, _step_linear)
 
 BACKWARD_SAVED_CAP = 16 << 30  # bytes of forward_backward()'s saved activations: shipped size 24 x 172,096 B per token, 4 sequences of 1024 per chunk
 MAX_DEPTH = 8           # enh_rq_embed_seq, enh_short_causal_attention_forward: the stage-1 residual quantizer's cap on num_quantizers
@@ -227,8 +235,19 @@ class GPT(Prior):
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
                use_fp16: bool = True, *, seed: Optional[int] = None, forced_codes: Optional[torch.Tensor] = None, return_logits: bool = True,
                call: int = 0, row_offset: int = 0, graph: Optional[bool] = None, weights: Optional[str] = None,
-               cache: Optional[str] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+               cache: Optional[str] = None, prefix_codes: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """reference layers.py:213-266: returns (logits [B, T*V] after the temperature and the top-k mask, codes [B, T]).
+
+        prefix_codes [B, P] (anything with B rows that reshapes to it, e.g. [B, h', w]; 0 <= P < T, ids in [0, V), else a ValueError) CONTINUES an
+        image: positions < P are given, positions >= P are drawn (or fed from forced_codes) exactly as without it, under the step
+        numbers t and so the uniforms of a full run.  The given codes enter the k / v caches through one batched prefill per chunk instead of P
+        weight-streaming steps: the rows of the condition and of codes 0 .. P - 2 go through every Block but the last layer's attention, proj and
+        MLP under the SAMPLER's model (every row is ln1(x) * time_mix, no previous-row term), their k / v rows fill slots 0 .. P - 1
+        (enh_kv_cache_fill, for cache="fp8" enh_kv_cache_fill_kv8) and enh_causal_attention_forward attends over them; the products are enh_gemm_h16
+        over all rows, or under weights="fp8" | "fp6" | "fp4" the step's own product in pieces of 64 rows (the codes are re-read once per piece).
+        The returned codes[:, :P] is the prefix; the logits of positions < P are NOT computed and are returned as NaN.  With forced_codes its
+        first P positions must equal the prefix (a ValueError).  P == 0 is the call without a prefix, launch for launch.  Under graph=True the
+        prefill and position P run eagerly, and the captured position is replayed T - P - 1 times.
 
         graph=True replays every position after the first from ONE captured HIP graph per chunk: the launches of a position
         in their cursor forms, which read the position from device memory; the same bits as the loop.  None reads ENH_GRAPHS == "1", False is the
@@ -255,6 +274,7 @@ class GPT(Prior):
         Batches above 64 rows run in chunks of 64 rows.
         Side effect: a module whose parameters are not on the device of `conds` is MOVED there (`self.to(conds.device)`) on the first call, as the
         stage-1 engine moves its model; the reference leaves that to the caller."""
+        prefix_codes = self._check_prefix(prefix_codes, conds.shape[0], "GPT.sample")
         if not conds.is_cuda:
             raise RuntimeError("GPT.sample runs on a ROCm device only: conds must be a device tensor (there is no CPU path)")
         dev = conds.device
@@ -273,44 +293,67 @@ class GPT(Prior):
         cache = self._sample_cache(cache, use_fp16, "GPT.sample")
         codes = torch.empty(B, T, dtype=torch.int64, device=dev)
         logits = torch.empty(B, T * V, dtype=torch.float32, device=dev) if return_logits else None
+        if prefix_codes is not None:
+            prefix_codes = self._place_prefix(prefix_codes, forced_codes, codes, logits, "GPT.sample")
         if self._use_graph(graph):
             state = lambda b: self._decode_state(b, dt, dev, weights=weights, cache=cache)
             self._sample_graphed(B, dev, state, lambda st, s, e, positions: self._sample_rows_graphed(
                 st, positions, conds[s:e], codes[s:e], None if logits is None else logits[s:e], None if forced_codes is None else forced_codes[s:e],
-                top_k, top_p, float(softmax_temperature), seed, call, row_offset + s))
+                top_k, top_p, float(softmax_temperature), seed, call, row_offset + s, None if prefix_codes is None else prefix_codes[s:e]))
             return logits, codes
         for s in range(0, B, MAX_BATCH):
             e = min(s + MAX_BATCH, B)
             self._sample_rows(conds[s:e], codes[s:e], None if logits is None else logits[s:e], None if forced_codes is None else forced_codes[s:e],
-                              dt, top_k, top_p, float(softmax_temperature), seed, call, row_offset + s, weights, cache)
+                              dt, top_k, top_p, float(softmax_temperature), seed, call, row_offset + s, weights, cache,
+                              None if prefix_codes is None else prefix_codes[s:e])
         return logits, codes
 
-    def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0, weights: str = "h16", cache: str = "h16"):
+    def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0, weights: str = "h16", cache: str = "h16",
+                     prefix=None):
         from ... import _C
         T, V = self.img_num_tokens, self.vocab_img_size
         st = self._decode_state(conds.shape[0], dt, conds.device, weights=weights, cache=cache)
         feed = codes if forced is None else forced
-        for t in range(T):
+        P = 0 if prefix is None else prefix.shape[1]
+        if P:
+            self._prefill(st, conds, prefix)
+        for t in range(P, T):
             self._decode_step(st, t, conds if t == 0 else feed[:, t - 1])
             _C.sample_logits(st["logits"], codes[:, t], temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, call=call, step=t, row0=row0,
                              logits_out=None if logits is None else logits[:, t * V:(t + 1) * V])
 
-    def _sample_rows_graphed(self, st, positions, conds, codes, logits, forced, top_k, top_p, temperature, seed, call, row0):
-        """_sample_rows for Prior._sample_graphed: position 0 as there, every later one the same launches in their cursor forms"""
+    def _sample_rows_graphed(self, st, positions, conds, codes, logits, forced, top_k, top_p, temperature, seed, call, row0, prefix=None):
+        """_sample_rows for Prior._sample_graphed: position 0 (under a prefix of P positions the prefill and position P) as there, every later one
+        the same launches in their cursor forms"""
         from ... import _C
         V = self.vocab_img_size
         feed = codes if forced is None else forced
         draw = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, call=call, row0=row0)
+        P = 0 if prefix is None else prefix.shape[1]
 
         def first():
-            self._decode_step(st, 0, conds)
-            _C.sample_logits(st["logits"], codes[:, 0], step=0, logits_out=None if logits is None else logits[:, :V], **draw)
+            if P:
+                self._prefill(st, conds, prefix)
+            self._decode_step(st, P, feed[:, P - 1] if P else conds)
+            _C.sample_logits(st["logits"], codes[:, P], step=P, logits_out=None if logits is None else logits[:, P * V:(P + 1) * V], **draw)
 
         def later(cursor):
             self._decode_step(st, None, feed, cursor=cursor)
             _C.sample_logits_at(st["logits"], codes, cursor, logits_out=logits, **draw)
 
-        positions(self.img_num_tokens, first, later)
+        positions(self.img_num_tokens, first, later, P)
+
+    def _prefill(self, st: dict, conds, prefix) -> None:
+        """the given codes prefix [b, P] of a chunk put into slots 0 .. P - 1 of every layer's cache of `st` (prior.py `_prefill_stack`): rows
+        s = 0 .. P - 1 (the condition, then codes 0 .. P - 2) are built in one embedding launch per group of whole sequences"""
+        from ... import _C
+        (b, P), C = prefix.shape, self.embed_dim
+        pf = _prefill_buffers(b, P, C, st["dt"], prefix.device, self.forward_hidden_cap)
+        for b0 in range(0, b, pf["g"]):
+            n = min(pf["g"], b - b0)
+            _C.gpt_embed_seq(conds[b0:b0 + n], prefix[b0:b0 + n], self.tok_emb_cond.weight.detach(), self.pos_emb_cond.detach()[0, 0],
+                             self.tok_emb_code.weight.detach(), self.pos_emb_code.detach()[0], pf["x"][:n * P].view(n, P, C))
+            _prefill_stack(self.blocks, st["ops"]["layers"], st["caches"], b0, n, P, self.n_heads, st["dt"], pf)
 
     def _decode_state(self, b: int, dt: torch.dtype, dev, cache_len: Optional[int] = None, weights: str = "h16", cache: str = "h16") -> dict:
         """the buffers of one chunk of b <= 64 rows: residual stream, activations, the step's logits and every layer's k / v cache [b, H, T, hs]
@@ -598,7 +641,8 @@ class RQTransformer(Prior):
     def sample(self, conds: torch.Tensor, top_k: Optional[float] = None, top_p: Optional[float] = None, softmax_temperature: float = 1.0,
                use_fp16: bool = True, *, seed: Optional[int] = None, forced_codes: Optional[torch.Tensor] = None, return_logits: bool = True,
                call: int = 0, row_offset: int = 0, slot0_ln: str = "once", graph: Optional[bool] = None,
-               weights: Optional[str] = None, cache: Optional[str] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+               weights: Optional[str] = None, cache: Optional[str] = None,
+               prefix_codes: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """reference layers.py:397-547 (sample, sample_spatial_step, sample_depth_step) with one condition token: returns (logits [B T, D, V] f32
         after the temperature and the top-k mask, codes [B, T, D] int64).  GPT.sample's contract: the loop is restated per
         step, one row per batch element.  Per position t the spatial Blocks run under a cache of T slots on the input row
@@ -635,7 +679,15 @@ class RQTransformer(Prior):
 
         cache="fp8" is GPT.sample's for the SPATIAL stack: its k / v caches are MXFP8 codes and scales behind enh_decode_attention_kv8 (DESIGN.md
         §3.14); the depth caches (D <= 8 slots, enh_short_decode_attention) stay 16-bit.  None reads ENH_SAMPLE_CACHE (default "h16"); it needs
-        use_fp16=True."""
+        use_fp16=True.
+
+        prefix_codes [B, P, D] (anything with B rows and a last axis of D that reshapes to it, e.g. [B, h', w, D]; 0 <= P < T, ids in [0, V), else
+        a ValueError) is GPT.sample's for the SPATIAL stack: positions < P are given with all their D codes, one batched prefill
+        per chunk puts the spatial rows of the condition and of positions 0 .. P - 2 (the spatial stream of enh_rq_embed_seq) into slots
+        0 .. P - 1 of the spatial caches under the sampler's model, and the loop runs positions P .. T - 1 unchanged under their step numbers
+        t D + d.  The depth stack needs no prefix: its caches are rewritten at every position.  codes[:, :P] is the prefix, the logits of positions
+        < P are NOT computed and are returned as NaN; with forced_codes its first P positions must equal the prefix."""
+        prefix_codes = self._check_prefix(prefix_codes, conds.shape[0] if torch.is_tensor(conds) else 0, "RQTransformer.sample")
         if not (torch.is_tensor(conds) and conds.is_cuda):
             raise NotImplementedError("RQTransformer.sample: sampling runs on a ROCm device only: conds must be a device tensor (the spatial / depth "
                                       "decode loop is HIP kernels: there is no CPU path)")
@@ -666,17 +718,20 @@ class RQTransformer(Prior):
         cache = self._sample_cache(cache, use_fp16, "RQTransformer.sample")
         codes = torch.empty(B, T, D, dtype=torch.int64, device=dev)
         logits = torch.empty(B * T, D, V, dtype=torch.float32, device=dev) if return_logits else None
+        if prefix_codes is not None:
+            prefix_codes = self._place_prefix(prefix_codes, forced_codes, codes, logits, "RQTransformer.sample")
         if self._use_graph(graph):
             self._sample_graphed(B, dev, lambda b: self._decode_state(b, dt, dev, weights, cache), lambda st, s, e, positions: self._sample_rows_graphed(
                 st, positions, conds[s:e], codes[s:e], None if logits is None else logits.view(B, T, D, V)[s:e],
                 None if forced_codes is None else forced_codes[s:e], top_k, top_p, float(softmax_temperature), seed, call, row_offset + s,
-                slot0_ln == "twice", depth_decode == "cache"))
+                slot0_ln == "twice", depth_decode == "cache", None if prefix_codes is None else prefix_codes[s:e]))
             return logits, codes
         for s in range(0, B, MAX_BATCH):
             e = min(s + MAX_BATCH, B)
             self._sample_rows(conds[s:e], codes[s:e], None if logits is None else logits.view(B, T, D, V)[s:e],
                               None if forced_codes is None else forced_codes[s:e], dt, top_k, top_p, float(softmax_temperature), seed, call,
-                              row_offset + s, slot0_ln == "twice", depth_decode == "cache", weights, cache)
+                              row_offset + s, slot0_ln == "twice", depth_decode == "cache", weights, cache,
+                              None if prefix_codes is None else prefix_codes[s:e])
         return logits, codes
 
     def _decode_state(self, b: int, dt: torch.dtype, dev, weights: str = "h16", cache: str = "h16") -> dict:
@@ -692,13 +747,17 @@ class RQTransformer(Prior):
                     depth=[(e(b, Hd, D, C // Hd), e(b, Hd, D, C // Hd)) for _ in self.depth_transformer], ops=self._sample_operands(dt, weights))
 
     def _sample_rows(self, conds, codes, logits, forced, dt, top_k, top_p, temperature, seed, call, row0, ln_twice: bool, depth_cache: bool,
-                     weights: str = "h16", cache: str = "h16"):
-        """one chunk of b <= 64 rows: codes [b, T, D] (a view the draws are written into), logits [b, T, D, V] (a view) or None"""
+                     weights: str = "h16", cache: str = "h16", prefix=None):
+        """one chunk of b <= 64 rows: codes [b, T, D] (a view the draws are written into), logits [b, T, D, V] (a view) or None; prefix [b, P, D]
+        or None: the given positions, which `_prefill` puts into the spatial caches"""
         from ... import _C
         T, D = self.img_num_tokens, self.depth_num_tokens
         st = self._decode_state(conds.shape[0], dt, conds.device, weights, cache)
         feed = codes if forced is None else forced
-        for t in range(T):
+        P = 0 if prefix is None else prefix.shape[1]
+        if P:
+            self._prefill(st, conds, prefix)
+        for t in range(P, T):
             self._spatial_step(st, t, conds if t == 0 else feed[:, t - 1, :])
             for d in range(D):
                 self._depth_step(st, t, d, None if d == 0 else feed[:, t, :d], ln_twice, depth_cache)
@@ -706,19 +765,22 @@ class RQTransformer(Prior):
                                  row0=row0, logits_out=None if logits is None else logits[:, t, d, :])
 
     def _sample_rows_graphed(self, st, positions, conds, codes, logits, forced, top_k, top_p, temperature, seed, call, row0, ln_twice: bool,
-                             depth_cache: bool):
-        """_sample_rows for Prior._sample_graphed: position 0 as there, every later one the same launches with the spatial attention, the input
-        rows and the draws in their cursor forms"""
+                             depth_cache: bool, prefix=None):
+        """_sample_rows for Prior._sample_graphed: position 0 (under a prefix of P positions the prefill and position P) as there, every later
+        one the same launches with the spatial attention, the input rows and the draws in their cursor forms"""
         from ... import _C
         D = self.depth_num_tokens
         feed = codes if forced is None else forced
         draw = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, call=call, row0=row0)
+        P = 0 if prefix is None else prefix.shape[1]
 
         def first():
-            self._spatial_step(st, 0, conds)
+            if P:
+                self._prefill(st, conds, prefix)
+            self._spatial_step(st, P, feed[:, P - 1, :] if P else conds)
             for d in range(D):
-                self._depth_step(st, 0, d, None if d == 0 else feed[:, 0, :d], ln_twice, depth_cache)
-                _C.sample_logits(st["logits"], codes[:, 0, d], step=d, logits_out=None if logits is None else logits[:, 0, d, :], **draw)
+                self._depth_step(st, P, d, None if d == 0 else feed[:, P, :d], ln_twice, depth_cache)
+                _C.sample_logits(st["logits"], codes[:, P, d], step=P * D + d, logits_out=None if logits is None else logits[:, P, d, :], **draw)
 
         def later(cursor):
             self._spatial_step(st, None, feed, cursor=cursor)
@@ -726,7 +788,23 @@ class RQTransformer(Prior):
                 self._depth_step(st, None, d, None if d == 0 else feed, ln_twice, depth_cache, cursor=cursor)
                 _C.sample_logits_at(st["logits"], codes, cursor, step_mul=D, step_add=d, logits_out=logits, **draw)
 
-        positions(self.img_num_tokens, first, later)
+        positions(self.img_num_tokens, first, later, P)
+
+    def _prefill(self, st: dict, conds, prefix) -> None:
+        """the given positions prefix [b, P, D] of a chunk put into slots 0 .. P - 1 of every spatial layer's cache of `st` (prior.py
+        `_prefill_stack`): the spatial rows s = 0 .. P - 1 (the condition, then the depth sums of positions 0 .. P - 2) are the spatial stream of
+        enh_rq_embed_seq at T = P, enh_rq_embed_step's bits; the depth stream it also writes is discarded (the depth caches are rewritten at every
+        position)"""
+        from ... import _C
+        (b, P, D), C = prefix.shape, self.embed_dim
+        pf = _prefill_buffers(b, P, C, st["dt"], prefix.device, self.forward_hidden_cap)
+        unused = torch.empty(pf["g"] * P, D, C, dtype=torch.float32, device=prefix.device)
+        for b0 in range(0, b, pf["g"]):
+            n = min(pf["g"], b - b0)
+            _C.rq_embed_seq(conds[b0:b0 + n], prefix[b0:b0 + n], self.tok_emb_cond.weight.detach(), self.pos_emb_cond.detach()[0, 0],
+                            self.tok_emb_code.weight.detach(), self.pos_emb_code.detach()[0], self.pos_emb_depth.detach()[0],
+                            pf["x"][:n * P].view(n, P, C), unused[:n * P])
+            _prefill_stack(self.spatial_transformer, st["ops"]["spatial"], st["spatial"], b0, n, P, self.spatial_n_heads, st["dt"], pf)
 
     def _spatial_step(self, st: dict, t: Optional[int], ids: torch.Tensor, cursor: Optional[torch.Tensor] = None) -> None:
         """position t of the spatial transformer, one row per batch element: ids (int64, on the device: the condition [b] at t == 0, else the D

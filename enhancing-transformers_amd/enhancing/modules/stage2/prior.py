@@ -1,6 +1,7 @@
 """What the stage-2 priors of layers.py (GPT, RQTransformer) and their optimizer (engine/optim.py GPTAdam) share, each stated once: the limits of
 the kernels, the launches of one Block over whole sequences forward (`_block_rows`) and backward (`_block_rows_backward`) with the products between
-them (`_row_linear`, `_grad_linears`), the launches of one Block in a cached sampling step (`_block_step`) and the product they run (`_step_linear`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`; MXFP8, MXFP6 and MXFP4: `_layer_operands_mx`), the k / v caches of a sampling chunk and the attention over them (`_kv_caches`, `_step_attention`), the flat
+them (`_row_linear`, `_grad_linears`), the launches of one Block in a cached sampling step (`_block_step`) and the product they run (`_step_linear`), the operand copies of a stack of Blocks (`_layer_operands`, `qkv_bias`; MXFP8, MXFP6 and MXFP4: `_layer_operands_mx`), the k / v caches of a sampling chunk and the attention over them (`_kv_caches`, `_step_attention`), the prefill of given codes into those caches (`_prefill_stack` with its
+products `_prefill_linear` and buffers `_prefill_buffers`; `Prior._check_prefix`, `_place_prefix`), the flat
 parameter layout
 (`flat_layout`), a layer's slice of the optimizer's operand arena (`ARENA_LAYER`), and `Prior`, the base class: init, input checks, the
 version-keyed operand cache, the one-chunk-at-a-time buffer cache and the two teacher-forced drivers (forward: chunks, cross-entropy rows, mean; forward_backward: chunks under the
@@ -253,6 +254,65 @@ def _block_step(blk, W, linear, attention, x, x2, a, qkv, att, hid) -> None:
     linear(hid, W["w1"], x, bias=blk.mlp.p1.bias, res=x2)
 
 
+# ---- the prefill of a sampling chunk: given codes put into the caches ------------------------------------------------------------------
+def _prefill_linear(M: int, dt: torch.dtype):
+    """linear(inp, w, out, bias, res, relu_sq) over the M rows of a prefill: `_row_linear` for a 16-bit or (exact mode) f32 weight; for an MXFP8 /
+    MXFP6 / MXFP4 operand the step's own product (`_step_linear`) in pieces of at most MAX_BATCH rows, which re-reads the codes once per piece and
+    builds no 16-bit copy of the weight"""
+    rows = _row_linear(M, dt)
+    if dt == torch.float32:
+        return rows
+    step = _step_linear(dt)
+
+    def linear(inp, w, out, bias=None, res=None, relu_sq=False):
+        if not isinstance(w, tuple):      # (MXFP6 and MXFP4 are NamedTuples, MXFP8 a plain pair)
+            return rows(inp, w, out, bias=bias, res=res, relu_sq=relu_sq)
+        for m0 in range(0, M, MAX_BATCH):
+            m1 = min(m0 + MAX_BATCH, M)
+            step(inp[m0:m1], w, out[m0:m1], bias=bias, relu_sq=relu_sq, res=None if res is None else res[m0:m1])
+    return linear
+
+
+def _prefill_buffers(b: int, P: int, C: int, dt: torch.dtype, dev, hidden_cap: int) -> dict:
+    """the buffers of a prefill of b sequences of P rows, apart from the b-row buffers of the steps: g, the whole sequences of one group, sized so
+    that the [g P, 4C] hidden activation (f32 and its operand copy) stays under `hidden_cap` bytes, and `_block_rows`' buffers at g P rows"""
+    f32 = torch.float32
+    g = max(1, min(b, int(hidden_cap) // (P * 4 * C * (4 + (2 if dt != f32 else 0)))))
+    M = g * P
+    e = lambda *shape, dtype=dt: torch.empty(*shape, dtype=dtype, device=dev)
+    return dict(g=g, x=e(M, C, dtype=f32), x2=e(M, C, dtype=f32), a=e(M, C), qkv=e(M, 3 * C), att=e(M, C), hid32=e(M, 4 * C, dtype=f32),
+                hid=e(M, 4 * C) if dt != f32 else None)
+
+
+def _prefill_stack(blocks, layers, caches, b0: int, n: int, P: int, H: int, dt: torch.dtype, pf: dict) -> None:
+    """rows s = 0 .. P - 1 of n sequences, built in pf["x"] [n P, C], through a stack of Blocks under the SAMPLER's model: under
+    the cache time_shift is zero in every Block, so every row is ln1(x) * time_mix with no previous-row term, which is enh_ln_timeshift at S = 1
+    over all rows.  Per layer `_block_rows`' launches at S = 1 with the fill of slots 0 .. P - 1 of caches[layer][b0 : b0 + n] (`_kv_caches`:
+    enh_kv_cache_fill, or for an MXFP8 cache enh_kv_cache_fill_kv8, which also leaves in qkv what the slots now hold) in front of the causal
+    attention over N = P.  The last layer stops behind its fill: nothing of it is needed any more."""
+    from ... import _C
+    M = n * P
+    x, x2, a, qkv, att, hid32, hid = (None if pf[k] is None else pf[k][:M] for k in ("x", "x2", "a", "qkv", "att", "hid32", "hid"))
+    hs = x.shape[1] // H
+    linear = _prefill_linear(M, dt)
+
+    def fill(kv):
+        (_C.kv_cache_fill_kv8 if len(kv) == 4 else _C.kv_cache_fill)(qkv, P, *(c[b0:b0 + n] for c in kv))
+
+    for i, (blk, W, kv) in enumerate(zip(blocks, layers, caches)):
+        if i == len(blocks) - 1:
+            _C.ln_timeshift(x, blk.ln1.weight, blk.ln1.bias, a, 1, colscale=W["time_mix"], eps=blk.ln1.eps)
+            linear(a, W["wqkv"], qkv, bias=W["bqkv"])
+            fill(kv)
+            return
+
+        def attention(q, o, kv=kv):
+            fill(kv)
+            _C.causal_attention(q, n, P, H, hs, o)
+
+        _block_rows(blk, W, linear, dt, 1, attention, x, x, a, a, qkv, att, x2, hid32, hid)
+
+
 def _block_rows_backward(blk, W, wgrad, dgrad, accumulate: bool, S: int, attention_backward, sv, st, g, g2, d32, g16, dh16, dqkv, datt, hid32) -> None:
     """the backward of _block_rows, setting (accumulate=False) or adding to the Block's parameter gradients.  sv: what the forward
     kept of the layer (x, a, qkv, att, lse, x2, a2, hid); st: the chunk's gradient buffers at their full Mp rows, which the weight-gradient
@@ -369,6 +429,41 @@ class Prior(nn.Module):
             raise ValueError(f"{who}: conds outside [0, {self.vocab_cond_size})")
         return codes, conds
 
+    def _check_prefix(self, prefix, B: int, who: str):
+        """sample(prefix_codes=): anything with B rows that reshapes to [B, P] (or [B, P, D] where the class has a depth_num_tokens, its last axis D)
+        with 0 <= P < img_num_tokens and ids in [0, V), returned as int64 where it lives (None for P == 0: the call is then the one without a prefix);
+        a ValueError otherwise.  Nothing here looks at the device unless the prefix is there: the range check reads the ids where they are."""
+        if prefix is None:
+            return None
+        T, V, D = self.img_num_tokens, self.vocab_img_size, getattr(self, "depth_num_tokens", None)
+        prefix = torch.as_tensor(prefix)
+        shape = "[B, P, depth_num_tokens = %d]" % D if D is not None else "[B, P]"
+        if prefix.dim() < 1 or prefix.shape[0] != B or prefix.is_complex():
+            raise ValueError(f"{who}: prefix_codes must be {shape} with one row per row of conds (B = {B}), got {tuple(prefix.shape)}")
+        if D is not None and (prefix.dim() < 2 or prefix.shape[-1] != D):
+            raise ValueError(f"{who}: prefix_codes must be {shape} (every given position holds all its codes), got {tuple(prefix.shape)}")
+        P = prefix.numel() // max(B * (D or 1), 1)
+        if P >= T:
+            raise ValueError(f"{who}: prefix_codes gives {P} of the img_num_tokens = {T} positions: at least one must be left to draw (0 <= P < {T})")
+        if P == 0:
+            return None
+        prefix = prefix.reshape((B, P) if D is None else (B, P, D)).to(torch.int64)
+        if int(prefix.min()) < 0 or int(prefix.max()) >= V:
+            raise ValueError(f"{who}: prefix_codes outside [0, {V})")
+        return prefix
+
+    def _place_prefix(self, prefix, forced, codes, logits, who: str):
+        """the prefix on the device of `codes`, checked once against forced_codes (whose first P positions must be the prefix: a ValueError), written
+        into codes[:, :P]; the logits of the given positions, which are not computed, are set to NaN"""
+        prefix = prefix.to(codes.device).contiguous()
+        P = prefix.shape[1]
+        if forced is not None and not torch.equal(forced[:, :P], prefix):
+            raise ValueError(f"{who}: forced_codes and prefix_codes disagree in the first {P} positions")
+        codes[:, :P] = prefix
+        if logits is not None:
+            logits.view(codes.shape[0], self.img_num_tokens, -1)[:, :P] = float("nan")
+        return prefix
+
     # ---- caches -----------------------------------------------------------------------------------
     def _chunk_state(self, cache: str, build, b: int, dt: torch.dtype, dev) -> dict:
         """build(b, dt, dev), the buffers of a chunk of b batch items, kept in the dict attribute `cache` from call to call; a shorter last chunk
@@ -472,9 +567,10 @@ class Prior(nn.Module):
 
     def _sample_graphed(self, B: int, dev, make_state, run_chunk) -> None:
         """sample(graph=True): the chunks of <= MAX_BATCH rows, each as position 0 and one captured position.  run_chunk(st, s, e, positions) runs
-        rows s .. e - 1 in the buffers st = make_state(e - s) by calling positions(T, first, later): first() runs eagerly (it embeds the condition,
-        and it warms the launches and their workspaces), the cursor (device int32) is set to 1, later(cursor), the launches of one position in
-        their cursor forms, is captured once with enh_cursor_advance behind it, and the graph is replayed T - 1 times.  Everything runs on one
+        rows s .. e - 1 in the buffers st = make_state(e - s) by calling positions(T, first, later, start = 0): first() runs eagerly (it embeds the
+        condition, or under prefix_codes prefills `start` positions and runs position `start`, and it warms the launches and their workspaces), the
+        cursor (device int32) is set to start + 1, later(cursor), the launches of one position in
+        their cursor forms, is captured once with enh_cursor_advance behind it, and the graph is replayed T - start - 1 times.  Everything runs on one
         side stream, so the graph is a chain; the current stream waits for it at the end.  Nothing is kept from call to call but what a replay
         that may still be running points at: the graphs, their cursors, the chunk buffers and the workspaces of the launches (`_sample_keep`),
         until the next call replaces them."""
@@ -485,16 +581,16 @@ class Prior(nn.Module):
             side = self._sample_stream = torch.cuda.Stream(dev)
         keep, states = [], {}
 
-        def positions(T, first, later):
+        def positions(T, first, later, start: int = 0):
             first()
-            if T == 1:
+            if T == start + 1:
                 return
-            cursor = torch.ones(1, dtype=torch.int32, device=dev)
+            cursor = torch.full((1,), start + 1, dtype=torch.int32, device=dev)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=side):
                 later(cursor)
                 _C.cursor_advance(cursor)
-            for _ in range(T - 1):
+            for _ in range(T - start - 1):
                 g.replay()
             keep.append((g, cursor))
 

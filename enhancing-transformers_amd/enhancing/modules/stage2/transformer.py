@@ -1,5 +1,6 @@
 """CondTransformer (reference enhancing/modules/stage2/transformer.py:23-95): a condition model, a frozen stage-1 tokenizer and the prior (GPT, or
-RQTransformer over a residual stage 1's codes [B, N, D]); `sample` draws codes on the device and decodes them with the tokenizer; `forward` /
+RQTransformer over a residual stage 1's codes [B, N, D]); `sample` draws codes on the device and decodes them with the tokenizer, `complete`
+keeps the top token rows of given images and draws the rest; `forward` /
 `validation_step` give the teacher-forced logits and the reference's val/total_loss; `loss_and_grads` returns the training loss and leaves the
 gradient of every parameter of the prior on the device (forward_backward); `configure_optimizers` returns the reference's Adam as one device launch
 (engine/optim.py GPTAdam) and `training_step` runs the loss-scaled forward + backward against it (Trainer.fit drives both, on one GPU).
@@ -58,7 +59,8 @@ class CondTransformer(nn.Module):
                use_fp16: bool = True, **kw) -> torch.Tensor:
         """reference transformer.py:78-95, for both priors: GPT draws codes [B, T], RQTransformer [B, T, D] (for a residual tokenizer), and
         `code_shape` is applied to them as the reference does (e.g. [32, 32] or [32, 32, 4]).  **kw goes to the prior's sample (seed, forced_codes,
-        slot0_ln, graph, weights, cache, ...).  The drawn codes are kept in `last_codes`.  An RQ prior that is off the device refuses (sampling runs on a ROCm device only)."""
+        slot0_ln, graph, weights, cache, prefix_codes, ...); prefix_codes may have the code_shape's axes ([B, h', w] or [B, h', w, D]: whole token
+        rows from the top).  The codes, given and drawn, are kept in `last_codes`.  An RQ prior that is off the device refuses (sampling runs on a ROCm device only)."""
         conds = conds.view(conds.shape[0], -1)
         kw.setdefault("return_logits", False)
         _, codes = self.transformer.sample(conds=conds, top_k=top_k, top_p=top_p, softmax_temperature=softmax_temperature, use_fp16=use_fp16, **kw)
@@ -66,6 +68,23 @@ class CondTransformer(nn.Module):
             codes = codes.view(codes.shape[0], *self.code_shape)
         self.last_codes = codes
         return self.stage1_model.decode_codes(codes).clamp(0, 1)
+
+    @torch.no_grad()
+    def complete(self, images: torch.Tensor, conds: torch.Tensor, keep: float = 0.5, **kw) -> torch.Tensor:
+        """image completion: tokenizes `images` with the frozen stage 1 (encode_codes), keeps the first floor(keep * rows) token rows in raster
+        order (rows: code_shape[0], or sqrt(img_num_tokens) without a code_shape) and samples the rest given them (the prior's
+        sample(prefix_codes=): one batched prefill instead of a step per kept token); returns the decoded pixels as `sample` does and leaves the
+        codes, kept and drawn, in `last_codes`.  **kw goes to `sample` (top_k, seed, graph, weights, cache, ...).  keep * rows below 1 keeps
+        nothing (a plain sample); keeping every row is a ValueError: nothing is left to draw."""
+        T = self.transformer.img_num_tokens
+        rows = int(self.code_shape[0]) if self.code_shape is not None else int(round(T ** 0.5))
+        if not float(keep) >= 0.0 or rows < 1 or T % rows:
+            raise ValueError(f"CondTransformer.complete: keep must be >= 0 and the {T} tokens whole rows of a grid of {rows} rows, got keep = {keep}")
+        codes = self.stage1_model.encode_codes(images).detach()
+        B = codes.shape[0]
+        codes = codes.reshape(B, T, -1) if isinstance(self.transformer, RQTransformer) else codes.reshape(B, T)
+        prefix = codes[:, :int(float(keep) * rows) * (T // rows)]
+        return self.sample(conds.to(codes.device), prefix_codes=prefix, **kw)
 
     def get_input(self, batch, key: str) -> torch.Tensor:
         """reference transformer.py:97-105"""

@@ -58,7 +58,7 @@ const char* enh_last_error(void);
  * launch records plain data; the string is composed here, into a thread-local buffer that the next call on the thread overwrites.  Timing labels are
  * taken from this (enhancing/_C.py KernelTimer), so a label is the kernel the planner launched and never a second guess at its decision. */
 const char* enh_last_kernel(void);
-#define ENH_ABI_VERSION 36 /* bumped whenever a signature below changes; the bindings check it at load */
+#define ENH_ABI_VERSION 37/* bumped whenever a signature below changes; the bindings check it at load */
 int enh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -743,6 +743,26 @@ int enh_decode_attention_kv8(const void* qkv, uint8_t* k_codes, uint8_t* k_scale
  * always required; t outside [0, Tmax): nothing is read or written. */
 int enh_decode_attention_kv8_at(const void* qkv, uint8_t* k_codes, uint8_t* k_scales, uint8_t* v_codes, uint8_t* v_scales, int B, int H, int hs,
                                 int Tmax, const int* cursor, int t_offset, void* out, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 sampling, the prefill of given codes (csrc/gpt_prefill_cache.hip; sample(prefix_codes=)): the k / v rows of whole sequences put into
+ * the caches of the decode attentions above in one launch.  qkv is the packed [B S, 3 H hs] output of the fused q | k | v product, the layout
+ * enh_causal_attention_forward reads; row (b, s) goes to slot slot0 + s of batch element b.  hs a multiple of 64 up to 384, slot0 >= 0,
+ * slot0 + S <= Tmax (else ENH_E_SHAPE); qkv and the caches 16-byte aligned; offsets are 64-bit.  Slots outside [slot0, slot0 + S) are not touched.
+ * 16-byte loads and stores, no atomics, no workspace.
+ * ------------------------------------------------------------------------------------------------ */
+/* k_cache / v_cache [B, H, Tmax, hs] and qkv in the format of dtype (ENH_DT_BF16 | ENH_DT_F16 | ENH_DT_F32: the exact mode): a bit-for-bit copy of
+ * the k and v columns, what S successive enh_decode_attention calls at t = slot0 .. slot0 + S - 1 append. */
+int enh_kv_cache_fill(const void* qkv, int B, int S, int H, int hs, int Tmax, int slot0, void* k_cache, void* v_cache, int dtype, void* stream);
+/* The MXFP8 cache of enh_decode_attention_kv8 (codes [B, H, Tmax, hs], scales [B, H, Tmax, hs / 32]); qkv in the 16-bit format of dtype
+ * (ENH_DT_BF16 | ENH_DT_F16).  Every head row is quantized as that entry's append quantizes it (blocks of 32 along hs, the rounding of
+ * enh_mxfp8_quantize), with one difference: a block that holds an infinity or a NaN gets the scale byte 0xff, E8M0's NaN (the append gives 247);
+ * its codes are those of X = 120.  The DEQUANTIZED values e4m3(code) 2^(scale - 127) are written back over the k and v columns of qkv in the
+ * operand format (the q columns are not touched), so that an attention over qkv reads what every later step reads from the slot.  The write-back
+ * is exact in bf16.  In fp16 it is exact whenever the block's amax is >= 2^-7: below that the smallest codes (2^-9 2^X) fall under fp16's
+ * subnormal step 2^-24 and are rounded to it (to nearest even); the cache itself, which is what later steps read, is not affected. */
+int enh_kv_cache_fill_kv8(void* qkv, int B, int S, int H, int hs, int Tmax, int slot0, uint8_t* k_codes, uint8_t* k_scales, uint8_t* v_codes,
+                          uint8_t* v_scales, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stage-2 GPT, teacher-forced forward (csrc/gpt_prefill.hip: the attention, csrc/gpt_rows.hip: the row kernels; reference enhancing/modules/stage2/layers.py:57-97,132-136,193-211 with

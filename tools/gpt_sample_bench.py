@@ -23,7 +23,12 @@ fp8 and the 16-bit step, the three alternating in this process, and the four Blo
 
 --cache fp8 writes profiles/gpt_sample_kv8.txt instead: the step with MXFP8 k / v caches (sample(cache="fp8")) against the step
 with 16-bit caches at batch 1, 4, 16 and 64, alternating windows in this process, under the weights of --weights (h16 or fp8: with fp8 the file is
-profiles/gpt_sample_kv8_w8.txt), and the decode attention alone in both forms with the TB/s of the bytes each actually moves."""
+profiles/gpt_sample_kv8_w8.txt), and the decode attention alone in both forms with the TB/s of the bytes each actually moves.
+
+--prefix P [P ...] writes profiles/gpt_sample_prefix.txt instead: the batched prefill of P given codes (sample(prefix_codes=))
+against the same P positions run by the forced loop (one weight-streaming step and one draw per position), alternating windows in this process, and
+the whole sample(prefix_codes=) against the whole forced run, at batch 1 and 4 under 16-bit and one MX weight format (--weights, default fp8) and
+under 16-bit and MXFP8 caches.  The MX prefill re-reads the Block weights once per piece of 64 rows: the table says how often and what it costs."""
 import argparse
 import math
 import os
@@ -456,6 +461,70 @@ def kv8_mode(m, L, out, weights):
         f.write(text)
 
 
+def prefix_mode(m, L, out, prefixes, mx, reps=3):
+    """--prefix: the prefill of P given codes against the forced loop over the same P positions, and the whole calls; writes
+    profiles/gpt_sample_prefix.txt"""
+    C, V, T, H = m.embed_dim, m.vocab_img_size, m.img_num_tokens, m.n_heads
+    dt = torch.float16
+    blocks = 12 * C * C * L
+    wb = {"h16": blocks * 2, "fp8": blocks + blocks // 32, "fp6": blocks * 3 // 4 + blocks // 32, "fp4": blocks // 2 + blocks // 32}
+    fs = lambda v: f"{v[1] / 1e3:.3f} [{v[0] / 1e3:.3f} .. {v[2] / 1e3:.3f}]"
+    st3 = lambda v: (min(v), statistics.median(v), max(v))
+    lines = [f"stage-2 GPT sampling, a batched prefill of P given codes against the forced loop over the same P positions, on {torch.cuda.get_device_name(0)}: "
+             f"C={C} layers={L} heads={H} V={V} T={T}, fp16 activations; Block weights per pass {wb['h16'] / 1e9:.2f} GB (16-bit) / {wb[mx] / 1e9:.2f} GB ({mx})",
+             f"prefill | loop: seconds, median [min .. max] of {reps} alternating windows in one process after a warm-up of both; a window is ONE prefill of all P",
+             "positions (every layer's k / v rows into the caches; the last layer stops behind its fill) or ONE pass of the existing loop over positions 0 .. P - 1",
+             "(a step and a draw per position).  whole: seconds, [min .. max] of 2 alternating calls of sample(prefix_codes=codes[:, :P]) and of",
+             "sample(forced_codes=codes), top_k 100, no logits returned.  passes: how often the prefill reads the Block weights (16-bit: once, enh_gemm_h16 over all",
+             f"rows; {mx}: once per piece of 64 rows, ceil(b P / 64) times); pass GB = passes x the Block weights",
+             f"{'weights':>7} {'cache':>5} {'batch':>5} {'P':>4} {'rows':>5} {'passes':>6} {'pass GB':>8} {'prefill s [min .. max]':>26} {'loop s [min .. max]':>26} {'loop/prefill':>12} "
+             f"{'beyond spread':>13} {'whole prefix s':>18} {'whole forced s':>18} {'forced/prefix':>13}"]
+    med = {}
+    for w in ("h16", mx):
+        for c in ("h16", "fp8"):
+            for b in (1, 4):
+                st = m._decode_state(b, dt, "cuda", weights=w, cache=c)
+                conds = torch.randint(0, 1000, (b,), device="cuda")
+                codes = torch.randint(0, V, (b, T), device="cuda")
+                drawn = torch.empty(b, T, dtype=torch.int64, device="cuda")
+                for P in prefixes:
+                    def prefill(i):
+                        m._prefill(st, conds, codes[:, :P])
+
+                    def loop(i):
+                        for t in range(P):
+                            m._decode_step(st, t, conds if t == 0 else codes[:, t - 1])
+                            _C.sample_logits(st["logits"], drawn[:, t], top_k=100, top_p=None, seed=1, step=t)
+                    a, l = ab(prefill, loop, inner=1, reps=reps)
+                    med[w, c, b, P] = a[1]
+                    kw = dict(top_k=100, seed=1, return_logits=False, weights=w, cache=c)
+                    wp, wf = [], []
+                    for _ in range(2):
+                        wp.append(timed(lambda i: m.sample(conds.view(b, 1), prefix_codes=codes[:, :P], **kw), 1))
+                        wf.append(timed(lambda i: m.sample(conds.view(b, 1), forced_codes=codes, **kw), 1))
+                    passes = 1 if w == "h16" else -(-b * P // 64)
+                    lines.append(f"{w:>7} {c:>5} {b:>5} {P:>4} {b * P:>5} {passes:>6} {passes * wb[w] / 1e9:>8.1f} {fs(a):>26} {fs(l):>26} {l[1] / a[1]:>12.1f} "
+                                 f"{'yes' if a[2] < l[0] else 'no':>13} {f'{min(wp) / 1e3:.2f} .. {max(wp) / 1e3:.2f}':>18} {f'{min(wf) / 1e3:.2f} .. {max(wf) / 1e3:.2f}':>18} "
+                                 f"{statistics.median(wf) / statistics.median(wp):>13.2f}")
+                    print(lines[-1], flush=True)
+                del st
+                torch.cuda.empty_cache()
+    lines.append("beyond spread: the slowest prefill window is faster than the fastest loop window of the same point")
+    lines.append(f"what the re-reads cost: the {mx} prefill against the 16-bit prefill of the same point (medians), and the TB/s of its weight passes alone:")
+    for c in ("h16", "fp8"):
+        for b in (1, 4):
+            for P in prefixes:
+                passes = -(-b * P // 64)
+                lines.append(f"  cache {c:>3} batch {b} P {P:>4}: {mx} {med[mx, c, b, P] / 1e3:.3f} s / 16-bit {med['h16', c, b, P] / 1e3:.3f} s = "
+                             f"{med[mx, c, b, P] / med['h16', c, b, P]:.2f}x; {passes} passes of {wb[mx] / 1e9:.2f} GB in that time: "
+                             f"{passes * wb[mx] / (med[mx, c, b, P] * 1e-3) / 1e12:.2f} TB/s")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -469,9 +538,12 @@ def main():
     ap.add_argument("--cache", choices=("h16", "fp8"), default="h16", help="fp8: instead of the tables, the step with MXFP8 k / v caches against the step "
                     "with 16-bit caches under the weights of --weights, and the decode attention alone (profiles/gpt_sample_kv8.txt, with --weights fp8 "
                     "profiles/gpt_sample_kv8_w8.txt, with --weights fp6 profiles/gpt_sample_kv8_w6.txt, with --weights fp4 profiles/gpt_sample_kv8_w4.txt)")
+    ap.add_argument("--prefix", type=int, nargs="+", default=None, metavar="P", help="instead of the tables: the batched prefill of P given codes against the forced "
+                    "loop over the same positions, and the whole calls, under 16-bit weights and the MX format of --weights (default fp8) and under both caches "
+                    "(profiles/gpt_sample_prefix.txt); the shipped points are --prefix 256 768")
     args = ap.parse_args()
     if args.out is None:
-        name = ("gpt_sample_graph.txt" if args.graph else dict(h16="gpt_sample_kv8.txt", fp8="gpt_sample_kv8_w8.txt", fp6="gpt_sample_kv8_w6.txt", fp4="gpt_sample_kv8_w4.txt")[args.weights]
+        name = ("gpt_sample_prefix.txt" if args.prefix else "gpt_sample_graph.txt" if args.graph else dict(h16="gpt_sample_kv8.txt", fp8="gpt_sample_kv8_w8.txt", fp6="gpt_sample_kv8_w6.txt", fp4="gpt_sample_kv8_w4.txt")[args.weights]
                 if args.cache == "fp8" else dict(h16="gpt_sample.txt", fp8="gpt_sample_fp8.txt", fp6="gpt_sample_fp6.txt", fp4="gpt_sample_fp4.txt")[args.weights])
         args.out = os.path.join(ROOT, "profiles", name)
     C, H, V, T, L = 6144, 16, 8192, 1024, args.layers
@@ -480,6 +552,10 @@ def main():
         m = GPT(vocab_cond_size=1000, vocab_img_size=V, embed_dim=C, cond_num_tokens=1, img_num_tokens=T, n_heads=H, n_layers=L)
         with torch.no_grad():
             m.pos_emb_code.normal_(0, 0.02)
+    if args.prefix:
+        if not all(0 < P < T for P in args.prefix):
+            raise SystemExit(f"--prefix: every P must be in (0, {T})")
+        return prefix_mode(m, L, args.out, args.prefix, "fp8" if args.weights == "h16" else args.weights)
     if args.graph:
         return graph_mode(m, L, args.out)
     if args.cache == "fp8":
