@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void gpt_prefill_relu_sq_kernel(const float* _
     unpack8<OT>(reinterpret_cast<const u32x4*>(y_)[i], f);
   }
 #pragma unroll
-  for (int k = 0; k < 8; ++k) { f[k] = fmaxf(f[k], 0.f); f[k] = f[k] * f[k]; }
+  for (int k = 0; k < 8; ++k) { f[k] = f[k] < 0.f ? 0.f : f[k]; f[k] = f[k] * f[k]; }      // (not fmaxf: fmaxf(NaN, 0) is 0, and a NaN of the fp16 forward must reach the loss)
   if constexpr (Y32) {
     const f32x4 a = {f[0], f[1], f[2], f[3]}, c = {f[4], f[5], f[6], f[7]};
     reinterpret_cast<f32x4*>(y_)[2 * i] = a;

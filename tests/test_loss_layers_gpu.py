@@ -25,13 +25,13 @@ Measured on MI355X (largest error / floor, bf16 | fp16, over this file and the o
   conv_pack_weight / blur4x4_nhwc<F16, 13 | 5> / blur_nhwc / lrelu_gate_h16 / img_to_nhwc8 / nhwc8_to_img / stddev_fwd | bwd / vgg_conv1_fwd | bwd /
   maxpool2_fwd | bwd / lpips_head_fwd | bwd<F16, 1 | 2 | 4 | 8>, and im2col / col2im<1>."""
 import ctypes
-import math
 import time
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+from nonfinite_util import check_overflow, floor_bound, pow2_scale as _pow2_scale
 from util import floor16, h16r, rel
 
 pytestmark = pytest.mark.gpu
@@ -354,23 +354,9 @@ def test_lpips_head_layer(ops, dt, HW, C):
 # fp16 overflow: +-inf exactly where the correctly rounded result is +-inf
 # ---------------------------------------------------------------------------------------------
 def _check_overflow(got, ref, what):
-    """got: the kernel's fp16 output (any layout, as f32 on the host), ref: the exact result in float64, same layout"""
-    want = ref.to(F16)
-    inf = torch.isinf(want)
-    assert 0.001 <= inf.float().mean().item() <= 0.9, f"{what}: the case must overflow in part ({inf.float().mean().item():.4f})"
-    assert not torch.isnan(got).any(), f"{what}: NaN"
-    assert torch.equal(torch.isinf(got), inf) and torch.equal(got[inf], want[inf].float()), f"{what}: +-inf must be exactly where fp16(ref) is"
-    assert not (got.abs() == 65504.0)[inf].any()
-    fin = ~inf
-    e = rel(got[fin], ref[fin]) / floor16(ref[fin], F16)
-    print(f"overflow {what}: {inf.float().mean().item() * 100:.1f} % inf, finite part {e:.3f} x floor")
-    assert e <= 1.25, (what, e)
-
-
-def _pow2_scale(unit, target=4e4):
-    """the power of two that takes the rms of a result computed on unit-scale operands to ~target (4e4: ~10-30 % of the results past 65520); scaling an
-    fp16 operand by it is exact"""
-    return 2.0 ** round(math.log2(target / unit.pow(2).mean().sqrt().item()))
+    """got: the kernel's fp16 output (any layout, as f32 on the host), ref: the exact result in float64, same layout (nonfinite_util.check_overflow with
+    this file's bound: the finite part within 1.25 x its rounding floor)"""
+    check_overflow(got, ref, floor_bound(1.25, F16), what, exact=True)
 
 
 # (B, H, Cin, Cout, k) and the kernels each reaches (conv_igemm.hip / conv_pointwise.hip dispatch):
